@@ -11,7 +11,8 @@ A "step" = one full par_cast of the workload into a framebuffer resident in HBM.
 Launch for N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
               or plain `python bench.py --gpus N`, which starts those N ranks itself.  Either way WORLD_SIZE must equal
               --gpus and the host must show N GPUs, else the run exits non-zero instead of reporting another N.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes the frame the last timed step rendered (dump_framebuffer):
+the inputs are fixed by the arguments (seeded scene construction, --seed), so two builds can be compared frame for frame.
 """
 import argparse
 import ctypes
@@ -88,6 +89,29 @@ def cpu_baseline(pkg, build_scene, nx, ny, target_seconds=12.0, max_spp=1000):
                     "(same row granularity as lib.rs:326-330) on the cores the cgroup quota allows"}
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_framebuffer(out_dir, fb, budget=DUMP_BYTES):
+    """--dump-outputs: the frame the last timed step produced (float32 [ny, nx, 3]) as out_dir/framebuffer.npy.  A frame too
+    large for `budget` is written as a fixed sample instead: framebuffer_sample.npy (float32 [k, 3]: k pixels drawn without
+    replacement by numpy's default_rng(0), in row-major order) and framebuffer_sample_pixel.npy (float64 [k]: their row-major
+    indices).  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    fb = np.ascontiguousarray(fb, dtype=np.float32)
+    header = 4096   # room for the two .npy headers (128 B each)
+    if fb.nbytes + header <= budget:
+        np.save(os.path.join(out_dir, "framebuffer.npy"), fb)
+        return ["framebuffer"]
+    flat = fb.reshape(-1, 3)
+    k = (budget - header) // (3 * 4 + 8)
+    pick = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "framebuffer_sample.npy"), flat[pick])
+    np.save(os.path.join(out_dir, "framebuffer_sample_pixel.npy"), pick.astype(np.float64))
+    return ["framebuffer_sample", "framebuffer_sample_pixel"]
+
+
 def rank_px_big(samples):
     """rtg_launch.inc: programs with a second flat program (book-2) take the pool-2 kernel from 32 M samples per launch on."""
     return samples >= (32 << 20) and os.environ.get("RTG_POOL2", "1") != "0"
@@ -145,10 +169,15 @@ def main():
                          "book-2 800x800x1000) that are timed in the same process after the headline loop")
     ap.add_argument("--verify", action="store_true",
                     help="rank 0 also renders the frame unsharded and checks the reduced frame bit-for-bit")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, rank 0 writes the frame of the last one to DIR/framebuffer.npy (float32 [ny, nx, 3]; "
+                         "a frame above 64 MB as a fixed seeded sample of its pixels)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     # RTG_BENCH_BACKEND=gloo is a TEST hook: it lets the N>1 code path run with several ranks on ONE GPU
     # (RCCL refuses two ranks per device); the framebuffer is then reduced through host memory.
     backend = os.environ.get("RTG_BENCH_BACKEND", "nccl")
@@ -275,6 +304,9 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [{"rank": r, "kernel_ms_avg": float(v[0]), "samples": int(v[1]), "reduce_ms_avg": float(v[2])} for r, v in enumerate(allr)]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # rank 0 holds the assembled frame; the copy to the host is outside the timed window
+        dumped = dump_framebuffer(args.dump_outputs, fb.cpu().numpy())
 
     # Secondary anchors of the default N = 1 run, timed in this process AFTER the headline loop (they cannot disturb it):
     # the frame north_star's target names (C3's 1200x800x500, here on ONE GPU: what `--gpus 2/4/8` is compared against) and
@@ -427,6 +459,8 @@ def main():
             line["also"] = also
         if verified is not None:
             line["verified_bit_exact_vs_unsharded"] = verified
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(pkg, build_scene, nx, ny)
         print(json.dumps(line))

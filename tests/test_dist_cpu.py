@@ -70,3 +70,31 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode != 0
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_refuses_zero_steps():
+    """--steps is the number of timed steps and ms_per_step is measured over them: none at all is refused before any GPU is touched."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: a frame within the budget is written whole; a larger one as the same seeded pixel sample every
+    time, with its row-major indices, files and all within the budget."""
+    from conftest import assert_bit_equal
+    import bench
+    fb = np.random.default_rng(1).random((60, 80, 3), dtype=np.float32)
+    assert bench.dump_framebuffer(str(tmp_path / "whole"), fb) == ["framebuffer"]
+    assert_bit_equal(np.load(tmp_path / "whole" / "framebuffer.npy"), fb, "whole frame")
+    budget = 4096 + 20 * 1000
+    for d in ("a", "b"):
+        assert bench.dump_framebuffer(str(tmp_path / d), fb, budget=budget) == ["framebuffer_sample", "framebuffer_sample_pixel"]
+        assert sum(p.stat().st_size for p in (tmp_path / d).iterdir()) <= budget
+    pix = np.load(tmp_path / "a" / "framebuffer_sample_pixel.npy")
+    smp = np.load(tmp_path / "a" / "framebuffer_sample.npy")
+    assert pix.dtype == np.float64 and smp.dtype == np.float32 and pix.shape == (1000,) and smp.shape == (1000, 3)
+    assert (np.diff(pix) > 0).all() and pix[-1] < 60 * 80
+    assert_bit_equal(smp, fb.reshape(-1, 3)[pix.astype(np.int64)], "sampled pixels")
+    for name in ("framebuffer_sample", "framebuffer_sample_pixel"):
+        assert (tmp_path / "a" / (name + ".npy")).read_bytes() == (tmp_path / "b" / (name + ".npy")).read_bytes()

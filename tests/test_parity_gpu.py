@@ -570,6 +570,24 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path, scaling, mode):
     assert line["slowest_rank_kernel_ms"] == max(r["kernel_ms_avg"] for r in line["per_rank"]) <= line["ms_per_step"] * 1.05
 
 
+def test_bench_dumps_the_frame_it_timed(tmp_path, pkg, oracle):
+    """`--dump-outputs DIR` writes the frame of the last of `--steps` timed steps: bit for bit the oracle's frame of the same
+    scene, size, spp and seed."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nx, ny = 160, 96
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--nx", str(nx), "--ny", str(ny),
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dumped_outputs"] == ["framebuffer"]
+    b = oracle.builder()
+    world, cam, _ = pkg.scenes.random_scene(b, nx, ny)
+    assert_bit_equal(np.load(tmp_path / "framebuffer.npy"), b.scene(world).par_cast(cam, nx, ny, 50, seed=0xDEADBEEF), "bench.py --dump-outputs")
+
+
 def test_bench_gpus_flag_is_self_sufficient(tmp_path, gpu):
     """`python bench.py --gpus N` WITHOUT a launcher starts its own N ranks (torch.distributed.run, one per GPU) and reports
     n_gpus == N; it never reports another N than the one asked for: with fewer GPUs than ranks (RCCL: one rank per device)
