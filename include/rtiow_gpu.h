@@ -66,16 +66,33 @@ typedef struct rtg_params {
   uint32_t tile_w, tile_h; /* multiples of 8; 0 -> 16                                         */
   uint32_t rank, nranks;   /* nranks 0 -> 1                                                   */
   uint32_t flags;          /* RTG_FLAG_*                                                      */
-  uint32_t reserved;
+  uint32_t sample_begin;   /* RTG_FLAG_RESUME: first sample this call renders (ignored without)  */
 } rtg_params;
 
 #define RTG_FLAG_COUNTERS 1u /* fill rtg_stats counters (instrumented kernel variant, slower) */
 #define RTG_FLAG_TRACE_KERNEL 2u /* rtg_debug_samples: trace the production ray-pool kernel instead of the one-lane probe */
+#define RTG_FLAG_PARTIAL 4u /* leave the UNNORMALISED running sum of the samples in out (skip lib.rs:374's division)  */
+#define RTG_FLAG_RESUME 8u  /* out holds the running sum of samples [0, sample_begin): render [sample_begin, ns) only */
+
+/* Progressive rendering (a frame in sample slices).  The RNG is keyed by (seed, pixel, sample index), so the first n
+ * samples of an ns-spp frame are exactly the samples of an n-spp frame, and the per-pixel sum is the reference's left fold
+ * (lib.rs:365-374).  RTG_FLAG_PARTIAL ends a call without dividing: `out` keeps the f32 running sum of the samples rendered
+ * so far.  RTG_FLAG_RESUME continues that fold: `out` holds the running sum of samples [0, sample_begin) of every pixel the
+ * call renders (as a PARTIAL call left it), and the call adds samples [sample_begin, ns) to it in order.
+ *   - RESUME without PARTIAL divides by ns at the end: the frame is finished, bit-identical to one call with that ns.
+ *   - sample_begin == ns renders nothing; without PARTIAL the call only divides (the resolve step: run it on a copy of
+ *     the running sum for a preview that is bit-identical to par_cast(ns = sample_begin)).
+ *   - sample_begin > ns: RTG_ERR_INVALID, nothing written or enqueued.  sample_begin == 0: as if RESUME were not set.
+ *   - Pixels of other ranks / tiles stay untouched, as without the flags.  rtg_stats.samples counts owned pixels x
+ *     (ns - sample_begin); every counter summed over the slices of a frame equals the one-call counter.
+ * The slices of one frame must agree on camera, nx / ny, seed, max_bounces, t_near and the tiling (tile_w / tile_h, rank /
+ * nranks); the library cannot check this.  rtg_par_cast, rtg_par_cast_device and rtg_par_cast_multi honour both flags;
+ * rtg_debug_samples rejects them (RTG_ERR_INVALID). */
 
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */
-  uint64_t samples;     /* pixels rendered by this call x ns                                   */
+  uint64_t samples;     /* pixels rendered by this call x its samples (ns - sample_begin)     */
   uint64_t aabb_tests;  /* Aabb::hit calls        (aabb.rs:16)                                 */
   uint64_t prim_tests;  /* Sphere/Rect::hit calls (object.rs:84,185)                           */
   uint64_t shaded_hits; /* hit_top() == Some      (lib.rs:73)                                  */

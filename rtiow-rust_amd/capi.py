@@ -7,6 +7,7 @@ same calls.
 """
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -17,6 +18,8 @@ c_u8p = C.POINTER(C.c_uint8)
 INVALID_ID = 0xFFFFFFFF
 FLAG_COUNTERS = 1
 FLAG_TRACE_KERNEL = 2
+FLAG_PARTIAL = 4   # leave the unnormalised running sum of the samples in the framebuffer
+FLAG_RESUME = 8    # the framebuffer holds the running sum of samples [0, sample_begin): render [sample_begin, ns)
 
 
 class Camera(C.Structure):
@@ -31,7 +34,7 @@ class Params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_uint32), ("ny", C.c_uint32), ("ns", C.c_uint32),
                 ("max_bounces", C.c_uint32), ("t_near", C.c_float), ("seed", C.c_uint64),
                 ("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("rank", C.c_uint32),
-                ("nranks", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+                ("nranks", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -44,7 +47,10 @@ class Stats(C.Structure):
 
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
-                nranks=1, flags=0):
+                nranks=1, flags=0, sample_begin=0, partial=False, resume=False):
+    """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
+    RTG_FLAG_RESUME)."""
+    flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0)
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.nx, p.ny, p.ns = nx, ny, ns
@@ -52,7 +58,29 @@ def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_
     p.t_near = t_near
     p.seed = seed
     p.tile_w, p.tile_h, p.rank, p.nranks, p.flags = tile_w, tile_h, rank, nranks, flags
+    p.sample_begin = sample_begin
     return p
+
+
+def _device_ptr(x):
+    return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
+_hip = None
+
+
+def _hip_runtime():
+    """The HIP runtime librtiow_gpu.so itself links (device-to-device copies of Scene.progressive)."""
+    global _hip
+    if _hip is None:
+        _hip = C.CDLL("libamdhip64.so")
+        _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    return _hip
+
+
+def _resumes(kw):
+    return bool(kw.get("resume")) and kw.get("sample_begin", 0) > 0
 
 
 # error codes of include/rtiow_gpu.h
@@ -182,11 +210,15 @@ class Backend:
                                      focus_dist, exposure[0], exposure[1], C.byref(cam)))
         return cam
 
-    def par_cast_multi(self, scenes, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, **kw):
+    def par_cast_multi(self, scenes, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, **kw):
         """rtg_par_cast_multi: one scene handle per device (the same world flattened on each), tiles sharded over
-        them, ONE RCCL reduce(sum) of the float3 framebuffer inside the library.  Returns the assembled frame."""
+        them, ONE RCCL reduce(sum) of the float3 framebuffer inside the library.  Returns the assembled frame.
+        resume=True, sample_begin=k: `out` holds the running sum of samples [0, k) (as a partial=True call left it)."""
         p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
-        out = np.zeros((ny, nx, 3), dtype=np.float32)
+        if out is None:
+            if _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
+            out = np.zeros((ny, nx, 3), dtype=np.float32)
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         arr = (C.c_void_p * len(scenes))(*[s.h for s in scenes])
@@ -391,9 +423,13 @@ class Scene:
         return args
 
     def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, **kw):
-        """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance."""
+        """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
+        One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
+        continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h)."""
         p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
         if out is None:
+            if _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
             out = np.zeros((ny, nx, 3), dtype=np.float32)
         st = Stats()
         st.struct_size = C.sizeof(Stats)
@@ -402,12 +438,74 @@ class Scene:
         self.be.check(self.be._par_cast(*args))
         return (out, st.as_dict()) if stats else out
 
-    def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False):
+    def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
+                        resume=None):
+        """rtg_par_cast_device.  sample_begin / partial / resume, when given, override those of `params` (a copy)."""
+        if sample_begin is not None or partial is not None or resume is not None:
+            q = Params()
+            C.pointer(q)[0] = params
+            if sample_begin is not None:
+                q.sample_begin = sample_begin
+            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME)):
+                if on is not None:
+                    q.flags = (q.flags | bit) if on else (q.flags & ~bit)
+            params = q
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         self.be.check(self.be._par_cast_device(self.h, C.byref(camera), C.byref(params), d_out_ptr, stream,
                                                C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+    def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None, **kw):
+        """Render a frame `step` samples at a time (include/rtiow_gpu.h progressive rendering).  Yields (n_done, preview)
+        after each slice: the preview is bit-identical to par_cast(ns = n_done), and the one at n_done == ns is the final
+        image, bit-identical to par_cast(ns).  Stops at ns, or after the first slice that ends past `budget_s` seconds.
+        Host frames (default): the running sum lives in `out`, a float32 [ny, nx, 3] array (default: zeros); every preview
+        is a new array.  Device frames: `out` and `preview` are device buffers of nx * ny * 3 floats on the scene's device
+        (a pointer, or an object with data_ptr() such as a torch tensor) and `stream` a hipStream_t (int, an object with
+        .cuda_stream, or None = the default stream): the same loop over par_cast_device, every slice, copy and resolve
+        enqueued on that stream; `preview` is rewritten by each slice.  **kw: tiling / max_bounces / t_near."""
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        if out is not None and not isinstance(out, np.ndarray):
+            if preview is None:
+                raise ValueError("a device running sum needs a device preview buffer (preview=)")
+            yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, kw)
+            return
+        acc = np.zeros((ny, nx, 3), dtype=np.float32) if out is None else out
+        t0 = time.perf_counter()
+        done = 0
+        while done < ns:
+            end = min(ns, done + step)
+            self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, **kw)
+            done = end
+            frame = acc.copy()   # resolve a copy: the running sum goes on
+            self.par_cast(camera, nx, ny, done, seed=seed, out=frame, sample_begin=done, resume=True, **kw)
+            yield done, frame
+            if budget_s is not None and time.perf_counter() - t0 >= budget_s:
+                return
+
+    def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, kw):
+        hip = _hip_runtime()
+        d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
+        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        t0 = time.perf_counter()
+        done = 0
+        while done < ns:
+            end = min(ns, done + step)
+            self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True, **kw),
+                                 d_acc, hs)
+            done = end
+            rc = hip.hipMemcpyAsync(d_preview, d_acc, nx * ny * 3 * 4, 3, hs)   # 3 = hipMemcpyDeviceToDevice
+            if rc != 0:
+                raise RtError(ERR_DEVICE, "hipMemcpyAsync(preview) failed: %d" % rc)
+            self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, **kw), d_preview, hs)
+            yield done, preview
+            if budget_s is not None:
+                if hip.hipStreamSynchronize(hs) != 0:
+                    raise RtError(ERR_DEVICE, "hipStreamSynchronize failed")
+                if time.perf_counter() - t0 >= budget_s:
+                    return
 
     def debug_hit_top(self, rays, seed=1, t_near=0.001):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)

@@ -338,6 +338,18 @@ __global__ void fold_samples_kernel(DevParams P, ChunkMode cm, PixMap pm, float*
   o[0] = col.x, o[1] = col.y, o[2] = col.z;
 }
 
+// the resolve step of a progressive frame (include/rtiow_gpu.h RTG_FLAG_RESUME with sample_begin = ns): the running sum of
+// every pixel this rank owns divided by the frame's sample count, as the last fold pass would have done (lib.rs:374)
+__global__ void resolve_sum_kernel(DevParams P, PixMap pm, uint32_t pix_work, float* __restrict__ out) {
+  uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= pix_work) return;
+  uint32_t x, row;
+  if (!work_to_pixel(P, pm, w, x, row)) return;
+  float* o = out + 3ull * ((size_t)row * P.nx + x);
+  const V3 col = sdiv(mk(o[0], o[1], o[2]), (float)P.ns);
+  o[0] = col.x, o[1] = col.y, o[2] = col.z;
+}
+
 struct PoolTuning {
   uint32_t refill_min;   // idle lanes before the wave services (finish / shade / refill)
   uint32_t sphere_min;   // parked lanes before a sphere pass

@@ -173,6 +173,20 @@ static int ctx_release(rtg_scene* s, hipStream_t stream) {
   return RTG_OK;
 }
 
+// Progressive rendering (include/rtiow_gpu.h RTG_FLAG_PARTIAL / RTG_FLAG_RESUME): the samples one call renders and what it does
+// at the end.  The default is the whole frame: samples [0, ns), divided by ns.
+struct SampleSlice {
+  uint32_t begin = 0;   // first sample this call renders; the framebuffer holds the running sum of [0, begin) when it is > 0
+  bool divide = true;   // false under RTG_FLAG_PARTIAL: the running sum stays in the framebuffer
+  bool sliced() const { return begin != 0u || !divide; }
+};
+static SampleSlice slice_of(const rtg_params* p) {
+  SampleSlice sl;
+  if (p->flags & RTG_FLAG_RESUME) sl.begin = p->sample_begin;
+  if (p->flags & RTG_FLAG_PARTIAL) sl.divide = false;
+  return sl;
+}
+
 #include "rtg_launch.inc"
 
 template <typename T>
@@ -655,6 +669,7 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   d.nranks = p->nranks ? p->nranks : 1u;
   d.rank = p->rank;
   if (d.rank >= d.nranks) return fail(RTG_ERR_INVALID, "rank >= nranks");
+  if ((p->flags & RTG_FLAG_RESUME) && p->sample_begin > p->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   *out = d;
   return RTG_OK;
 }
@@ -683,6 +698,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   if ((rc = ctx_acquire(s))) return rc;
   DevCamera cam = to_dev(camera);
   bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
+  const SampleSlice sl = slice_of(params);
   // From here on work of this frame may sit on `stream`: a failure must not hand the context out again while kernels of the
   // partly enqueued frame still run (they read d_consts / d_lpt / the scratch the next call would rewrite) -- drain first.
 #define HIP_TRY_CTX(expr)                               \
@@ -710,7 +726,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   }
 #endif
   if (stats) HIP_TRY_CTX(hipEventRecord(s->cx->ev0, stream));
-  HIP_TRY_CTX(count ? launch_render<true>(s, cam, d, d_out, stream) : launch_render<false>(s, cam, d, d_out, stream));
+  HIP_TRY_CTX(count ? launch_render<true>(s, cam, d, d_out, stream, sl) : launch_render<false>(s, cam, d, d_out, stream, sl));
   if ((rc = ctx_release(s, stream))) {
     (void)hipStreamSynchronize(stream);
     return rc;
@@ -733,7 +749,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
     }
 #endif
     stats->kernel_ms = ms;
-    stats->samples = owned_pixels(d) * d.ns;
+    stats->samples = owned_pixels(d) * (d.ns - sl.begin);
     unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (count) HIP_TRY(hipMemcpy(h, s->cx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
     stats->aabb_tests = h[0], stats->prim_tests = h[1], stats->shaded_hits = h[2], stats->rays = h[3], stats->draws = h[4];
@@ -789,15 +805,21 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
 
 int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* params, float* out_rgb, rtg_stats* stats) {
   if (!s || !params || !out_rgb) return fail(RTG_ERR_INVALID, "null argument");
+  {
+    DevParams d;  // (refused before anything is uploaded)
+    const int rc0 = check_params(s, camera, params, &d);
+    if (rc0) return rc0;
+  }
   HIP_TRY(hipSetDevice(s->device));
   size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float);
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
   hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, bytes ? bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
   float* d_out = s->d_frame;
-  // pixels of other ranks stay as the caller left them; a single rank overwrites every pixel
-  const bool partial = params->nranks > 1;
-  if (partial) e = hipMemcpy(d_out, out_rgb, bytes, hipMemcpyHostToDevice);
+  // pixels of other ranks stay as the caller left them; a single rank overwrites every pixel -- unless it resumes a progressive
+  // frame, whose running sums are in out_rgb
+  const bool upload = params->nranks > 1 || slice_of(params).begin != 0u;
+  if (upload) e = hipMemcpy(d_out, out_rgb, bytes, hipMemcpyHostToDevice);
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();

@@ -16,9 +16,11 @@ __device__ __forceinline__ void flush_counts(const Counts& c, uint32_t draws, un
 // par_cast (lib.rs:363-376): one lane owns one pixel and folds its ns samples IN ORDER
 // (iter::Sum is a left fold from (0,0,0), vec3.rs:195-203), then divides by ns.
 // Block = 16x16 pixels, each wave an 8x8 sub-tile (primary rays of a wave stay coherent).
-template <uint32_t FEAT, bool COUNT>
-__global__ __launch_bounds__(256) void render_kernel(DevScene sc, DevCamera cam, DevParams P, float* out,
-                                                     unsigned long long* counters) {
+// SLICE (render_slice_kernel only, include/rtiow_gpu.h progressive rendering): the fold starts at sample s_begin from the
+// running sum `out` holds (+0 when s_begin = 0) and divides only when `divide` -- the plain instantiations do not see it.
+template <uint32_t FEAT, bool COUNT, bool SLICE>
+__device__ __forceinline__ void render_pixel(const DevScene& sc, const DevCamera& cam, const DevParams& P, float* out,
+                                             unsigned long long* counters, uint32_t s_begin, bool divide) {
   const uint32_t nbx = (P.nx + 15u) / 16u;
   const uint32_t bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
   const uint32_t tiles_x = (P.nx + P.tile_w - 1u) / P.tile_w;
@@ -33,16 +35,34 @@ __global__ __launch_bounds__(256) void render_kernel(DevScene sc, DevCamera cam,
   Counts cnt = {0, 0, 0, 0};
   uint32_t total_draws = 0;
   V3 col = mk(0.f, 0.f, 0.f);
-  for (uint32_t s = 0; s < P.ns; s++) {
+  uint32_t s0 = 0;
+  if (SLICE && s_begin != 0u) {
+    const float* i = out + 3ull * ((size_t)row * P.nx + x);
+    col = mk(i[0], i[1], i[2]), s0 = s_begin;
+  }
+  for (uint32_t s = s0; s < P.ns; s++) {
     uint32_t bounces, draws;
     V3 c = sample_color<FEAT, COUNT>(sc, cam, P, x, y, s, cnt, bounces, draws);
     col = vadd(col, c);
     if (COUNT) total_draws += draws;
   }
-  col = sdiv(col, (float)P.ns);  // lib.rs:374
+  if (!SLICE || divide) col = sdiv(col, (float)P.ns);  // lib.rs:374
   float* o = out + 3ull * ((size_t)row * P.nx + x);
   o[0] = col.x, o[1] = col.y, o[2] = col.z;
   if (COUNT) flush_counts(cnt, total_draws, counters);
+}
+
+template <uint32_t FEAT, bool COUNT>
+__global__ __launch_bounds__(256) void render_kernel(DevScene sc, DevCamera cam, DevParams P, float* out,
+                                                     unsigned long long* counters) {
+  render_pixel<FEAT, COUNT, false>(sc, cam, P, out, counters, 0u, true);
+}
+
+// the same for a slice of a progressive frame: samples [s_begin, P.ns), `divide` = 0 under RTG_FLAG_PARTIAL
+template <uint32_t FEAT, bool COUNT>
+__global__ __launch_bounds__(256) void render_slice_kernel(DevScene sc, DevCamera cam, DevParams P, float* out,
+                                                           unsigned long long* counters, uint32_t s_begin, uint32_t divide) {
+  render_pixel<FEAT, COUNT, true>(sc, cam, P, out, counters, s_begin, divide != 0u);
 }
 
 template <uint32_t FEAT>

@@ -106,9 +106,11 @@ static PoolGeometry pool_geometry(const rtg_scene* s, uint64_t total_work, int b
 }
 
 // Lean scenes, ray-pool kernel (rt_pool.h): one persistent 1024-thread workgroup per CU.
+// `sl`: the samples [sl.begin, d.ns) of a progressive frame's slice -- pass sizing, chunking and launch geometry follow this
+// call's samples, not the frame's.
 template <bool COUNT>
 static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
-                              hipStream_t stream) {
+                              hipStream_t stream, const SampleSlice& sl) {
   uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
   uint32_t tiles = tiles_x * tiles_y;
   uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
@@ -120,22 +122,27 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   // Sample-chunk mode (see rt_pool.h).  Default: one sample per work item.  Work items are then ~100x more numerous than
   // path slots, so the end-of-frame tail (slots finishing their last item while the queue is empty) is negligible;
   // measured on C2: 40.6 ms with one pixel (50 samples) per item, 23.5 ms with one sample per item.
-  uint64_t n_chunks = d.ns;
+  const uint32_t ns_call = d.ns - sl.begin;  // samples of this call
+  uint64_t n_chunks = ns_call;
   if (s->force_chunks > 0) n_chunks = (uint64_t)s->force_chunks;
-  if (n_chunks > d.ns) n_chunks = d.ns;
-  const bool use_scratch = n_chunks > 1;  // else (ns = 1, or option chunks = 1): a slot folds its pixel's samples itself
+  if (n_chunks > ns_call) n_chunks = ns_call;
+  // else (ns = 1, or option chunks = 1): a slot folds its pixel's samples itself -- from +0, dividing at the end; a slice of a
+  // progressive frame takes the chunk mode instead, whose fold kernel continues the running sum and divides only when asked
+  const bool use_scratch = n_chunks > 1 || sl.sliced();
   uint32_t per_pass = d.ns, chunk = d.ns;
   if (use_scratch) {
-    per_pass = samples_per_pass(s, pix_work, d.ns);
-    chunk = (uint32_t)((d.ns + n_chunks - 1) / n_chunks);
-    if (per_pass < d.ns) chunk = 1u;  // several passes: one sample per work item
+    per_pass = samples_per_pass(s, pix_work, ns_call);
+    chunk = (uint32_t)((ns_call + n_chunks - 1) / n_chunks);
+    // several passes: one sample per work item; the same when the slice does not begin on a chunk boundary (the kernel ends a
+    // work item where s % chunk == 0)
+    if (per_pass < ns_call || sl.begin % chunk != 0u) chunk = 1u;
     hipError_t ea = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
     if (ea != hipSuccess) return ea;
   }
   s->cx->last_pix_work = use_scratch && per_pass == d.ns ? (uint32_t)pix_work : 0u;
   uint32_t* queue = (uint32_t*)(s->cx->d_counters + 7);
   // (geometry from the first pass's work: passes are balanced, so every pass of the frame gets the same one)
-  const uint64_t work0 = pix_work * (use_scratch ? (std::min(d.ns, per_pass) + chunk - 1) / chunk : 1u);
+  const uint64_t work0 = pix_work * (use_scratch ? (std::min(ns_call, per_pass) + chunk - 1) / chunk : 1u);
   const PoolGeometry geo = pool_geometry(s, work0, RT_POOL_MAX_THREADS, s->pool_threads, POOL, true);
   const int bt = geo.bt;
   const uint32_t waves = (uint32_t)bt / 64;
@@ -160,7 +167,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   if (e != hipSuccess) return e;
   if (s->wg_per_cu > 0) per_cu = s->wg_per_cu;
   if (per_cu < 1) per_cu = 1;
-  for (uint32_t s0 = 0; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the frame's sample colours
+  for (uint32_t s0 = sl.begin; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the call's sample colours
     DevParams dp = d;
     dp.ns = std::min(d.ns, s0 + per_pass);  // the pass renders samples [s0, dp.ns)
     ChunkMode cm{};
@@ -188,7 +195,9 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (cm.scratch) {
-      hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out, d.ns);
+      // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL)
+      hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
+                         sl.divide ? d.ns : 0u);
       e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
@@ -303,9 +312,10 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipS
 
 // Full-feature scenes, ray-pool kernel (rt_pool_full.h) or, for list worlds without a Bvh, the lock-step kernel
 // (rt_sync_full.h): always one sample per work item + ordered fold, in as many sample passes as the scratch budget asks for.
+// (`sl`: as in launch_pool)
 template <bool COUNT>
 static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
-                                   hipStream_t stream) {
+                                   hipStream_t stream, const SampleSlice& sl) {
   uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
   uint32_t tiles = tiles_x * tiles_y;
   uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
@@ -314,11 +324,12 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   const uint64_t pix_work = ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
   if (pix_work == 0) return hipSuccess;
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
-  const uint32_t per_pass = samples_per_pass(s, pix_work, d.ns);
+  const uint32_t ns_call = d.ns - sl.begin;  // samples of this call
+  const uint32_t per_pass = samples_per_pass(s, pix_work, ns_call);
   const bool tex = (s->features & FEAT_TEXTURE) != 0;
   // ONE 16-wave workgroup per CU shares one LDS copy of the program (128 VGPRs per lane).
   const int bt_max = tex ? RT_FULL_TEX_THREADS : 1024;
-  const PoolGeometry geo = pool_geometry(s, pix_work * std::min(d.ns, per_pass), bt_max, s->full_threads, FPOOL, false);
+  const PoolGeometry geo = pool_geometry(s, pix_work * std::min(ns_call, per_pass), bt_max, s->full_threads, FPOOL, false);
   const int bt = geo.bt;
   const uint32_t waves = (uint32_t)bt / 64;
   hipError_t e = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
@@ -363,7 +374,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   // 469 -> 344 us, 100x100x4 641 -> 485 us, 300x300x10 1.19 -> 0.94 ms, volume_bvh 600x600x50 13.1 -> 11.0 ms, book-2 32x32x8
   // 2.2 -> 1.8 ms; book-2 100x100x10 and larger stay on the pool kernel (2.5 vs 3.0 ms).
   const bool tiny_bvh = s->n_box <= 32u;
-  const bool tiny_frame = pix_work * std::min(d.ns, per_pass) <= (uint64_t)std::max(1, s->num_cus) * 64u;
+  const bool tiny_frame = pix_work * std::min(ns_call, per_pass) <= (uint64_t)std::max(1, s->num_cus) * 64u;
   const bool lock_step = (s->sync_full > 0 || (s->sync_full < 0 && (s->n_box == 0 || tiny_bvh || tiny_frame))) && prog == 1;
   void (*k2)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
   const size_t lds2 = (size_t)window * 32;
@@ -373,7 +384,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
     else k2 = tex ? render_full_sync<1, true, COUNT, false> : render_full_sync<1, false, COUNT, false>;
     // the lock-step kernel keeps ONE path per lane (64 per wave, not the pool kernel's FPOOL): its grid comes from that, and
     // the cap from ITS occupancy -- with the pool kernel's figures a frame of 0.3 .. 0.9 M work items left CUs idle
-    geo2 = pool_geometry(s, pix_work * std::min(d.ns, per_pass), bt_max, s->full_threads, 64u, false);
+    geo2 = pool_geometry(s, pix_work * std::min(ns_call, per_pass), bt_max, s->full_threads, 64u, false);
     if (geo2.bt != bt) geo2 = geo;  // (one block size serves both: the stack and slot buffers below are sized by `waves`)
     e = kernel_setup(s, (const void*)k2, bt, lds2, &per_cu);
     if (e != hipSuccess) return e;
@@ -387,7 +398,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   uint32_t p2_mat = 0, p2_lists = 0;
   // (pool2 = 1: frames of >= 32 M samples -- the pool-2 kernel's slope is 11 % lower, its fixed cost per launch 1.7 ms higher:
   // profiles/r06_experiments/r06c_pool2_tail_probe.txt; pool2 = 2: every frame)
-  const bool p2_size_ok = s->pool2 > 1 || pix_work * (uint64_t)d.ns >= (32ull << 20);
+  const bool p2_size_ok = s->pool2 > 1 || pix_work * (uint64_t)ns_call >= (32ull << 20);
   if (s->pool2 > 0 && p2_size_ok && s->n_prog2 != 0 && !lock_step && !genb) {
     const bool mats3 = s->mat_lds > 0 && pool2_lds_bytes(s->n_prog2, s->n_mat, waves) <= budget;
     lds3 = pool2_lds_bytes(s->n_prog2, mats3 ? s->n_mat : 0u, waves);
@@ -403,7 +414,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
       s->cx->last_kernel = 5;
     }
   }
-  for (uint32_t s0 = 0; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the frame's sample colours
+  for (uint32_t s0 = sl.begin; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the call's sample colours
     DevParams dp = d;
     dp.ns = std::min(d.ns, s0 + per_pass);
     ChunkMode cm{};
@@ -441,16 +452,31 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
                          s->cx->d_counters, s->full_tune, s->cx->d_slots, s->cx->d_stack, window);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out, d.ns);
+    hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
+                       sl.divide ? d.ns : 0u);  // (0 = never divide: RTG_FLAG_PARTIAL)
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
+// The resolve step of a progressive frame (a call with sample_begin = ns and no RTG_FLAG_PARTIAL): divide the running sum of
+// every owned pixel by ns.  Work items as in the pool kernels (work_to_pixel), so it follows the tiles whichever kernel
+// rendered the samples.
+static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t stream) {
+  const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h, tiles = tiles_x * tiles_y;
+  const uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
+  const uint64_t pix_work = ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+  if (pix_work == 0) return hipSuccess;
+  if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(resolve_sum_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, d, make_pixmap(d), (uint32_t)pix_work, d_out);
+  return hipGetLastError();
+}
+
+// `sl` (rtg_api.hip SampleSlice): the samples of a progressive frame this call renders; the default is the whole frame.
 template <bool COUNT>
 static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
-                                hipStream_t stream) {
+                                hipStream_t stream, const SampleSlice& sl = SampleSlice{}) {
   // geometry / texture features pick the kernel; the albedo-range bits only say whether the pool kernels' "accum
   // is +0" argument holds (rt_pool.h PoolField)
   const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
@@ -458,16 +484,29 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
   s->cx->last_kernel = 1;
+  if (sl.begin == d.ns) return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;  // nothing to render
   if (geom != 0 && pool_ok) {
     s->cx->last_kernel = 4;
-    return launch_full_pool<COUNT>(s, cam, d, d_out, stream);
+    return launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl);
   }
   if (geom == 0 && pool_ok) {
     s->cx->last_kernel = 3;
-    return launch_pool<COUNT>(s, cam, d, d_out, stream);
+    return launch_pool<COUNT>(s, cam, d, d_out, stream, sl);
   }
   uint32_t nbx = (d.nx + 15) / 16, nby = (d.ny + 15) / 16;
   dim3 grid(nbx * nby), block(256);
+  if (sl.sliced()) {
+    // a slice of a progressive frame: its own instantiations (FEAT_DEEP graphs on the largest general walk, as the probes)
+    constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+    const uint32_t divide = sl.divide ? 1u : 0u;
+    if (s->features & FEAT_DEEP)
+      hipLaunchKernelGGL((render_slice_kernel<D, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    else if (geom == 0)
+      hipLaunchKernelGGL((render_slice_kernel<0u, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    else
+      hipLaunchKernelGGL((render_slice_kernel<FEAT_ALL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    return hipGetLastError();
+  }
   if (s->features & FEAT_DEEP) {
     // the general walk, sized for what the graph needs (flat_scene.h FEAT_DEEP_FEW_WRAPPERS / FEAT_DEEP_ONE_LEVEL; the probes
     // of rtg_probes.inc keep the largest instantiation: same arithmetic)

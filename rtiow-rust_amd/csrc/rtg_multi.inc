@@ -191,6 +191,17 @@ static uint32_t rank_pix_work(const DevParams& d) {
   return (uint32_t)(((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull);
 }
 
+// RTG_FLAG_RESUME: scene i's full frame starts as the caller's running sums on the pixels it owns and +0 on every other pixel, so
+// that the reduce (x + 0 is exact; a sum starts at +0, so it is never -0) and the packed gather assemble the frame unchanged
+__global__ void keep_owned_kernel(DevParams P, float* __restrict__ fb) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)P.nx * P.ny) return;
+  const uint32_t row = (uint32_t)(i / P.nx), x = (uint32_t)(i - (size_t)row * P.nx);
+  const uint32_t tiles_x = (P.nx + P.tile_w - 1u) / P.tile_w;
+  if (((row / P.tile_h) * tiles_x + x / P.tile_w) % P.nranks == P.rank) return;
+  fb[3 * i] = 0.f, fb[3 * i + 1] = 0.f, fb[3 * i + 2] = 0.f;
+}
+
 __global__ void add_frames_kernel(size_t n, float* __restrict__ dst, const float* __restrict__ src) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = dst[i] + src[i];  // every pixel has ONE non-zero contributor: x + 0 is exact
@@ -220,7 +231,7 @@ static int multi_stats(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
       multi_default_tiles(&p, n_scenes);
       DevParams d;
       (void)check_params(s, camera, &p, &d);
-      total.samples += owned_pixels(d) * d.ns;
+      total.samples += owned_pixels(d) * (d.ns - slice_of(params).begin);
       if (count) {
         unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIP_TRY(hipMemcpy(h, s->cx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
@@ -237,14 +248,17 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
   const size_t n_floats = (size_t)params->nx * params->ny * 3;
   const size_t bytes = n_floats * sizeof(float);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
-  // (1) every scene renders ITS tiles (tile % n_scenes == i) into its own zero-filled full frame, on its own stream
+  const SampleSlice sl = slice_of(params);
+  // (1) every scene renders ITS tiles (tile % n_scenes == i) into its own zero-filled full frame, on its own stream (resuming a
+  // progressive frame: its tiles hold the caller's running sums)
   for (int i = 0; i < n_scenes; i++) {
     rtg_scene* s = scenes[i];
     HIP_TRY(hipSetDevice(s->device));
     if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
     hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, bytes ? bytes : 16);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
-    HIP_TRY(hipMemsetAsync(s->d_frame, 0, bytes, s->own_stream));
+    if (sl.begin != 0u) HIP_TRY(hipMemcpyAsync(s->d_frame, out_rgb, bytes, hipMemcpyHostToDevice, s->own_stream));
+    else HIP_TRY(hipMemsetAsync(s->d_frame, 0, bytes, s->own_stream));
     {
       const int rc_ctx = ctx_acquire(s);
       if (rc_ctx) return rc_ctx;
@@ -255,13 +269,17 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
     DevParams d;
     int rc = check_params(s, camera, &p, &d);
     if (rc) return rc;
+    if (sl.begin != 0u) {
+      hipLaunchKernelGGL(keep_owned_kernel, dim3((uint32_t)(((size_t)d.nx * d.ny + 255) / 256)), dim3(256), 0, s->own_stream, d, s->d_frame);
+      HIP_TRY(hipGetLastError());
+    }
     if (count) {
       HIP_TRY(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), s->own_stream));
       HIP_TRY(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), s->own_stream));
     }
     HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
     const DevCamera cam = to_dev(camera);
-    HIP_TRY(count ? launch_render<true>(s, cam, d, s->d_frame, s->own_stream) : launch_render<false>(s, cam, d, s->d_frame, s->own_stream));
+    HIP_TRY(count ? launch_render<true>(s, cam, d, s->d_frame, s->own_stream, sl) : launch_render<false>(s, cam, d, s->d_frame, s->own_stream, sl));
     HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
     {
       const int rc_ctx = ctx_release(s, s->own_stream);
@@ -385,6 +403,7 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   if (params->struct_size != sizeof(rtg_params)) return fail(RTG_ERR_INVALID, "rtg_params.struct_size mismatch");
   if (params->nranks > 1u) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi shards by itself: params.rank / nranks must be 0 / 0|1");
   if (stats && stats->struct_size != sizeof(rtg_stats)) return fail(RTG_ERR_INVALID, "rtg_stats.struct_size mismatch");
+  if ((params->flags & RTG_FLAG_RESUME) && params->sample_begin > params->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   for (int i = 0; i < n_scenes; i++) {
     if (!scenes[i]) return fail(RTG_ERR_INVALID, "null scene handle");
     // one handle = one frame, one work queue, one stream: the same handle twice would wipe its own tiles

@@ -35,6 +35,7 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
   int rc = check_params(s, camera, params, &d);
   if (rc) return rc;
   if (!xs || !ys || !samples || !out_rgb || !out_info) return fail(RTG_ERR_INVALID, "null argument");
+  if (params->flags & (RTG_FLAG_PARTIAL | RTG_FLAG_RESUME)) return fail(RTG_ERR_INVALID, "rtg_debug_samples renders whole frames: RTG_FLAG_PARTIAL / RTG_FLAG_RESUME are not accepted");
   HIP_TRY(hipSetDevice(s->device));
   if (params->flags & RTG_FLAG_TRACE_KERNEL) {
     // Trace the PRODUCTION kernel: render the whole frame with the instrumented variant of whatever kernel par_cast

@@ -15,6 +15,7 @@
 // par_cast flattens the world, mirroring how a Rust `-sys` binding would add `fn flatten(&self, b)`
 // to `trait Object`.  The reference's panics surface as rtiow::Error.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <memory>
@@ -232,10 +233,10 @@ struct CastOptions {
   const uint8_t *perm_x = nullptr, *perm_y = nullptr, *perm_z = nullptr;
 };
 
-// par_cast, lib.rs:363: `world` is the list world of lib.rs:33; pass {boxed(bvh::from_scene(..))}
-// for the `impl World for Bvh` of lib.rs:51.
-inline Image par_cast(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world,
-                      const CastOptions& opt = CastOptions()) {
+using SceneHandle = std::unique_ptr<rtg_scene, void (*)(rtg_scene*)>;
+
+// flatten `world` once onto opt.device
+inline SceneHandle make_scene(const Scene& world, const CastOptions& opt) {
   rtg_builder* b = nullptr;
   check(rtg_builder_create(&b));
   std::unique_ptr<rtg_builder, void (*)(rtg_builder*)> guard(b, rtg_builder_destroy);
@@ -244,18 +245,58 @@ inline Image par_cast(size_t nx, size_t ny, size_t ns, const Camera& camera, con
   for (const auto& o : world) ids.push_back(o.emit(b));
   rtg_scene* s = nullptr;
   check(rtg_scene_create(b, ids.data(), ids.size(), opt.device, &s));
-  std::unique_ptr<rtg_scene, void (*)(rtg_scene*)> sguard(s, rtg_scene_destroy);
+  return SceneHandle(s, rtg_scene_destroy);
+}
+
+inline rtg_params cast_params(size_t nx, size_t ny, size_t ns, const CastOptions& opt) {
   rtg_params p{};
   p.struct_size = sizeof(p);
   p.nx = (uint32_t)nx, p.ny = (uint32_t)ny, p.ns = (uint32_t)ns;
   p.max_bounces = 50;  // lib.rs:93
   p.t_near = 0.001f;   // lib.rs:35
   p.seed = opt.seed;
+  return p;
+}
+
+// par_cast, lib.rs:363: `world` is the list world of lib.rs:33; pass {boxed(bvh::from_scene(..))}
+// for the `impl World for Bvh` of lib.rs:51.
+inline Image par_cast(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world,
+                      const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  rtg_params p = cast_params(nx, ny, ns, opt);
   Image img;
   img.nx = nx, img.ny = ny;
   img.rgb.assign(nx * ny * 3, 0.f);
-  check(rtg_par_cast(s, &camera.c, &p, img.rgb.data(), nullptr));
+  check(rtg_par_cast(s.get(), &camera.c, &p, img.rgb.data(), nullptr));
   return img;
+}
+
+// Not in the reference: the same frame rendered `step` samples at a time (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
+// RTG_FLAG_RESUME).  After each slice `on_preview(n_done, preview)` receives the frame resolved at n_done samples --
+// bit-identical to par_cast(nx, ny, n_done, ...) -- and returns false to stop early (a time budget, a cancel button).  The
+// last preview, at n_done == ns, is bit-identical to par_cast(nx, ny, ns, ...).  Returns the samples rendered.
+template <typename OnPreview>
+inline size_t par_cast_progressive(size_t nx, size_t ny, size_t ns, size_t step, const Camera& camera, const Scene& world,
+                                   OnPreview&& on_preview, const CastOptions& opt = CastOptions()) {
+  if (step == 0) throw Error(RTG_ERR_INVALID, "par_cast_progressive: step must be > 0");
+  SceneHandle s = make_scene(world, opt);
+  std::vector<float> sum(nx * ny * 3, 0.f);  // the running sum of the samples so far
+  Image preview;
+  preview.nx = nx, preview.ny = ny;
+  size_t done = 0;
+  while (done < ns) {
+    const size_t end = std::min(ns, done + step);
+    rtg_params p = cast_params(nx, ny, end, opt);
+    p.flags = RTG_FLAG_PARTIAL | RTG_FLAG_RESUME, p.sample_begin = (uint32_t)done;
+    check(rtg_par_cast(s.get(), &camera.c, &p, sum.data(), nullptr));
+    done = end;
+    preview.rgb = sum;  // the resolve step divides a copy
+    p = cast_params(nx, ny, done, opt);
+    p.flags = RTG_FLAG_RESUME, p.sample_begin = (uint32_t)done;
+    check(rtg_par_cast(s.get(), &camera.c, &p, preview.rgb.data(), nullptr));
+    if (!on_preview(done, static_cast<const Image&>(preview))) break;
+  }
+  return done;
 }
 
 // print_ppm, lib.rs:344-361 (host post-process)

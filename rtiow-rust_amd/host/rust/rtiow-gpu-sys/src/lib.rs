@@ -20,6 +20,11 @@ pub const RTG_ERR_DEVICE: c_int = -6;
 pub type rtg_id = u32;
 pub const RTG_INVALID_ID: rtg_id = 0xffff_ffff;
 pub const RTG_FLAG_COUNTERS: u32 = 1;
+pub const RTG_FLAG_TRACE_KERNEL: u32 = 2;
+/// Leave the unnormalised running sum of the samples in the framebuffer (progressive rendering, see the header).
+pub const RTG_FLAG_PARTIAL: u32 = 4;
+/// The framebuffer holds the running sum of samples `[0, sample_begin)`: render `[sample_begin, ns)` only.
+pub const RTG_FLAG_RESUME: u32 = 8;
 
 #[repr(C)]
 pub struct rtg_builder {
@@ -61,7 +66,7 @@ pub struct rtg_params {
     pub rank: u32,
     pub nranks: u32,
     pub flags: u32,
-    pub reserved: u32,
+    pub sample_begin: u32, // read under RTG_FLAG_RESUME only
 }
 
 /// 56 bytes.

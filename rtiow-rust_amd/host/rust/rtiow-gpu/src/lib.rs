@@ -247,6 +247,36 @@ impl GpuScene {
         check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, rgb.as_mut_ptr(), ptr::null_mut()) })?;
         Ok(Image { nx, ny, rgb })
     }
+
+    /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).
+    /// After each slice `on_preview(n_done, &preview)` gets the frame resolved at `n_done` samples -- bit-identical to
+    /// `par_cast(nx, ny, n_done, ..)` -- and returns `false` to stop early (time budget, cancel).  The preview at
+    /// `n_done == ns` is bit-identical to `par_cast(nx, ny, ns, ..)`.  Returns the samples rendered.
+    pub fn progressive<F: FnMut(usize, &Image) -> bool>(&mut self, nx: usize, ny: usize, ns: usize, step: usize, camera: &Camera,
+                                                         options: &CastOptions, mut on_preview: F) -> Result<usize> {
+        if step == 0 {
+            return Err(Error { code: sys::RTG_ERR_INVALID, message: "progressive: step must be > 0".into() });
+        }
+        let mut sum = vec![0f32; nx * ny * 3]; // the running sum of the samples so far
+        let mut done = 0;
+        while done < ns {
+            let end = ns.min(done + step);
+            let mut p = params(nx, ny, end, options);
+            p.flags = sys::RTG_FLAG_PARTIAL | sys::RTG_FLAG_RESUME;
+            p.sample_begin = done as u32;
+            check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, sum.as_mut_ptr(), ptr::null_mut()) })?;
+            done = end;
+            let mut preview = Image { nx, ny, rgb: sum.clone() }; // the resolve step divides a copy
+            let mut p = params(nx, ny, done, options);
+            p.flags = sys::RTG_FLAG_RESUME;
+            p.sample_begin = done as u32;
+            check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, preview.rgb.as_mut_ptr(), ptr::null_mut()) })?;
+            if !on_preview(done, &preview) {
+                break;
+            }
+        }
+        Ok(done)
+    }
 }
 
 /// Implemented by the reference's `World` types (lib.rs:23-55): `[Box<dyn Object>]` flattens each object in order,
