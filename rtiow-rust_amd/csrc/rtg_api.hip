@@ -59,6 +59,8 @@ struct rtg_builder {
 // the next one and first waits for the frame that used it last (`done`), so asynchronous calls on one handle are always safe
 // and, with more than one context, overlap.
 constexpr int RTG_MAX_FRAMES = 4;
+// The kernel that rendered a frame (rtg_launch.inc launch_render)
+enum class KernelKind { baseline, lean_pool, full_pool, lock_step, pool2 };
 struct LaunchCtx {
   unsigned long long* d_counters = nullptr;  // [0..4] N/P/H/rays/draws, [7] = work-queue head (persistent kernel), [8..] schedule statistics
   hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
@@ -73,7 +75,7 @@ struct LaunchCtx {
   uint32_t* d_lpt = nullptr;    // cost-ordered work queue (rt_pool.h LptQueue)
   size_t lpt_bytes = 0;
   LptQueue lpt_desc{};          // descriptor of the last launch (RTG_VERBOSE histogram)
-  int last_kernel = 0;          // what launch_render chose last: 1 = baseline, 3 = lean ray pools, 4 = full-feature ray pools
+  KernelKind last_kernel = KernelKind::baseline;  // what launch_render chose last
   uint32_t last_pix_work = 0;   // pixel work items of that launch (tiles x tile area), 0 when it kept no per-sample scratch
 };
 
@@ -674,16 +676,53 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   return RTG_OK;
 }
 
-static uint64_t owned_pixels(const DevParams& d) {
-  uint64_t px = 0;
-  uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
-  for (uint32_t ty = 0; ty < tiles_y; ty++)
-    for (uint32_t tx = 0; tx < tiles_x; tx++) {
-      if ((ty * tiles_x + tx) % d.nranks != d.rank) continue;
-      uint32_t w = std::min(d.tile_w, d.nx - tx * d.tile_w), h = std::min(d.tile_h, d.ny - ty * d.tile_h);
-      px += (uint64_t)w * h;
+// Option verbose, counting builds: the schedule statistics of the frame just rendered (`ms`: its kernel time)
+static int print_schedule_stats(rtg_scene* s, float ms) {
+  if (s->cx->lpt_desc.n_blocks && s->cx->d_lpt) {  // cost classes of the last frame (class 0 = deepest)
+    std::vector<uint32_t> ctl(LPT_CTL);
+    HIP_TRY(hipMemcpy(ctl.data(), s->cx->lpt_desc.ctl, LPT_CTL * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::string line;
+    for (uint32_t c = 0; c < LPT_CLASSES; c++)
+      if (ctl[c]) line += " " + std::to_string(c) + ":" + std::to_string(ctl[c]);
+    fprintf(stderr, "[rtg] cost-ordered queue: %u of %u blocks filed, class:blocks%s\n", ctl[LPT_CLASSES], s->cx->lpt_desc.n_blocks, line.c_str());
+  }
+  unsigned long long q[24];
+  HIP_TRY(hipMemcpy(q, s->cx->d_counters + 8, sizeof(q), hipMemcpyDeviceToHost));
+  if (q[18]) {  // lean pool kernel: per-wave timeline, scaled so that the longest wave = the measured kernel time
+    const double us = (double)ms * 1000. / (double)q[16], n = (double)q[18];
+    fprintf(stderr, "[rtg] wave timeline (us from its start): sees the work queue empty at min %.0f / mean %.0f / max %.0f; done at mean %.0f / max %.0f\n",
+            (double)((1ull << 62) - q[19]) * us, (double)q[20] / n * us, (double)q[21] * us, (double)q[17] / n * us, (double)q[16] * us);
+  }
+  double tt = (double)(q[8] + q[9] + q[10] + q[11]);  // (q[9] = service minus shade)
+  fprintf(stderr, "[rtg] wave-time shares (s_memtime, instrumented variant): shade %.1f%% gen+pull|service %.1f%% box %.1f%% sphere %.1f%%; "
+          "per pass: shade %.0f, gen|service %.0f, box %.0f, sphere %.0f ticks\n", 100 * q[8] / tt, 100 * q[9] / tt, 100 * q[10] / tt,
+          100 * q[11] / tt, q[4] ? (double)q[8] / q[4] : 0., q[4] ? (double)q[9] / q[4] : 0., q[0] ? (double)q[10] / q[0] : 0.,
+          q[2] ? (double)q[11] / q[2] : 0.);
+  if (q[15]) {  // full-feature pool kernel: the steps of a service
+    unsigned long long f[2];
+    HIP_TRY(hipMemcpy(f, s->cx->d_counters + 5, sizeof(f), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[rtg] services %llu: finish step %.1f%% of wave time (%.0f ticks each), refill step %.1f%% (%.0f ticks per refill)\n", f[0],
+            100 * f[1] / tt, f[0] ? (double)f[1] / f[0] : 0., 100 * q[15] / tt, q[6] ? (double)q[15] / q[6] : 0.);
+  }
+#ifdef RT_CENSUS
+  {
+    unsigned long long c[32];
+    HIP_TRY(hipMemcpy(c, s->cx->d_counters + 32, sizeof(c), hipMemcpyDeviceToHost));
+    static const char* nm[13] = {"BOX", "END", "no-ray", "held", "?", "?", "SPHERE", "RECT", "PUSH", "POP", "MEDIUM", "PRISM", "BEND"};
+    for (int k = 0; k < 2; k++) {
+      std::string line;
+      char buf[64];
+      for (int j = 0; j < 13; j++)
+        if (c[16 * k + j]) snprintf(buf, sizeof buf, " %s %.1f", nm[j], (double)c[16 * k + j] / (double)c[16 * k + 15]), line += buf;
+      fprintf(stderr, "[rtg] lane census at %s (%llu):%s\n", k ? "slow-pass iterations" : "box steps", c[16 * k + 15], line.c_str());
     }
-  return px;
+  }
+#endif
+  fprintf(stderr, "[rtg] pool schedule: box steps %llu (avg %.1f lanes), sphere passes %llu (avg %.1f lanes), shade passes %llu "
+            "(avg %.1f lanes), end / camera-ray passes %llu (avg %.1f lanes), refills %llu (avg %.1f lanes)\n", q[0], q[0] ? (double)q[1] / q[0] : 0.0, q[2],
+            q[2] ? (double)q[3] / q[2] : 0.0, q[4], q[4] ? (double)q[5] / q[4] : 0.0, q[12], q[12] ? (double)q[13] / q[12] : 0.0, q[6],
+            q[6] && q[7] ? (double)q[7] / q[6] : 0.0);
+  return RTG_OK;
 }
 
 int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params* params, float* d_out,
@@ -753,52 +792,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
     unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (count) HIP_TRY(hipMemcpy(h, s->cx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
     stats->aabb_tests = h[0], stats->prim_tests = h[1], stats->shaded_hits = h[2], stats->rays = h[3], stats->draws = h[4];
-    if (count && s->verbose && s->cx->lpt_desc.n_blocks && s->cx->d_lpt) {  // cost classes of the last frame (class 0 = deepest)
-      std::vector<uint32_t> ctl(LPT_CTL);
-      HIP_TRY(hipMemcpy(ctl.data(), s->cx->lpt_desc.ctl, LPT_CTL * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      std::string line;
-      for (uint32_t c = 0; c < LPT_CLASSES; c++)
-        if (ctl[c]) line += " " + std::to_string(c) + ":" + std::to_string(ctl[c]);
-      fprintf(stderr, "[rtg] cost-ordered queue: %u of %u blocks filed, class:blocks%s\n", ctl[LPT_CLASSES], s->cx->lpt_desc.n_blocks, line.c_str());
-    }
-    if (count && s->verbose) {
-      unsigned long long q[24];
-      HIP_TRY(hipMemcpy(q, s->cx->d_counters + 8, sizeof(q), hipMemcpyDeviceToHost));
-      if (q[18]) {  // lean pool kernel: per-wave timeline, scaled so that the longest wave = the measured kernel time
-        const double us = (double)ms * 1000. / (double)q[16], n = (double)q[18];
-        fprintf(stderr, "[rtg] wave timeline (us from its start): sees the work queue empty at min %.0f / mean %.0f / max %.0f; done at mean %.0f / max %.0f\n",
-                (double)((1ull << 62) - q[19]) * us, (double)q[20] / n * us, (double)q[21] * us, (double)q[17] / n * us, (double)q[16] * us);
-      }
-      double tt = (double)(q[8] + q[9] + q[10] + q[11]);  // (q[9] = service minus shade)
-      fprintf(stderr, "[rtg] wave-time shares (s_memtime, instrumented variant): shade %.1f%% gen+pull|service %.1f%% box %.1f%% sphere %.1f%%; "
-              "per pass: shade %.0f, gen|service %.0f, box %.0f, sphere %.0f ticks\n", 100 * q[8] / tt, 100 * q[9] / tt, 100 * q[10] / tt,
-              100 * q[11] / tt, q[4] ? (double)q[8] / q[4] : 0., q[4] ? (double)q[9] / q[4] : 0., q[0] ? (double)q[10] / q[0] : 0.,
-              q[2] ? (double)q[11] / q[2] : 0.);
-      if (q[15]) {  // full-feature pool kernel: the steps of a service
-        unsigned long long f[2];
-        HIP_TRY(hipMemcpy(f, s->cx->d_counters + 5, sizeof(f), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[rtg] services %llu: finish step %.1f%% of wave time (%.0f ticks each), refill step %.1f%% (%.0f ticks per refill)\n", f[0],
-                100 * f[1] / tt, f[0] ? (double)f[1] / f[0] : 0., 100 * q[15] / tt, q[6] ? (double)q[15] / q[6] : 0.);
-      }
-#ifdef RT_CENSUS
-      {
-        unsigned long long c[32];
-        HIP_TRY(hipMemcpy(c, s->cx->d_counters + 32, sizeof(c), hipMemcpyDeviceToHost));
-        static const char* nm[13] = {"BOX", "END", "no-ray", "held", "?", "?", "SPHERE", "RECT", "PUSH", "POP", "MEDIUM", "PRISM", "BEND"};
-        for (int k = 0; k < 2; k++) {
-          std::string line;
-          char buf[64];
-          for (int j = 0; j < 13; j++)
-            if (c[16 * k + j]) snprintf(buf, sizeof buf, " %s %.1f", nm[j], (double)c[16 * k + j] / (double)c[16 * k + 15]), line += buf;
-          fprintf(stderr, "[rtg] lane census at %s (%llu):%s\n", k ? "slow-pass iterations" : "box steps", c[16 * k + 15], line.c_str());
-        }
-      }
-#endif
-      fprintf(stderr, "[rtg] pool schedule: box steps %llu (avg %.1f lanes), sphere passes %llu (avg %.1f lanes), shade passes %llu "
-                "(avg %.1f lanes), end / camera-ray passes %llu (avg %.1f lanes), refills %llu (avg %.1f lanes)\n", q[0], q[0] ? (double)q[1] / q[0] : 0.0, q[2],
-                q[2] ? (double)q[3] / q[2] : 0.0, q[4], q[4] ? (double)q[5] / q[4] : 0.0, q[12], q[12] ? (double)q[13] / q[12] : 0.0, q[6],
-                q[6] && q[7] ? (double)q[7] / q[6] : 0.0);
-    }
+    if (count && s->verbose && (rc = print_schedule_stats(s, ms))) return rc;
   }
   return RTG_OK;
 }

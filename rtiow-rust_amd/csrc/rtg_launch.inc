@@ -24,7 +24,28 @@ static uint32_t samples_per_pass(const rtg_scene* s, uint64_t pix_work, uint32_t
   return (uint32_t)((ns + n_pass - 1) / n_pass);  // balanced passes
 }
 
-static uint64_t owned_pixels(const DevParams& d);
+// Tile ownership (part of the ABI; rt_pool.h work_to_pixel is its device side): the tiles are numbered row-major and tile t
+// belongs to rank t % nranks.  A rank's work items are its tiles x the tile area, rounded up to whole 256-item reservations
+// (tiles smaller than 16 x 16 need not add up to one; the padding items lie beyond the rank's last tile, i.e. outside the
+// image, and are skipped like the padding of ragged image sizes).
+static uint64_t rank_pix_work(const DevParams& d) {
+  const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h, tiles = tiles_x * tiles_y;
+  const uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
+  return ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+}
+// ... and the pixels of those tiles that lie inside the image, exactly (rtg_stats.samples)
+static uint64_t owned_pixels(const DevParams& d) {
+  uint64_t px = 0;
+  uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
+  for (uint32_t ty = 0; ty < tiles_y; ty++)
+    for (uint32_t tx = 0; tx < tiles_x; tx++) {
+      if ((ty * tiles_x + tx) % d.nranks != d.rank) continue;
+      uint32_t w = std::min(d.tile_w, d.nx - tx * d.tile_w), h = std::min(d.tile_h, d.ny - ty * d.tile_h);
+      px += (uint64_t)w * h;
+    }
+  return px;
+}
+
 static hipError_t grow(void** buf, size_t* have, size_t need) {
   if (need <= *have) return hipSuccess;
   if (*buf) (void)hipFree(*buf);
@@ -40,6 +61,7 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipS
 // small frame more than its kernels (tools/latency_probe.py), so they are made once per process.  The attribute belongs to
 // the FUNCTION (per device), not to a scene handle, and the last call wins: it is raised once to all of a CU's LDS, so that
 // handles (or frame sizes of one handle) that ask the same kernel for different amounts never lower it under each other.
+// `per_cu`: the workgroups per CU a launch counts on -- option wg_per_cu when set, else the occupancy figure, at least one.
 static hipError_t kernel_setup(rtg_scene* s, const void* kernel, int bt, size_t lds, int* per_cu) {
   static std::mutex mu;
   static std::map<std::pair<int, const void*>, size_t> raised;                                // (device, kernel) -> the dynamic-LDS limit the function has now
@@ -72,7 +94,7 @@ static hipError_t kernel_setup(rtg_scene* s, const void* kernel, int bt, size_t 
     if (e != hipSuccess) return e;
     it = occupancy.emplace(key, n).first;
   }
-  *per_cu = it->second;
+  *per_cu = s->wg_per_cu > 0 ? s->wg_per_cu : std::max(1, it->second);
   return hipSuccess;
 }
 
@@ -105,18 +127,53 @@ static PoolGeometry pool_geometry(const rtg_scene* s, uint64_t total_work, int b
   return g;
 }
 
+// A pool-kernel launch, decided before its first sample pass: the kernel, its block, dynamic LDS, geometry and workgroups per
+// CU (kernel_setup), and the paths a wave keeps in flight as the cost-ordered queue counts them.
+struct PoolLaunch {
+  KernelKind kind;
+  int bt, per_cu;
+  size_t lds;
+  PoolGeometry geo;
+  uint32_t pool;
+};
+
+// The sample passes of a pool-kernel frame, ONE unless the scratch budget is smaller than the call's sample colours.
+// `chunks(s0, end)`: the work items of the pass over samples [s0, end) (rt_pool.h ChunkMode, without the reservations and the
+// cost-ordered queue); `issue(s0, dp, cm, grid, total_work)`: make room for the launch, write its constants, launch the kernel.
+template <typename Chunks, typename Issue>
+static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl,
+                                const PoolLaunch& L, uint32_t per_pass, Chunks chunks, Issue issue) {
+  for (uint32_t s0 = sl.begin; s0 < d.ns; s0 += per_pass) {
+    DevParams dp = d;
+    dp.ns = std::min(d.ns, s0 + per_pass);  // the pass renders samples [s0, dp.ns)
+    ChunkMode cm = chunks(s0, dp.ns);
+    cm.work_block = L.geo.work_block;
+    const uint64_t total_work = (uint64_t)cm.pix_work * cm.n_chunks;
+    if (total_work > 0xfffffffeull) return hipErrorInvalidValue;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(L.geo.grid, (uint64_t)s->num_cus * L.per_cu);
+    hipError_t e = setup_lpt(s, cm, (uint64_t)grid * (uint32_t)(L.bt / 64) * L.pool, stream);
+    if (e != hipSuccess) return e;
+    if (cm.lpt) cm.work_block = WORK_BLOCK;  // (its blocks are the reservations)
+    e = issue(s0, dp, cm, grid, (uint32_t)total_work);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (cm.scratch) {  // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL)
+      hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)(((uint64_t)cm.pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
+                         sl.divide ? d.ns : 0u);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  }
+  return hipSuccess;
+}
+
 // Lean scenes, ray-pool kernel (rt_pool.h): one persistent 1024-thread workgroup per CU.
 // `sl`: the samples [sl.begin, d.ns) of a progressive frame's slice -- pass sizing, chunking and launch geometry follow this
 // call's samples, not the frame's.
 template <bool COUNT>
 static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
                               hipStream_t stream, const SampleSlice& sl) {
-  uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
-  uint32_t tiles = tiles_x * tiles_y;
-  uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
-  // (rounded up to whole 256-item reservations: tiles smaller than 16 x 16 need not add up to one; the padding items lie beyond
-  // the rank's last tile, i.e. outside the image, and are skipped like the padding of ragged image sizes)
-  const uint64_t pix_work = ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+  const uint64_t pix_work = rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   // Sample-chunk mode (see rt_pool.h).  Default: one sample per work item.  Work items are then ~100x more numerous than
@@ -162,47 +219,31 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   if (wide) kernel = ray_lds ? render_lean_pool<true, COUNT, true, true> : render_lean_pool<true, COUNT, false, true>;
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
-  int per_cu = 0;
-  hipError_t e = kernel_setup(s, (const void*)kernel, bt, lds, &per_cu);
+  PoolLaunch L{KernelKind::lean_pool, bt, 0, lds, geo, POOL};
+  hipError_t e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
   if (e != hipSuccess) return e;
-  if (s->wg_per_cu > 0) per_cu = s->wg_per_cu;
-  if (per_cu < 1) per_cu = 1;
-  for (uint32_t s0 = sl.begin; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the call's sample colours
-    DevParams dp = d;
-    dp.ns = std::min(d.ns, s0 + per_pass);  // the pass renders samples [s0, dp.ns)
+  auto chunks = [&](uint32_t s0, uint32_t end) {
     ChunkMode cm{};
     cm.scratch = nullptr, cm.chunk = d.ns, cm.n_chunks = 1, cm.pix_work = (uint32_t)pix_work, cm.s_begin = s0;
-    cm.work_block = geo.work_block;
     if (use_scratch) {
       cm.chunk = chunk;
-      cm.n_chunks = (dp.ns - s0 + chunk - 1) / chunk;
+      cm.n_chunks = (end - s0 + chunk - 1) / chunk;
       cm.scratch = s->cx->d_scratch - 3ull * s0 * pix_work;  // biased: sample s of work index w at scratch[3 * (s * pix_work + w)]
     }
-    const uint64_t total_work = pix_work * cm.n_chunks;
-    if (total_work > 0xfffffffeull) return hipErrorInvalidValue;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(geo.grid, (uint64_t)s->num_cus * per_cu);
-    e = setup_lpt(s, cm, (uint64_t)grid * waves * POOL, stream);
-    if (e != hipSuccess) return e;
-    if (cm.lpt) cm.work_block = WORK_BLOCK;  // (its blocks are the reservations)
+    return cm;
+  };
+  auto issue = [&](uint32_t s0, const DevParams& dp, const ChunkMode& cm, uint32_t grid, uint32_t total_work) {
     if (s->verbose)
       fprintf(stderr, "[rtg] pool: samples [%u, %u) of %u: grid %u x %d threads, %d WG/CU, lds %zu B (program staged: %d, hot slot fields in LDS: %d), %u chunk(s) of %u samples, cost-ordered queue after %u chunk(s)\n",
-              s0, dp.ns, d.ns, grid, bt, per_cu, lds, (int)use_lds, (int)ray_lds, cm.n_chunks, cm.chunk, (cm.lpt_samples - (cm.lpt_samples ? s0 : 0u)) / (cm.chunk ? cm.chunk : 1u));
-    e = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
-    if (e != hipSuccess) return e;
+              s0, dp.ns, d.ns, grid, bt, L.per_cu, lds, (int)use_lds, (int)ray_lds, cm.n_chunks, cm.chunk, (cm.lpt_samples - (cm.lpt_samples ? s0 : 0u)) / (cm.chunk ? cm.chunk : 1u));
+    hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
+    if (eg != hipSuccess) return eg;
     hipLaunchKernelGGL(write_launch_consts, dim3(1), dim3(1), 0, stream, s->cx->d_consts, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, (unsigned long long*)queue);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, (uint32_t)total_work, queue,
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                        s->cx->d_counters, s->pool_tune, s->cx->d_slots);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (cm.scratch) {
-      // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL)
-      hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
-                         sl.divide ? d.ns : 0u);
-      e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-  }
-  return hipSuccess;
+    return hipSuccess;
+  };
+  return sample_passes(s, d, d_out, stream, sl, L, per_pass, chunks, issue);
 }
 
 // The 4-wide image of a lean program that is ONE Bvh over spheres (rt_pool.h WIDE; option `bvh4`): every node record holds
@@ -316,12 +357,7 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipS
 template <bool COUNT>
 static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
                                    hipStream_t stream, const SampleSlice& sl) {
-  uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
-  uint32_t tiles = tiles_x * tiles_y;
-  uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
-  // (rounded up to whole 256-item reservations: tiles smaller than 16 x 16 need not add up to one; the padding items lie beyond
-  // the rank's last tile, i.e. outside the image, and are skipped like the padding of ragged image sizes)
-  const uint64_t pix_work = ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+  const uint64_t pix_work = rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   const uint32_t ns_call = d.ns - sl.begin;  // samples of this call
@@ -361,11 +397,6 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   } else if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT> : render_full_pool<0, false, COUNT>;
   else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT> : render_full_pool<1, false, COUNT>;
   else kernel = tex ? render_full_pool<2, true, COUNT> : render_full_pool<2, false, COUNT>;
-  int per_cu = 0;
-  e = kernel_setup(s, (const void*)kernel, bt, lds, &per_cu);
-  if (e != hipSuccess) return e;
-  if (s->wg_per_cu > 0) per_cu = s->wg_per_cu;
-  if (per_cu < 1) per_cu = 1;
   // The lock-step kernel (rt_sync_full.h: one path per lane, no stacks, no pools) renders list worlds without a Bvh -- and, by
   // default (option sync = -1), programs whose Bvhs are tiny (<= 32 BOX records: the Criterion scene of benches/scene.rs has 15,
   // volume_test under bvh::from_scene 5; a box loop has nothing to batch there) and frames with fewer work items than the chip has
@@ -376,97 +407,87 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   const bool tiny_bvh = s->n_box <= 32u;
   const bool tiny_frame = pix_work * std::min(ns_call, per_pass) <= (uint64_t)std::max(1, s->num_cus) * 64u;
   const bool lock_step = (s->sync_full > 0 || (s->sync_full < 0 && (s->n_box == 0 || tiny_bvh || tiny_frame))) && prog == 1;
-  void (*k2)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
-  const size_t lds2 = (size_t)window * 32;
-  PoolGeometry geo2 = geo;
-  if (lock_step) {
-    if (genb) k2 = tex ? render_full_sync<1, true, COUNT, true> : render_full_sync<1, false, COUNT, true>;
-    else k2 = tex ? render_full_sync<1, true, COUNT, false> : render_full_sync<1, false, COUNT, false>;
-    // the lock-step kernel keeps ONE path per lane (64 per wave, not the pool kernel's FPOOL): its grid comes from that, and
-    // the cap from ITS occupancy -- with the pool kernel's figures a frame of 0.3 .. 0.9 M work items left CUs idle
-    geo2 = pool_geometry(s, pix_work * std::min(ns_call, per_pass), bt_max, s->full_threads, 64u, false);
-    if (geo2.bt != bt) geo2 = geo;  // (one block size serves both: the stack and slot buffers below are sized by `waves`)
-    e = kernel_setup(s, (const void*)k2, bt, lds2, &per_cu);
-    if (e != hipSuccess) return e;
-    if (s->wg_per_cu > 0) per_cu = s->wg_per_cu;
-    if (per_cu < 1) per_cu = 1;
-  }
   // The pool-2 kernel (rt_pool2.h) for programs that have a second program (flat_scene.h "the list level, hoisted"), when that
   // program and the waves' lists fit LDS whole; option pool2 = 0 keeps the first kernel (A/B).
-  void (*k3)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
-  size_t lds3 = 0;
-  uint32_t p2_mat = 0, p2_lists = 0;
   // (pool2 = 1: frames of >= 32 M samples -- the pool-2 kernel's slope is 11 % lower, its fixed cost per launch 1.7 ms higher:
   // profiles/r06_experiments/r06c_pool2_tail_probe.txt; pool2 = 2: every frame)
   const bool p2_size_ok = s->pool2 > 1 || pix_work * (uint64_t)ns_call >= (32ull << 20);
-  if (s->pool2 > 0 && p2_size_ok && s->n_prog2 != 0 && !lock_step && !genb) {
-    const bool mats3 = s->mat_lds > 0 && pool2_lds_bytes(s->n_prog2, s->n_mat, waves) <= budget;
-    lds3 = pool2_lds_bytes(s->n_prog2, mats3 ? s->n_mat : 0u, waves);
-    if (lds3 <= budget) {
-      k3 = tex ? render_full_pool2<true, COUNT> : render_full_pool2<false, COUNT>;
-      const uint32_t tab = s->n_prog2 * 32u + DC_WORDS * 4u;
-      p2_mat = mats3 ? tab + P2_TABLE_BYTES : 0u;
-      p2_lists = tab + P2_TABLE_BYTES + (mats3 ? s->n_mat * 32u : 0u);
-      e = kernel_setup(s, (const void*)k3, bt, lds3, &per_cu);
-      if (e != hipSuccess) return e;
-      if (s->wg_per_cu > 0) per_cu = s->wg_per_cu;
-      if (per_cu < 1) per_cu = 1;
-      s->cx->last_kernel = 5;
-    }
+  const bool mats3 = s->mat_lds > 0 && pool2_lds_bytes(s->n_prog2, s->n_mat, waves) <= budget;
+  const size_t lds3 = pool2_lds_bytes(s->n_prog2, mats3 ? s->n_mat : 0u, waves);
+  const bool pool2 = s->pool2 > 0 && p2_size_ok && s->n_prog2 != 0 && !lock_step && !genb && lds3 <= budget;
+  // The launch of the kernel that takes the frame.  The first kernel is set up whichever wins, and before the winner: the LDS
+  // raise and the occupancy query are cached per function.
+  PoolLaunch L{KernelKind::full_pool, bt, 0, lds, geo, FPOOL};  // (FPOOL for all three: the queue's phase 1 as the first kernel sizes it)
+  LaunchConsts consts{};  // the launch constants particular to the kernel (parent, mat_lds, seg_first / seg_end, p2_lists)
+  consts.parent = s->d_parent;
+  e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
+  if (e != hipSuccess) return e;
+  void (*sync_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
+  void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
+  if (lock_step) {
+    L.kind = KernelKind::lock_step;
+    if (genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true> : render_full_sync<1, false, COUNT, true>;
+    else sync_kernel = tex ? render_full_sync<1, true, COUNT, false> : render_full_sync<1, false, COUNT, false>;
+    L.lds = (size_t)window * 32;
+    // the lock-step kernel keeps ONE path per lane (64 per wave, not the pool kernel's FPOOL): its grid comes from that, and
+    // the cap from ITS occupancy -- with the pool kernel's figures a frame of 0.3 .. 0.9 M work items left CUs idle
+    L.geo = pool_geometry(s, pix_work * std::min(ns_call, per_pass), bt_max, s->full_threads, 64u, false);
+    if (L.geo.bt != bt) L.geo = geo;  // (one block size serves both: the stack and slot buffers below are sized by `waves`)
+    e = kernel_setup(s, (const void*)sync_kernel, bt, L.lds, &L.per_cu);
+  } else if (pool2) {
+    L.kind = KernelKind::pool2;
+    pool2_kernel = tex ? render_full_pool2<true, COUNT> : render_full_pool2<false, COUNT>;
+    L.lds = lds3;
+    const uint32_t tab = s->n_prog2 * 32u + DC_WORDS * 4u;
+    consts.mat_lds = mats3 ? tab + P2_TABLE_BYTES : 0u;
+    consts.p2_lists = tab + P2_TABLE_BYTES + (mats3 ? s->n_mat * 32u : 0u);
+    e = kernel_setup(s, (const void*)pool2_kernel, bt, L.lds, &L.per_cu);
+  } else {
+    // (pool kernel only: book-2 -1 %, book2_bvh -0.7 %; the lock-step kernel measured 2 % slower on Cornell with its materials in LDS)
+    if (mats_in_lds) consts.mat_lds = (uint32_t)full_pool_lds_bytes(window, waves);
+    if (s->hoist > 0 && s->seg_end > s->seg_first) consts.seg_first = s->seg_first * RSZ, consts.seg_end = s->seg_end * RSZ;
   }
-  for (uint32_t s0 = sl.begin; s0 < d.ns; s0 += per_pass) {  // ONE pass unless the scratch budget is smaller than the call's sample colours
-    DevParams dp = d;
-    dp.ns = std::min(d.ns, s0 + per_pass);
+  if (e != hipSuccess) return e;
+  s->cx->last_kernel = L.kind;
+  auto chunks = [&](uint32_t s0, uint32_t end) {
     ChunkMode cm{};
-    cm.scratch = s->cx->d_scratch - 3ull * s0 * pix_work, cm.chunk = 1u, cm.n_chunks = dp.ns - s0, cm.pix_work = (uint32_t)pix_work, cm.s_begin = s0;
-    cm.work_block = lock_step ? geo2.work_block : geo.work_block;
-    const uint64_t total_work = pix_work * cm.n_chunks;
-    if (total_work > 0xfffffffeull) return hipErrorInvalidValue;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(lock_step ? geo2.grid : geo.grid, (uint64_t)s->num_cus * per_cu);
-    e = setup_lpt(s, cm, (uint64_t)grid * waves * FPOOL, stream);
-    if (e != hipSuccess) return e;
-    if (cm.lpt) cm.work_block = WORK_BLOCK;
+    cm.scratch = s->cx->d_scratch - 3ull * s0 * pix_work, cm.chunk = 1u, cm.n_chunks = end - s0, cm.pix_work = (uint32_t)pix_work, cm.s_begin = s0;
     cm.drain_share = (uint32_t)std::max(0, s->drain_share);
-    e = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * std::max(full_pool_wg_words(waves), pool2_slot_words(waves)) * sizeof(uint32_t));
-    if (e != hipSuccess) return e;
-    e = grow((void**)&s->cx->d_stack, &s->cx->stack_bytes, (size_t)grid * waves * (genb ? 2 : 1) * MAX_XFORM_DEPTH * 6 * 64 * sizeof(float));
-    if (e != hipSuccess) return e;
+    return cm;
+  };
+  auto issue = [&](uint32_t s0, const DevParams& dp, const ChunkMode& cm, uint32_t grid, uint32_t total_work) {
+    hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * std::max(full_pool_wg_words(waves), pool2_slot_words(waves)) * sizeof(uint32_t));
+    if (eg != hipSuccess) return eg;
+    eg = grow((void**)&s->cx->d_stack, &s->cx->stack_bytes, (size_t)grid * waves * (genb ? 2 : 1) * MAX_XFORM_DEPTH * 6 * 64 * sizeof(float));
+    if (eg != hipSuccess) return eg;
+    // (the lock-step kernel reports as the first kernel, with that kernel's LDS figure)
+    const bool p2 = L.kind == KernelKind::pool2;
     if (s->verbose)
       fprintf(stderr, "[rtg] full pool%s: samples [%u, %u) of %u: grid %u x %d threads, %d WG/CU, lds %zu B (program window: %u of %u records), cost-ordered queue after %u chunk(s)\n",
-              k3 ? " 2 (second program)" : "", s0, dp.ns, d.ns, grid, bt, per_cu, k3 ? lds3 : lds, k3 ? s->n_prog2 : window, k3 ? s->n_prog2 : s->n_prog,
+              p2 ? " 2 (second program)" : "", s0, dp.ns, d.ns, grid, bt, L.per_cu, p2 ? lds3 : lds, p2 ? s->n_prog2 : window, p2 ? s->n_prog2 : s->n_prog,
               cm.lpt_samples - (cm.lpt_samples ? s0 : 0u));
-    LaunchConsts consts{cam, dp, cm, make_pixmap(dp), s->d_parent, 0u, 0u, 0u, 0u};
-    if (k3) consts.mat_lds = p2_mat, consts.p2_lists = p2_lists;
-    // (pool kernel only: book-2 -1 %, book2_bvh -0.7 %; the lock-step kernel measured 2 % slower on Cornell with its materials in LDS)
-    if (mats_in_lds && !lock_step && !k3) consts.mat_lds = (uint32_t)full_pool_lds_bytes(window, waves);
-    if (!lock_step && !k3 && s->hoist > 0 && s->seg_end > s->seg_first) consts.seg_first = s->seg_first * RSZ, consts.seg_end = s->seg_end * RSZ;
-    hipLaunchKernelGGL(write_launch_consts, dim3(1), dim3(1), 0, stream, s->cx->d_consts, consts, (unsigned long long*)queue);
-    if (lock_step)
-      hipLaunchKernelGGL(k2, dim3(grid), dim3(bt), lds2, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, (uint32_t)total_work, queue,
+    LaunchConsts c = consts;
+    c.cam = cam, c.P = dp, c.cm = cm, c.pm = make_pixmap(dp);
+    hipLaunchKernelGGL(write_launch_consts, dim3(1), dim3(1), 0, stream, s->cx->d_consts, c, (unsigned long long*)queue);
+    if (L.kind == KernelKind::lock_step)
+      hipLaunchKernelGGL(sync_kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                          s->cx->d_counters, s->sync_tune, s->cx->d_stack, window);
-    else if (k3)
-      hipLaunchKernelGGL(k3, dim3(grid), dim3(bt), lds3, stream, s->dev2, (const LaunchConsts*)s->cx->d_consts, d_out, (uint32_t)total_work, queue,
+    else if (p2)
+      hipLaunchKernelGGL(pool2_kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev2, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                          s->cx->d_counters, s->pool2_tune, s->cx->d_slots, s->d_p2);
     else
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, (uint32_t)total_work, queue,
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                          s->cx->d_counters, s->full_tune, s->cx->d_slots, s->cx->d_stack, window);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
-                       sl.divide ? d.ns : 0u);  // (0 = never divide: RTG_FLAG_PARTIAL)
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipSuccess;
+  };
+  return sample_passes(s, d, d_out, stream, sl, L, per_pass, chunks, issue);
 }
 
 // The resolve step of a progressive frame (a call with sample_begin = ns and no RTG_FLAG_PARTIAL): divide the running sum of
 // every owned pixel by ns.  Work items as in the pool kernels (work_to_pixel), so it follows the tiles whichever kernel
 // rendered the samples.
 static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t stream) {
-  const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h, tiles = tiles_x * tiles_y;
-  const uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
-  const uint64_t pix_work = ((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+  const uint64_t pix_work = rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(resolve_sum_kernel, dim3((uint32_t)((pix_work + 255) / 256)), dim3(256), 0, stream, d, make_pixmap(d), (uint32_t)pix_work, d_out);
@@ -483,14 +504,14 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
   // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
-  s->cx->last_kernel = 1;
+  s->cx->last_kernel = KernelKind::baseline;
   if (sl.begin == d.ns) return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;  // nothing to render
   if (geom != 0 && pool_ok) {
-    s->cx->last_kernel = 4;
+    s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)
     return launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl);
   }
   if (geom == 0 && pool_ok) {
-    s->cx->last_kernel = 3;
+    s->cx->last_kernel = KernelKind::lean_pool;
     return launch_pool<COUNT>(s, cam, d, d_out, stream, sl);
   }
   uint32_t nbx = (d.nx + 15) / 16, nby = (d.ny + 15) / 16;

@@ -21,8 +21,8 @@ struct Rccl {
 Rccl g_rccl;
 
 // (g_rccl.mu held)
-bool rccl_load(std::string* why) {
-  if (g_rccl.lib) return true;
+int rccl_load() {
+  if (g_rccl.lib) return RTG_OK;
   void* h = nullptr;
   std::string tried;
   auto attempt = [&](const char* n, int flags) {
@@ -41,10 +41,7 @@ bool rccl_load(std::string* why) {
     for (const char* n : {"librccl.so", "librccl.so.1"}) attempt(n, RTLD_NOW | RTLD_NOLOAD);
     for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) attempt(n, RTLD_NOW | RTLD_LOCAL);
   }
-  if (!h) {
-    *why = "librccl not loadable: " + (tried.empty() ? std::string("?") : tried);
-    return false;
-  }
+  if (!h) return fail(RTG_ERR_DEVICE, "librccl not loadable: " + (tried.empty() ? std::string("?") : tried));
   auto sym = [&](const char* n) { return dlsym(h, n); };
   g_rccl.CommInitAll = (decltype(g_rccl.CommInitAll))sym("ncclCommInitAll");
   g_rccl.CommDestroy = (decltype(g_rccl.CommDestroy))sym("ncclCommDestroy");
@@ -55,12 +52,11 @@ bool rccl_load(std::string* why) {
   g_rccl.Send = (decltype(g_rccl.Send))sym("ncclSend");
   g_rccl.Recv = (decltype(g_rccl.Recv))sym("ncclRecv");
   if (!g_rccl.CommInitAll || !g_rccl.CommDestroy || !g_rccl.GroupStart || !g_rccl.GroupEnd || !g_rccl.Reduce || !g_rccl.GetErrorString) {
-    *why = "librccl lacks ncclCommInitAll / ncclCommDestroy / ncclGroupStart / ncclGroupEnd / ncclReduce / ncclGetErrorString";
     dlclose(h);
-    return false;
+    return fail(RTG_ERR_DEVICE, "librccl lacks ncclCommInitAll / ncclCommDestroy / ncclGroupStart / ncclGroupEnd / ncclReduce / ncclGetErrorString");
   }
   g_rccl.lib = h;
-  return true;
+  return RTG_OK;
 }
 
 // (g_rccl.mu held) destroy the cached cliques
@@ -72,13 +68,11 @@ void rccl_drop_comms() {
   g_rccl.comms.clear();
 }
 
-// ONE collective over the distinct devices: reduce(sum) of the float3 framebuffers heads[k]->d_frame (device devs[k],
-// stream heads[k]->own_stream) to heads[0]'s.  On any failure the group is still closed and the communicators of this
-// device list are dropped (their state is unknown); the caller synchronizes the streams.
-int rccl_reduce_frames(const std::vector<int>& devs, const std::vector<rtg_scene*>& heads, size_t n_floats) {
-  std::lock_guard<std::mutex> lock(g_rccl.mu);
-  std::string why;
-  if (!rccl_load(&why)) return fail(RTG_ERR_DEVICE, why);
+// (g_rccl.mu held) ONE grouped collective over the clique of this device list (created on first use): `body(comms, err)` issues
+// its calls, stopping at the first failure, which it reports in `err`.  The group is always closed (a group left open would
+// swallow every later RCCL call of the process); after any failure the clique's communicators are dropped (their state is
+// unknown).  The caller synchronizes the streams.
+int rccl_group(const std::vector<int>& devs, const std::function<void(const std::vector<ncclComm_t>&, std::string&)>& body) {
   auto it = g_rccl.comms.find(devs);
   if (it == g_rccl.comms.end()) {
     std::vector<ncclComm_t> c(devs.size(), nullptr);
@@ -91,55 +85,51 @@ int rccl_reduce_frames(const std::vector<int>& devs, const std::vector<rtg_scene
   if (r != ncclSuccess) {
     err = std::string("ncclGroupStart: ") + g_rccl.GetErrorString(r);
   } else {
+    body(it->second, err);
+    const ncclResult_t r2 = g_rccl.GroupEnd();
+    if (r2 != ncclSuccess && err.empty()) err = std::string("ncclGroupEnd: ") + g_rccl.GetErrorString(r2);
+  }
+  if (err.empty()) return RTG_OK;
+  for (ncclComm_t c : it->second)
+    if (c) (void)g_rccl.CommDestroy(c);
+  g_rccl.comms.erase(it);
+  return fail(RTG_ERR_DEVICE, err);
+}
+
+// ONE collective over the distinct devices: reduce(sum) of the float3 framebuffers heads[k]->d_frame (device devs[k],
+// stream heads[k]->own_stream) to heads[0]'s.
+int rccl_reduce_frames(const std::vector<int>& devs, const std::vector<rtg_scene*>& heads, size_t n_floats) {
+  std::lock_guard<std::mutex> lock(g_rccl.mu);
+  if (int rc = rccl_load()) return rc;
+  return rccl_group(devs, [&](const std::vector<ncclComm_t>& comms, std::string& err) {
     for (size_t k = 0; k < devs.size() && err.empty(); k++) {
       hipError_t he = hipSetDevice(devs[k]);
       if (he != hipSuccess) {
         err = std::string("hipSetDevice: ") + hipGetErrorString(he);
         break;
       }
-      r = g_rccl.Reduce(heads[k]->d_frame, heads[k]->d_frame, n_floats, ncclFloat, ncclSum, 0, it->second[k], heads[k]->own_stream);
+      ncclResult_t r = g_rccl.Reduce(heads[k]->d_frame, heads[k]->d_frame, n_floats, ncclFloat, ncclSum, 0, comms[k], heads[k]->own_stream);
       if (r != ncclSuccess) err = std::string("ncclReduce: ") + g_rccl.GetErrorString(r);
       else g_rccl.n_reduces++;
     }
-    const ncclResult_t r2 = g_rccl.GroupEnd();  // always: a group left open would swallow every later RCCL call of the process
-    if (r2 != ncclSuccess && err.empty()) err = std::string("ncclGroupEnd: ") + g_rccl.GetErrorString(r2);
-  }
-  if (!err.empty()) {
-    for (ncclComm_t c : it->second)
-      if (c) (void)g_rccl.CommDestroy(c);
-    g_rccl.comms.erase(it);
-    return fail(RTG_ERR_DEVICE, err);
-  }
-  return RTG_OK;
+  });
 }
 
 // The PACKED collective (scene option multi_gather): every scene ships only the pixels it owns -- its tiles in work-item order
 // (rt_pool.h work_to_pixel: pix_work x float3, 1 / n_scenes of the frame) -- to the first device, which scatters them into the frame.
 // Grouped ncclSend / ncclRecv: scene i's packed tiles (sends[k]: buffer, floats, clique rank of its device) arrive in recvs[k] on
-// device 0.  Copies only: bit-identical by construction.  Same failure rule as rccl_reduce_frames.
+// device 0.  Copies only: bit-identical by construction.
 struct PackedMove { const float* src; float* dst; size_t n_floats; int from; hipStream_t src_stream; };
 int rccl_gather_tiles(const std::vector<int>& devs, const std::vector<rtg_scene*>& heads, const std::vector<PackedMove>& moves) {
   std::lock_guard<std::mutex> lock(g_rccl.mu);
-  std::string why;
-  if (!rccl_load(&why)) return fail(RTG_ERR_DEVICE, why);
+  if (int rc = rccl_load()) return rc;
   if (!g_rccl.Send || !g_rccl.Recv) return fail(RTG_ERR_DEVICE, "librccl lacks ncclSend / ncclRecv (the packed collective needs them)");
-  auto it = g_rccl.comms.find(devs);
-  if (it == g_rccl.comms.end()) {
-    std::vector<ncclComm_t> c(devs.size(), nullptr);
-    ncclResult_t r = g_rccl.CommInitAll(c.data(), (int)devs.size(), devs.data());
-    if (r != ncclSuccess) return fail(RTG_ERR_DEVICE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r));
-    it = g_rccl.comms.emplace(devs, std::move(c)).first;
-  }
-  std::string err;
-  ncclResult_t r = g_rccl.GroupStart();
-  if (r != ncclSuccess) {
-    err = std::string("ncclGroupStart: ") + g_rccl.GetErrorString(r);
-  } else {
+  return rccl_group(devs, [&](const std::vector<ncclComm_t>& comms, std::string& err) {
     for (size_t k = 0; k < moves.size() && err.empty(); k++) {
       const PackedMove& m = moves[k];
       hipError_t he = hipSetDevice(devs[m.from]);
       if (he == hipSuccess) {
-        r = g_rccl.Send(m.src, m.n_floats, ncclFloat, 0, it->second[m.from], m.src_stream);
+        ncclResult_t r = g_rccl.Send(m.src, m.n_floats, ncclFloat, 0, comms[m.from], m.src_stream);
         if (r != ncclSuccess) err = std::string("ncclSend: ") + g_rccl.GetErrorString(r);
         he = hipSetDevice(devs[0]);
       }
@@ -148,21 +138,12 @@ int rccl_gather_tiles(const std::vector<int>& devs, const std::vector<rtg_scene*
         break;
       }
       if (err.empty()) {
-        r = g_rccl.Recv(m.dst, m.n_floats, ncclFloat, m.from, it->second[0], heads[0]->own_stream);
+        ncclResult_t r = g_rccl.Recv(m.dst, m.n_floats, ncclFloat, m.from, comms[0], heads[0]->own_stream);
         if (r != ncclSuccess) err = std::string("ncclRecv: ") + g_rccl.GetErrorString(r);
         else g_rccl.n_reduces++;
       }
     }
-    const ncclResult_t r2 = g_rccl.GroupEnd();
-    if (r2 != ncclSuccess && err.empty()) err = std::string("ncclGroupEnd: ") + g_rccl.GetErrorString(r2);
-  }
-  if (!err.empty()) {
-    for (ncclComm_t c : it->second)
-      if (c) (void)g_rccl.CommDestroy(c);
-    g_rccl.comms.erase(it);
-    return fail(RTG_ERR_DEVICE, err);
-  }
-  return RTG_OK;
+  });
 }
 
 // work item w of the rank P.rank -> its pixel (rt_pool.h work_to_pixel); items beyond the image are padding
@@ -185,11 +166,6 @@ __global__ void unpack_tiles_kernel(DevParams P, PixMap pm, uint32_t pix_work, c
   float* p = fb + 3ull * ((size_t)row * P.nx + x);
   p[0] = packed[3ull * w], p[1] = packed[3ull * w + 1], p[2] = packed[3ull * w + 2];
 }
-static uint32_t rank_pix_work(const DevParams& d) {
-  const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h, tiles = tiles_x * tiles_y;
-  const uint32_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
-  return (uint32_t)(((uint64_t)owned * d.tile_w * d.tile_h + 255u) & ~255ull);
-}
 
 // RTG_FLAG_RESUME: scene i's full frame starts as the caller's running sums on the pixels it owns and +0 on every other pixel, so
 // that the reduce (x + 0 is exact; a sum starts at +0, so it is never -0) and the packed gather assemble the frame unchanged
@@ -210,10 +186,32 @@ __global__ void add_frames_kernel(size_t n, float* __restrict__ dst, const float
 // Tile size when the caller leaves it to the library (tile_w / tile_h = 0): 16x16 up to 7 devices, 8x8 from 8 on -- with an eighth
 // of the tiles per device the slowest shard of the 16x16 interleave lies 5-6 % above the mean, with 8x8 tiles 2-4 %
 // (profiles/r04_experiments/r04x_shard_tiles.txt; the same rule as rtiow-rust_amd/parallel.py shard_tile, which bench.py uses).
-static void multi_default_tiles(rtg_params* p, int n_scenes) {
+// Scene i's checked DevParams: the caller's params as rank i of n_scenes, with those tiles.
+static int rank_params(const rtg_scene* s, const rtg_camera* camera, const rtg_params* params, int i, int n_scenes, DevParams* d) {
+  rtg_params p = *params;
+  p.rank = (uint32_t)i, p.nranks = (uint32_t)n_scenes;
   const uint32_t t = n_scenes >= 8 ? 8u : 16u;
-  if (p->tile_w == 0) p->tile_w = t;
-  if (p->tile_h == 0) p->tile_h = t;
+  if (p.tile_w == 0) p.tile_w = t;
+  if (p.tile_h == 0) p.tile_h = t;
+  return check_params(s, camera, &p, d);
+}
+
+// The scenes' distinct devices in order of first appearance, the first scene on each (`heads`: it holds that device's frame)
+// and, per scene, the index of its device in both
+struct DeviceGroups {
+  std::vector<int> devs;
+  std::vector<rtg_scene*> heads;
+  std::vector<int> of;
+};
+static DeviceGroups group_by_device(rtg_scene* const* scenes, int n_scenes) {
+  DeviceGroups g;
+  for (int i = 0; i < n_scenes; i++) {
+    size_t k = 0;
+    while (k < g.devs.size() && g.devs[k] != scenes[i]->device) k++;
+    if (k == g.devs.size()) g.devs.push_back(scenes[i]->device), g.heads.push_back(scenes[i]);
+    g.of.push_back((int)k);
+  }
+  return g;
 }
 
 static int multi_stats(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params, rtg_stats* stats, bool count) {
@@ -226,11 +224,8 @@ static int multi_stats(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, s->cx->ev0, s->cx->ev1));
       total.kernel_ms = std::max(total.kernel_ms, ms);
-      rtg_params p = *params;
-      p.rank = (uint32_t)i, p.nranks = (uint32_t)n_scenes;
-      multi_default_tiles(&p, n_scenes);
       DevParams d;
-      (void)check_params(s, camera, &p, &d);
+      (void)rank_params(s, camera, params, i, n_scenes, &d);
       total.samples += owned_pixels(d) * (d.ns - slice_of(params).begin);
       if (count) {
         unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -263,12 +258,8 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
       const int rc_ctx = ctx_acquire(s);
       if (rc_ctx) return rc_ctx;
     }
-    rtg_params p = *params;
-    p.rank = (uint32_t)i, p.nranks = (uint32_t)n_scenes;
-    multi_default_tiles(&p, n_scenes);
     DevParams d;
-    int rc = check_params(s, camera, &p, &d);
-    if (rc) return rc;
+    if (int rc = rank_params(s, camera, params, i, n_scenes, &d)) return rc;
     if (sl.begin != 0u) {
       hipLaunchKernelGGL(keep_owned_kernel, dim3((uint32_t)(((size_t)d.nx * d.ny + 255) / 256)), dim3(256), 0, s->own_stream, d, s->d_frame);
       HIP_TRY(hipGetLastError());
@@ -286,33 +277,24 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
       if (rc_ctx) return rc_ctx;
     }
   }
-  bool gather = false;
-  for (int i = 0; i < n_scenes; i++) gather = gather || scenes[i]->multi_gather != 0;
+  bool gather = false, force_rccl = false;
+  for (int i = 0; i < n_scenes; i++) {
+    gather = gather || scenes[i]->multi_gather != 0;
+    force_rccl = force_rccl || scenes[i]->force_rccl != 0;
+  }
+  const DeviceGroups g = group_by_device(scenes, n_scenes);
+  const std::vector<int>& devs = g.devs;
+  const std::vector<rtg_scene*>& heads = g.heads;
   if (gather) {
     // (2') the packed collective: every scene packs ITS tiles (work-item order); the ones on other devices travel to the first
     // device by grouped ncclSend / ncclRecv, and the first device scatters all of them into its frame
-    std::vector<int> devs;
-    std::vector<rtg_scene*> heads;
-    bool force_rccl = false;
-    std::vector<int> dev_of(n_scenes, 0);
-    for (int i = 0; i < n_scenes; i++) {
-      force_rccl = force_rccl || scenes[i]->force_rccl != 0;
-      size_t k = 0;
-      while (k < devs.size() && devs[k] != scenes[i]->device) k++;
-      if (k == devs.size()) devs.push_back(scenes[i]->device), heads.push_back(scenes[i]);
-      dev_of[i] = (int)k;
-    }
     std::vector<PackedMove> moves;
     std::vector<DevParams> dps(n_scenes);
     std::vector<const float*> at_head(n_scenes, nullptr);  // where scene i's packed tiles stand on the first device
     for (int i = 0; i < n_scenes; i++) {
       rtg_scene* s = scenes[i];
-      rtg_params p = *params;
-      p.rank = (uint32_t)i, p.nranks = (uint32_t)n_scenes;
-      multi_default_tiles(&p, n_scenes);
-      int rc = check_params(s, camera, &p, &dps[i]);
-      if (rc) return rc;
-      const uint32_t pw = rank_pix_work(dps[i]);
+      if (int rc = rank_params(s, camera, params, i, n_scenes, &dps[i])) return rc;
+      const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
       if (pw == 0) continue;
       HIP_TRY(hipSetDevice(s->device));
       hipError_t e = grow((void**)&s->d_pack, &s->pack_bytes, (size_t)pw * 3 * sizeof(float));
@@ -320,12 +302,12 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
       hipLaunchKernelGGL(pack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, s->own_stream, dps[i], make_pixmap(dps[i]), pw, (const float*)s->d_frame, s->d_pack);
       HIP_TRY(hipGetLastError());
       // (a clique of one under force_rccl: the first scene's tiles take the send / recv path too, to itself)
-      const bool travels = dev_of[i] != 0 || (force_rccl && devs.size() == 1 && i == 0);
+      const bool travels = g.of[i] != 0 || (force_rccl && devs.size() == 1 && i == 0);
       if (travels) {
         HIP_TRY(hipSetDevice(devs[0]));
         e = grow((void**)&s->d_recv, &s->recv_bytes, (size_t)pw * 3 * sizeof(float));
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(received tiles)");
-        moves.push_back(PackedMove{s->d_pack, s->d_recv, (size_t)pw * 3, dev_of[i], s->own_stream});
+        moves.push_back(PackedMove{s->d_pack, s->d_recv, (size_t)pw * 3, g.of[i], s->own_stream});
         at_head[i] = s->d_recv;
       } else {
         at_head[i] = s->d_pack;
@@ -339,12 +321,12 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
     HIP_TRY(hipSetDevice(devs[0]));
     for (int i = 0; i < n_scenes; i++) {
       if (!at_head[i] || scenes[i] == heads[0]) continue;  // (the first scene's own tiles already stand in its frame)
-      const uint32_t pw = rank_pix_work(dps[i]);
+      const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
       hipLaunchKernelGGL(unpack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, heads[0]->own_stream, dps[i], make_pixmap(dps[i]), pw, at_head[i], heads[0]->d_frame);
       HIP_TRY(hipGetLastError());
     }
     if (at_head[0] == scenes[0]->d_recv && at_head[0]) {  // clique of one: what came back through RCCL replaces the first scene's tiles
-      const uint32_t pw = rank_pix_work(dps[0]);
+      const uint32_t pw = (uint32_t)rank_pix_work(dps[0]);
       hipLaunchKernelGGL(unpack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, heads[0]->own_stream, dps[0], make_pixmap(dps[0]), pw, at_head[0], heads[0]->d_frame);
       HIP_TRY(hipGetLastError());
     }
@@ -361,22 +343,12 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
     return multi_stats(scenes, n_scenes, camera, params, stats, count);
   }
   // (2) scenes that share a device with an earlier one are summed there; one frame per DISTINCT device remains
-  std::vector<int> devs;          // distinct devices in order of first appearance
-  std::vector<rtg_scene*> heads;  // the scene holding each device's partial frame
-  bool force_rccl = false;
   for (int i = 0; i < n_scenes; i++) {
-    rtg_scene* s = scenes[i];
-    force_rccl = force_rccl || s->force_rccl != 0;
-    size_t k = 0;
-    while (k < devs.size() && devs[k] != s->device) k++;
-    if (k == devs.size()) {
-      devs.push_back(s->device), heads.push_back(s);
-      continue;
-    }
+    rtg_scene *s = scenes[i], *h = heads[g.of[i]];
+    if (s == h) continue;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->own_stream));
-    hipLaunchKernelGGL(add_frames_kernel, dim3((uint32_t)((n_floats + 255) / 256)), dim3(256), 0, heads[k]->own_stream, n_floats,
-                       heads[k]->d_frame, s->d_frame);
+    hipLaunchKernelGGL(add_frames_kernel, dim3((uint32_t)((n_floats + 255) / 256)), dim3(256), 0, h->own_stream, n_floats, h->d_frame, s->d_frame);
     HIP_TRY(hipGetLastError());
   }
   // (3) ONE collective over the distinct devices: reduce(sum) of the float3 framebuffer to the first device (xGMI).

@@ -41,10 +41,8 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
     // Trace the PRODUCTION kernel: render the whole frame with the instrumented variant of whatever kernel par_cast
     // uses for this scene, with its per-sample trace table switched on, then pick the requested keys out of the table
     // (colour: the per-sample scratch the ordered fold reads).
-    const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w, tiles_y = (d.ny + d.tile_h - 1) / d.tile_h;
-    const uint32_t tiles = tiles_x * tiles_y;
-    const uint64_t owned = tiles > d.rank ? (tiles - d.rank + d.nranks - 1) / d.nranks : 0;
-    const uint64_t pix_work = (owned * d.tile_w * d.tile_h + 255u) & ~255ull;
+    const uint32_t tiles_x = (d.nx + d.tile_w - 1) / d.tile_w;
+    const uint64_t pix_work = rank_pix_work(d);
     // per-slot accumulators, indexed by (workgroup * waves + wave): a CU holds at most 32 waves of these kernels, and the
     // `wg_per_cu` option may ask for more (queued) workgroups of up to 16 waves each
     const size_t trace_waves = (size_t)s->num_cus * std::max(32, s->wg_per_cu > 0 ? s->wg_per_cu * 16 : 0);
@@ -64,7 +62,7 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipMemset(s->cx->d_counters + 30, 0, 2 * sizeof(unsigned long long));
     if (e != hipSuccess) return hip_fail(e, "trace launch");
-    if (s->cx->last_kernel < 3 || s->cx->last_pix_work == 0)
+    if (s->cx->last_kernel == KernelKind::baseline || s->cx->last_pix_work == 0)
       return fail(RTG_ERR_UNSUPPORTED, "this scene / frame runs on the baseline kernel (or without the per-sample scratch): nothing to trace");
     std::vector<uint32_t> h_trace(table);
     std::vector<float> h_col((size_t)3 * d.ns * pix_work);
