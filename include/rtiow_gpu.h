@@ -89,6 +89,22 @@ typedef struct rtg_params {
  * nranks); the library cannot check this.  rtg_par_cast, rtg_par_cast_device and rtg_par_cast_multi honour both flags;
  * rtg_debug_samples rejects them (RTG_ERR_INVALID). */
 
+#define RTG_FLAG_SUM_SQUARES 16u /* out holds a second plane: the running sum of the squared sample colours (below) */
+
+/* Per-pixel noise estimates.  With RTG_FLAG_SUM_SQUARES `out` holds two planes of nx * ny * 3 floats each (2 * nx * ny * 3 in
+ * all).  Plane 0 is exactly what the call writes without the flag.  Plane 1 starts at out + 3 * nx * ny, has the same pixel
+ * layout, and holds per pixel and channel the f32 left fold q = q + (c * c) over the samples c in order, from +0: the product
+ * is rounded before the add (no fused multiply-add).  (sum, sum of squares, n) give each pixel's sample variance and the
+ * standard error of its mean (rtiow-rust_amd/noise.py).
+ *   - Plane 1 is never divided, with or without RTG_FLAG_PARTIAL.
+ *   - RTG_FLAG_RESUME: plane 1 holds the sum over samples [0, sample_begin) and the call continues it.  The resolve call
+ *     (sample_begin == ns, no PARTIAL) divides plane 0 and leaves plane 1 bit for bit as it was.
+ *   - Pixels of other ranks / tiles stay untouched in both planes.
+ *   - rtg_par_cast and rtg_par_cast_device honour the flag; rtg_par_cast_multi returns RTG_ERR_UNSUPPORTED and writes and
+ *     enqueues nothing; rtg_debug_samples returns RTG_ERR_INVALID.
+ *   - The lean ray-pool kernel then always parks every sample colour in its scratch for the fold, one sample per work item:
+ *     scene option "chunks" is overridden for the call.  rtg_stats and its counters are those of the call without the flag. */
+
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */

@@ -11,6 +11,8 @@ import time
 
 import numpy as np
 
+from . import noise
+
 c_f32p = C.POINTER(C.c_float)
 c_u32p = C.POINTER(C.c_uint32)
 c_u8p = C.POINTER(C.c_uint8)
@@ -20,6 +22,7 @@ FLAG_COUNTERS = 1
 FLAG_TRACE_KERNEL = 2
 FLAG_PARTIAL = 4   # leave the unnormalised running sum of the samples in the framebuffer
 FLAG_RESUME = 8    # the framebuffer holds the running sum of samples [0, sample_begin): render [sample_begin, ns)
+FLAG_SUM_SQUARES = 16   # the framebuffer has a second plane: the running sum of the squared sample colours
 
 
 class Camera(C.Structure):
@@ -47,10 +50,10 @@ class Stats(C.Structure):
 
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
-                nranks=1, flags=0, sample_begin=0, partial=False, resume=False):
+                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False):
     """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
-    RTG_FLAG_RESUME)."""
-    flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0)
+    RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane."""
+    flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.nx, p.ny, p.ns = nx, ny, ns
@@ -81,6 +84,27 @@ def _hip_runtime():
 
 def _resumes(kw):
     return bool(kw.get("resume")) and kw.get("sample_begin", 0) > 0
+
+
+def _squares_supported(be):
+    """RTG_FLAG_SUM_SQUARES is the HIP library's (prefix rtg_): a library that exports the same entry points under another
+    prefix ignores flags it does not know and would write one plane where the caller expects two."""
+    if be.prefix != "rtg_":
+        raise ValueError("squares=True: %s (prefix %s) does not implement RTG_FLAG_SUM_SQUARES" % (be.path, be.prefix))
+
+
+def _host_frame(out, nx, ny, kw):
+    """The host framebuffer of a par_cast call: `out`, checked, or a new zeroed one -- [ny, nx, 3] float32, or [2, ny, nx, 3]
+    with squares=True (the library writes both planes: a smaller array would be overrun)."""
+    shape = (2, ny, nx, 3) if kw.get("squares") else (ny, nx, 3)
+    if out is None:
+        if _resumes(kw):
+            raise ValueError("resume=True needs out= (the running sum to continue)")
+        return np.zeros(shape, dtype=np.float32)
+    if kw.get("squares") and not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == np.float32
+                                  and out.flags.c_contiguous):
+        raise ValueError("squares=True needs out= a C-contiguous float32 array of shape %s" % (shape,))
+    return out
 
 
 # error codes of include/rtiow_gpu.h
@@ -215,10 +239,7 @@ class Backend:
         them, ONE RCCL reduce(sum) of the float3 framebuffer inside the library.  Returns the assembled frame.
         resume=True, sample_begin=k: `out` holds the running sum of samples [0, k) (as a partial=True call left it)."""
         p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
-        if out is None:
-            if _resumes(kw):
-                raise ValueError("resume=True needs out= (the running sum to continue)")
-            out = np.zeros((ny, nx, 3), dtype=np.float32)
+        out = _host_frame(out, nx, ny, kw)
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         arr = (C.c_void_p * len(scenes))(*[s.h for s in scenes])
@@ -425,12 +446,13 @@ class Scene:
     def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, **kw):
         """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
         One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
-        continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h)."""
+        continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h).
+        squares=True (RTG_FLAG_SUM_SQUARES): float32 [2, ny, nx, 3] instead -- [0] as without the flag, [1] the running sum
+        of the squared sample colours; `out`, when given, must have that shape."""
+        if kw.get("squares"):
+            _squares_supported(self.be)
         p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
-        if out is None:
-            if _resumes(kw):
-                raise ValueError("resume=True needs out= (the running sum to continue)")
-            out = np.zeros((ny, nx, 3), dtype=np.float32)
+        out = _host_frame(out, nx, ny, kw)
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), out.ctypes.data_as(c_f32p), C.byref(st)],
@@ -439,14 +461,17 @@ class Scene:
         return (out, st.as_dict()) if stats else out
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None):
-        """rtg_par_cast_device.  sample_begin / partial / resume, when given, override those of `params` (a copy)."""
-        if sample_begin is not None or partial is not None or resume is not None:
+                        resume=None, squares=None):
+        """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
+        With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats."""
+        if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
+            _squares_supported(self.be)
+        if sample_begin is not None or partial is not None or resume is not None or squares is not None:
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
-            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME)):
+            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES)):
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
@@ -456,7 +481,8 @@ class Scene:
                                                C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
-    def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None, **kw):
+    def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None,
+                    squares=False, target_rmse=None, **kw):
         """Render a frame `step` samples at a time (include/rtiow_gpu.h progressive rendering).  Yields (n_done, preview)
         after each slice: the preview is bit-identical to par_cast(ns = n_done), and the one at n_done == ns is the final
         image, bit-identical to par_cast(ns).  Stops at ns, or after the first slice that ends past `budget_s` seconds.
@@ -464,28 +490,47 @@ class Scene:
         is a new array.  Device frames: `out` and `preview` are device buffers of nx * ny * 3 floats on the scene's device
         (a pointer, or an object with data_ptr() such as a torch tensor) and `stream` a hipStream_t (int, an object with
         .cuda_stream, or None = the default stream): the same loop over par_cast_device, every slice, copy and resolve
-        enqueued on that stream; `preview` is rewritten by each slice.  **kw: tiling / max_bounces / t_near."""
+        enqueued on that stream; `preview` is rewritten by each slice.
+        squares=True (RTG_FLAG_SUM_SQUARES): the running sums have two planes -- `out` is [2, ny, nx, 3] on the host, 2 * nx * ny
+        * 3 floats on the device -- and the loop yields (n_done, preview, stderr).  On the host, stderr is
+        noise.standard_error of every pixel and channel (float64 [ny, nx, 3]); on the device it is `out` itself, the two
+        planes the estimate is computed from (no device-side reduction).
+        target_rmse (host frames; implies squares): stop after the first slice whose noise.estimated_rmse is <= target_rmse
+        -- or at ns, or at budget_s, whichever comes first.  **kw: tiling / max_bounces / t_near."""
         if step < 1:
             raise ValueError("step must be >= 1")
+        squares = bool(squares) or target_rmse is not None
+        if squares:
+            _squares_supported(self.be)
         if out is not None and not isinstance(out, np.ndarray):
+            if target_rmse is not None:
+                raise ValueError("target_rmse needs host frames: there is no device-side error reduction")
             if preview is None:
                 raise ValueError("a device running sum needs a device preview buffer (preview=)")
-            yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, kw)
+            yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, squares, kw)
             return
-        acc = np.zeros((ny, nx, 3), dtype=np.float32) if out is None else out
+        shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
+        acc = np.zeros(shape, dtype=np.float32) if out is None else out
+        sums = acc[0] if squares else acc
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, **kw)
+            self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, squares=squares, **kw)
             done = end
-            frame = acc.copy()   # resolve a copy: the running sum goes on
+            frame = sums.copy()   # resolve a copy: the running sum goes on
             self.par_cast(camera, nx, ny, done, seed=seed, out=frame, sample_begin=done, resume=True, **kw)
-            yield done, frame
+            if squares:
+                se = noise.standard_error(acc[0], acc[1], done)
+                yield done, frame, se
+                if target_rmse is not None and float(np.sqrt(np.mean(se * se))) <= target_rmse:
+                    return
+            else:
+                yield done, frame
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
-    def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, kw):
+    def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw):
         hip = _hip_runtime()
         d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
@@ -493,14 +538,14 @@ class Scene:
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True, **kw),
-                                 d_acc, hs)
+            self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
+                                                     squares=squares, **kw), d_acc, hs)
             done = end
-            rc = hip.hipMemcpyAsync(d_preview, d_acc, nx * ny * 3 * 4, 3, hs)   # 3 = hipMemcpyDeviceToDevice
+            rc = hip.hipMemcpyAsync(d_preview, d_acc, nx * ny * 3 * 4, 3, hs)   # plane 0; 3 = hipMemcpyDeviceToDevice
             if rc != 0:
                 raise RtError(ERR_DEVICE, "hipMemcpyAsync(preview) failed: %d" % rc)
             self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, **kw), d_preview, hs)
-            yield done, preview
+            yield (done, preview, acc) if squares else (done, preview)
             if budget_s is not None:
                 if hip.hipStreamSynchronize(hs) != 0:
                     raise RtError(ERR_DEVICE, "hipStreamSynchronize failed")

@@ -338,6 +338,41 @@ __global__ void fold_samples_kernel(DevParams P, ChunkMode cm, PixMap pm, float*
   o[0] = col.x, o[1] = col.y, o[2] = col.z;
 }
 
+// the same fold under RTG_FLAG_SUM_SQUARES (include/rtiow_gpu.h): plane 0 (`out`) exactly as fold_samples_kernel writes it,
+// and plane 1 (out + 3 nx ny) the running sum of the squared colours, q = q + (c * c) in sample order from +0 -- or from what
+// the previous pass / slice left there -- never divided.  A lane loads RT_FOLD_DEPTH samples' colours before it adds the first
+// of them (the loads are independent; the adds stay in order); a warp's loads of one sample are contiguous 12-byte records.
+#ifndef RT_FOLD_DEPTH
+#define RT_FOLD_DEPTH 4u
+#endif
+__global__ void fold_samples_sq_kernel(DevParams P, ChunkMode cm, PixMap pm, float* __restrict__ out, uint32_t ns_frame) {
+  uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= cm.pix_work) return;
+  uint32_t x, row;
+  if (!work_to_pixel(P, pm, w, x, row)) return;
+  float* o = out + 3ull * ((size_t)row * P.nx + x);
+  float* q = o + 3ull * ((size_t)P.nx * P.ny);
+  V3 col = mk(0.f, 0.f, 0.f), sq = mk(0.f, 0.f, 0.f);
+  if (cm.s_begin != 0u) col = mk(o[0], o[1], o[2]), sq = mk(q[0], q[1], q[2]);
+  const float* c = cm.scratch + 3ull * ((size_t)cm.s_begin * cm.pix_work + w);
+  const size_t step = 3ull * cm.pix_work;
+  uint32_t s = cm.s_begin;
+  for (; s + RT_FOLD_DEPTH <= P.ns; s += RT_FOLD_DEPTH) {
+    V3 v[RT_FOLD_DEPTH];
+#pragma unroll
+    for (uint32_t k = 0; k < RT_FOLD_DEPTH; k++, c += step) v[k] = mk(RT_SCRATCH_LOAD(c), RT_SCRATCH_LOAD(c + 1), RT_SCRATCH_LOAD(c + 2));
+#pragma unroll
+    for (uint32_t k = 0; k < RT_FOLD_DEPTH; k++) col = vadd(col, v[k]), sq = vadd(sq, vmul(v[k], v[k]));
+  }
+  for (; s < P.ns; s++, c += step) {
+    const V3 v = mk(RT_SCRATCH_LOAD(c), RT_SCRATCH_LOAD(c + 1), RT_SCRATCH_LOAD(c + 2));
+    col = vadd(col, v), sq = vadd(sq, vmul(v, v));
+  }
+  if (P.ns == ns_frame) col = sdiv(col, (float)ns_frame);
+  o[0] = col.x, o[1] = col.y, o[2] = col.z;
+  q[0] = sq.x, q[1] = sq.y, q[2] = sq.z;
+}
+
 // the resolve step of a progressive frame (include/rtiow_gpu.h RTG_FLAG_RESUME with sample_begin = ns): the running sum of
 // every pixel this rank owns divided by the frame's sample count, as the last fold pass would have done (lib.rs:374)
 __global__ void resolve_sum_kernel(DevParams P, PixMap pm, uint32_t pix_work, float* __restrict__ out) {

@@ -180,12 +180,14 @@ static int ctx_release(rtg_scene* s, hipStream_t stream) {
 struct SampleSlice {
   uint32_t begin = 0;   // first sample this call renders; the framebuffer holds the running sum of [0, begin) when it is > 0
   bool divide = true;   // false under RTG_FLAG_PARTIAL: the running sum stays in the framebuffer
+  bool squares = false; // RTG_FLAG_SUM_SQUARES: the framebuffer has a second plane, the running sum of the squared colours
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
   SampleSlice sl;
   if (p->flags & RTG_FLAG_RESUME) sl.begin = p->sample_begin;
   if (p->flags & RTG_FLAG_PARTIAL) sl.divide = false;
+  if (p->flags & RTG_FLAG_SUM_SQUARES) sl.squares = true;
   return sl;
 }
 
@@ -805,7 +807,8 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     if (rc0) return rc0;
   }
   HIP_TRY(hipSetDevice(s->device));
-  size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float);
+  // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares)
+  size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (slice_of(params).squares ? 2 : 1);
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
   hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, bytes ? bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");

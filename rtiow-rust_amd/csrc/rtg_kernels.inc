@@ -18,7 +18,9 @@ __device__ __forceinline__ void flush_counts(const Counts& c, uint32_t draws, un
 // Block = 16x16 pixels, each wave an 8x8 sub-tile (primary rays of a wave stay coherent).
 // SLICE (render_slice_kernel only, include/rtiow_gpu.h progressive rendering): the fold starts at sample s_begin from the
 // running sum `out` holds (+0 when s_begin = 0) and divides only when `divide` -- the plain instantiations do not see it.
-template <uint32_t FEAT, bool COUNT, bool SLICE>
+// SQ (render_squares_kernel only, RTG_FLAG_SUM_SQUARES): a second fold of the squared colours into plane 1 (out + 3 nx ny),
+// continued like the first and never divided.
+template <uint32_t FEAT, bool COUNT, bool SLICE, bool SQ = false>
 __device__ __forceinline__ void render_pixel(const DevScene& sc, const DevCamera& cam, const DevParams& P, float* out,
                                              unsigned long long* counters, uint32_t s_begin, bool divide) {
   const uint32_t nbx = (P.nx + 15u) / 16u;
@@ -34,21 +36,24 @@ __device__ __forceinline__ void render_pixel(const DevScene& sc, const DevCamera
   const uint32_t y = P.ny - 1u - row;  // lib.rs:328: row 0 is y = ny-1
   Counts cnt = {0, 0, 0, 0};
   uint32_t total_draws = 0;
-  V3 col = mk(0.f, 0.f, 0.f);
+  V3 col = mk(0.f, 0.f, 0.f), sq = mk(0.f, 0.f, 0.f);
   uint32_t s0 = 0;
   if (SLICE && s_begin != 0u) {
     const float* i = out + 3ull * ((size_t)row * P.nx + x);
     col = mk(i[0], i[1], i[2]), s0 = s_begin;
+    if (SQ) i += 3ull * ((size_t)P.nx * P.ny), sq = mk(i[0], i[1], i[2]);
   }
   for (uint32_t s = s0; s < P.ns; s++) {
     uint32_t bounces, draws;
     V3 c = sample_color<FEAT, COUNT>(sc, cam, P, x, y, s, cnt, bounces, draws);
     col = vadd(col, c);
+    if (SQ) sq = vadd(sq, vmul(c, c));
     if (COUNT) total_draws += draws;
   }
   if (!SLICE || divide) col = sdiv(col, (float)P.ns);  // lib.rs:374
   float* o = out + 3ull * ((size_t)row * P.nx + x);
   o[0] = col.x, o[1] = col.y, o[2] = col.z;
+  if (SQ) o += 3ull * ((size_t)P.nx * P.ny), o[0] = sq.x, o[1] = sq.y, o[2] = sq.z;
   if (COUNT) flush_counts(cnt, total_draws, counters);
 }
 
@@ -63,6 +68,13 @@ template <uint32_t FEAT, bool COUNT>
 __global__ __launch_bounds__(256) void render_slice_kernel(DevScene sc, DevCamera cam, DevParams P, float* out,
                                                            unsigned long long* counters, uint32_t s_begin, uint32_t divide) {
   render_pixel<FEAT, COUNT, true>(sc, cam, P, out, counters, s_begin, divide != 0u);
+}
+
+// RTG_FLAG_SUM_SQUARES: whole frames and slices alike (s_begin = 0, divide = 1: a whole frame), plane 1 beside the sum
+template <uint32_t FEAT, bool COUNT>
+__global__ __launch_bounds__(256) void render_squares_kernel(DevScene sc, DevCamera cam, DevParams P, float* out,
+                                                             unsigned long long* counters, uint32_t s_begin, uint32_t divide) {
+  render_pixel<FEAT, COUNT, true, true>(sc, cam, P, out, counters, s_begin, divide != 0u);
 }
 
 template <uint32_t FEAT>

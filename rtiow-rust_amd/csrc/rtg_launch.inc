@@ -157,8 +157,9 @@ static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, 
     e = issue(s0, dp, cm, grid, (uint32_t)total_work);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (cm.scratch) {  // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL)
-      hipLaunchKernelGGL(fold_samples_kernel, dim3((uint32_t)(((uint64_t)cm.pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
+    if (cm.scratch) {  // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL; RTG_FLAG_SUM_SQUARES: the fold that also sums the squares)
+      void (*fold)(DevParams, ChunkMode, PixMap, float*, uint32_t) = sl.squares ? fold_samples_sq_kernel : fold_samples_kernel;
+      hipLaunchKernelGGL(fold, dim3((uint32_t)(((uint64_t)cm.pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
                          sl.divide ? d.ns : 0u);
       e = hipGetLastError();
       if (e != hipSuccess) return e;
@@ -184,15 +185,16 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   if (s->force_chunks > 0) n_chunks = (uint64_t)s->force_chunks;
   if (n_chunks > ns_call) n_chunks = ns_call;
   // else (ns = 1, or option chunks = 1): a slot folds its pixel's samples itself -- from +0, dividing at the end; a slice of a
-  // progressive frame takes the chunk mode instead, whose fold kernel continues the running sum and divides only when asked
-  const bool use_scratch = n_chunks > 1 || sl.sliced();
+  // progressive frame takes the chunk mode instead, whose fold kernel continues the running sum and divides only when asked,
+  // and so does a call that sums the squares (the fold kernel squares every sample colour: one sample per work item)
+  const bool use_scratch = n_chunks > 1 || sl.sliced() || sl.squares;
   uint32_t per_pass = d.ns, chunk = d.ns;
   if (use_scratch) {
     per_pass = samples_per_pass(s, pix_work, ns_call);
     chunk = (uint32_t)((ns_call + n_chunks - 1) / n_chunks);
     // several passes: one sample per work item; the same when the slice does not begin on a chunk boundary (the kernel ends a
     // work item where s % chunk == 0)
-    if (per_pass < ns_call || sl.begin % chunk != 0u) chunk = 1u;
+    if (per_pass < ns_call || sl.begin % chunk != 0u || sl.squares) chunk = 1u;
     hipError_t ea = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
     if (ea != hipSuccess) return ea;
   }
@@ -516,6 +518,18 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   }
   uint32_t nbx = (d.nx + 15) / 16, nby = (d.ny + 15) / 16;
   dim3 grid(nbx * nby), block(256);
+  if (sl.squares) {
+    // RTG_FLAG_SUM_SQUARES, whole frames and slices: the squares' own instantiations (FEAT_DEEP as below)
+    constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+    const uint32_t divide = sl.divide ? 1u : 0u;
+    if (s->features & FEAT_DEEP)
+      hipLaunchKernelGGL((render_squares_kernel<D, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    else if (geom == 0)
+      hipLaunchKernelGGL((render_squares_kernel<0u, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    else
+      hipLaunchKernelGGL((render_squares_kernel<FEAT_ALL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    return hipGetLastError();
+  }
   if (sl.sliced()) {
     // a slice of a progressive frame: its own instantiations (FEAT_DEEP graphs on the largest general walk, as the probes)
     constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;

@@ -299,6 +299,44 @@ inline size_t par_cast_progressive(size_t nx, size_t ny, size_t ns, size_t step,
   return done;
 }
 
+// Not in the reference: par_cast with RTG_FLAG_SUM_SQUARES.  `image` is exactly what par_cast returns; `sum_sq` (same layout)
+// holds per pixel and channel the f32 running sum of the squared sample colours, from which standard_error estimates the
+// noise of every pixel's mean.
+struct SquaresImage {
+  Image image;
+  std::vector<float> sum_sq;  // ny * nx * 3
+  size_t ns = 0;
+};
+
+inline SquaresImage par_cast_squares(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world,
+                                     const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_SUM_SQUARES;
+  std::vector<float> planes(2 * nx * ny * 3, 0.f);  // plane 0: the image, plane 1: the sum of squares
+  check(rtg_par_cast(s.get(), &camera.c, &p, planes.data(), nullptr));
+  SquaresImage r;
+  r.image.nx = nx, r.image.ny = ny, r.ns = ns;
+  r.image.rgb.assign(planes.begin(), planes.begin() + nx * ny * 3);
+  r.sum_sq.assign(planes.begin() + nx * ny * 3, planes.end());
+  return r;
+}
+
+// Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /
+// (n - 1)), se = sqrt(s2 / n); +inf for n = 1.  `mean` = sum / n (par_cast's image; a PARTIAL running sum divided by n).
+inline double standard_error(double mean, double sum_sq, size_t n) {
+  if (n < 2) return INFINITY;
+  const double nd = (double)n, var = std::max(0.0, (sum_sq - nd * mean * mean) / (nd - 1.0));
+  return std::sqrt(var / nd);
+}
+
+// ... of every pixel channel of a par_cast_squares frame (ny * nx * 3 values)
+inline std::vector<double> standard_error(const SquaresImage& f) {
+  std::vector<double> se(f.sum_sq.size());
+  for (size_t i = 0; i < se.size(); i++) se[i] = standard_error((double)f.image.rgb[i], (double)f.sum_sq[i], f.ns);
+  return se;
+}
+
 // print_ppm, lib.rs:344-361 (host post-process)
 inline void print_ppm(const Image& image, FILE* out = stdout) {
   std::fprintf(out, "P3\n%zu %zu\n255\n", image.nx, image.ny);

@@ -25,6 +25,8 @@ pub const RTG_FLAG_TRACE_KERNEL: u32 = 2;
 pub const RTG_FLAG_PARTIAL: u32 = 4;
 /// The framebuffer holds the running sum of samples `[0, sample_begin)`: render `[sample_begin, ns)` only.
 pub const RTG_FLAG_RESUME: u32 = 8;
+/// The framebuffer has a second plane of `nx * ny * 3` floats: the running sum of the squared sample colours (see the header).
+pub const RTG_FLAG_SUM_SQUARES: u32 = 16;
 
 #[repr(C)]
 pub struct rtg_builder {

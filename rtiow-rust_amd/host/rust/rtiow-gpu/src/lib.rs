@@ -248,6 +248,19 @@ impl GpuScene {
         Ok(Image { nx, ny, rgb })
     }
 
+    /// Not in the reference: par_cast with `RTG_FLAG_SUM_SQUARES`.  Returns the image exactly as `par_cast` does and, in the
+    /// same layout, the running sum of the squared sample colours of every pixel and channel (the input of a per-pixel
+    /// standard error, see `standard_error`).
+    pub fn par_cast_squares(&mut self, nx: usize, ny: usize, ns: usize, camera: &Camera, options: &CastOptions) -> Result<(Image, Vec<f32>)> {
+        let n = nx * ny * 3;
+        let mut planes = vec![0f32; 2 * n]; // plane 0: the image, plane 1: the sum of squares
+        let mut p = params(nx, ny, ns, options);
+        p.flags = sys::RTG_FLAG_SUM_SQUARES;
+        check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, planes.as_mut_ptr(), ptr::null_mut()) })?;
+        let sum_sq = planes.split_off(n);
+        Ok((Image { nx, ny, rgb: planes }, sum_sq))
+    }
+
     /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).
     /// After each slice `on_preview(n_done, &preview)` gets the frame resolved at `n_done` samples -- bit-identical to
     /// `par_cast(nx, ny, n_done, ..)` -- and returns `false` to stop early (time budget, cancel).  The preview at
@@ -277,6 +290,16 @@ impl GpuScene {
         }
         Ok(done)
     }
+}
+
+/// Standard error of a pixel channel's mean over `n` samples from its mean and its sum of squared samples
+/// (`GpuScene::par_cast_squares`), in f64: s2 = max(0, (sum_sq - n m^2) / (n - 1)), se = sqrt(s2 / n); infinite for n = 1.
+pub fn standard_error(mean: f32, sum_sq: f32, n: usize) -> f64 {
+    if n < 2 {
+        return f64::INFINITY;
+    }
+    let (m, q, nf) = (mean as f64, sum_sq as f64, n as f64);
+    (((q - nf * m * m) / (nf - 1.0)).max(0.0) / nf).sqrt()
 }
 
 /// Implemented by the reference's `World` types (lib.rs:23-55): `[Box<dyn Object>]` flattens each object in order,
