@@ -105,10 +105,35 @@ typedef struct rtg_params {
  *   - The lean ray-pool kernel then always parks every sample colour in its scratch for the fold, one sample per work item:
  *     scene option "chunks" is overridden for the call.  rtg_stats and its counters are those of the call without the flag. */
 
+#define RTG_FLAG_SAMPLE_COUNTS 32u /* out ends with a count plane: every pixel's own sample count n_p (below) */
+
+/* Per-pixel sample counts (adaptive sampling).  With RTG_FLAG_SAMPLE_COUNTS `out` ends with a count plane of nx * ny uint32_t
+ * words in pixel order (row 0 = top): it starts right after the float planes, at word 3 * nx * ny without
+ * RTG_FLAG_SUM_SQUARES and at word 6 * nx * ny with it.  Its value n_p is pixel p's target count; let e_p = min(n_p, ns).  The
+ * library only reads the count plane, never writes it.
+ *   - Precondition: the running sum of p holds samples [0, min(e_p, sample_begin)) (sample_begin = 0 without RTG_FLAG_RESUME).
+ *   - The call renders samples [sample_begin, e_p) of p and continues the left fold in order (both planes under
+ *     RTG_FLAG_SUM_SQUARES).  Pixels with e_p <= sample_begin get no samples.
+ *   - Without RTG_FLAG_PARTIAL the call finishes the frame: every owned pixel with e_p > 0 ends as its sum divided by e_p,
+ *     including pixels this call rendered nothing for.  The resolve-only call (sample_begin == ns) divides every pixel by its
+ *     own e_p.  Plane 1 is never divided.
+ *   - Pixels with n_p == 0, and pixels of other ranks / tiles, are left untouched in every plane.
+ *   - Parity: a pixel whose sum holds e_p samples resolves bit for bit to par_cast(ns = e_p) at that pixel, and its plane 1 is
+ *     bit for bit the RTG_FLAG_SUM_SQUARES call's.  With n_p == ns everywhere the call is bit-identical to the same call
+ *     without the flag, in both planes.
+ *   - rtg_stats.samples is the number of (pixel, sample) pairs rendered: the sum over owned pixels of max(0, e_p -
+ *     sample_begin); every counter is the sum over exactly those pairs, and kernel_ms covers the call's kernels.  (Scene
+ *     option bvh4 is not honoured by a counts call: it takes the binary walk, whose counters differ from the 4-wide walk's.)
+ *   - rtg_par_cast and rtg_par_cast_device honour the flag.  rtg_par_cast_device synchronises `hip_stream` once during the
+ *     call, to read back how many pixels are active (the ray-pool kernels run over a compacted list of them).
+ *     rtg_par_cast_multi returns RTG_ERR_UNSUPPORTED and writes and enqueues nothing; rtg_debug_samples returns
+ *     RTG_ERR_INVALID. */
+
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */
-  uint64_t samples;     /* pixels rendered by this call x its samples (ns - sample_begin)     */
+  uint64_t samples;     /* pixels rendered by this call x its samples (ns - sample_begin);
+                           RTG_FLAG_SAMPLE_COUNTS: the (pixel, sample) pairs it rendered       */
   uint64_t aabb_tests;  /* Aabb::hit calls        (aabb.rs:16)                                 */
   uint64_t prim_tests;  /* Sphere/Rect::hit calls (object.rs:84,185)                           */
   uint64_t shaded_hits; /* hit_top() == Some      (lib.rs:73)                                  */

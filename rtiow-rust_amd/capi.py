@@ -23,6 +23,7 @@ FLAG_TRACE_KERNEL = 2
 FLAG_PARTIAL = 4   # leave the unnormalised running sum of the samples in the framebuffer
 FLAG_RESUME = 8    # the framebuffer holds the running sum of samples [0, sample_begin): render [sample_begin, ns)
 FLAG_SUM_SQUARES = 16   # the framebuffer has a second plane: the running sum of the squared sample colours
+FLAG_SAMPLE_COUNTS = 32  # the framebuffer ends with a count plane: every pixel's own sample count (uint32)
 
 
 class Camera(C.Structure):
@@ -50,10 +51,12 @@ class Stats(C.Structure):
 
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
-                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False):
+                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False):
     """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
-    RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane."""
+    RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
+    the count plane at the framebuffer's end."""
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
+    flags |= FLAG_SAMPLE_COUNTS if counts else 0
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.nx, p.ny, p.ns = nx, ny, ns
@@ -91,6 +94,45 @@ def _squares_supported(be):
     prefix ignores flags it does not know and would write one plane where the caller expects two."""
     if be.prefix != "rtg_":
         raise ValueError("squares=True: %s (prefix %s) does not implement RTG_FLAG_SUM_SQUARES" % (be.path, be.prefix))
+
+
+def _counts_supported(be):
+    """RTG_FLAG_SAMPLE_COUNTS is the HIP library's (prefix rtg_), like RTG_FLAG_SUM_SQUARES: another library would ignore the
+    count plane and render every pixel to ns."""
+    if be.prefix != "rtg_":
+        raise ValueError("counts=: %s (prefix %s) does not implement RTG_FLAG_SAMPLE_COUNTS" % (be.path, be.prefix))
+
+
+class CountsFrame:
+    """One contiguous host framebuffer for RTG_FLAG_SAMPLE_COUNTS: the float planes ([ny, nx, 3], or [2, ny, nx, 3] with
+    squares) followed by the count plane (uint32 [ny, nx]), as include/rtiow_gpu.h lays them out.  `planes` and `counts` are
+    views of `buf`; passing them as par_cast(out=frame.planes, counts=frame.counts) renders in place, without copies."""
+
+    def __init__(self, nx, ny, squares=False):
+        n_f = (2 if squares else 1) * ny * nx * 3
+        self.buf = np.zeros(n_f + ny * nx, dtype=np.float32)
+        self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
+        self.counts = self.buf[n_f:].view(np.uint32).reshape(ny, nx)
+
+
+def counts_frame(nx, ny, squares=False):
+    """A zeroed CountsFrame (float planes + count plane in one buffer)."""
+    return CountsFrame(nx, ny, squares)
+
+
+def _counts_call(out, counts, nx, ny, squares):
+    """(buffer to render into, float planes view): `out` / `counts` themselves when the count plane already follows the
+    float planes in memory (a CountsFrame), else a staging CountsFrame holding copies of both."""
+    counts = np.asarray(counts)
+    if counts.shape != (ny, nx):
+        raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+    if (out.dtype == np.float32 and out.flags.c_contiguous and counts.dtype == np.uint32 and counts.flags.c_contiguous
+            and out.ctypes.data + out.nbytes == counts.ctypes.data):
+        return out, None
+    f = CountsFrame(nx, ny, squares)
+    f.planes[...] = out
+    f.counts[...] = counts
+    return f.planes, f
 
 
 def _host_frame(out, nx, ny, kw):
@@ -443,35 +485,57 @@ class Scene:
     def _par_cast_args(self, args, threads):
         return args
 
-    def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, **kw):
+    def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, counts=None, counters=None,
+                 **kw):
         """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
         One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
         continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h).
         squares=True (RTG_FLAG_SUM_SQUARES): float32 [2, ny, nx, 3] instead -- [0] as without the flag, [1] the running sum
-        of the squared sample colours; `out`, when given, must have that shape."""
+        of the squared sample colours; `out`, when given, must have that shape.
+        counts= (RTG_FLAG_SAMPLE_COUNTS): uint32 [ny, nx], every pixel's own sample count n_p -- the call renders samples
+        [sample_begin, min(n_p, ns)) of each pixel; pixels with n_p = 0 are left as `out` holds them.  `out` and `counts` of
+        one CountsFrame are rendered in place; anything else goes through a staging copy.
+        stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
         if kw.get("squares"):
             _squares_supported(self.be)
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
+        if counts is not None:
+            _counts_supported(self.be)
+        if counters is None:
+            counters = stats
+        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, counts=counts is not None,
+                        **kw)
         out = _host_frame(out, nx, ny, kw)
+        dst, staging = (out, None) if counts is None else _counts_call(out, counts, nx, ny, kw.get("squares"))
         st = Stats()
         st.struct_size = C.sizeof(Stats)
-        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), out.ctypes.data_as(c_f32p), C.byref(st)],
+        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), dst.ctypes.data_as(c_f32p), C.byref(st)],
                                    threads)
         self.be.check(self.be._par_cast(*args))
+        if staging is not None:
+            out[...] = staging.planes
         return (out, st.as_dict()) if stats else out
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None):
+                        resume=None, squares=None, counts=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
-        With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats."""
+        With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
+        counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
+        (copied device to device) -- written to the count plane behind the float planes of `d_out_ptr` on `stream` before the
+        call; True: the flag alone, the caller has filled the count plane.  `d_out_ptr` then holds nx * ny more words."""
         if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
             _squares_supported(self.be)
-        if sample_begin is not None or partial is not None or resume is not None or squares is not None:
+        if counts is not None and counts is not False:
+            _counts_supported(self.be)
+        if counts is not None and counts is not True and counts is not False:
+            sq = squares if squares is not None else bool(params.flags & FLAG_SUM_SQUARES)
+            self._upload_counts(params.nx, params.ny, sq, counts, d_out_ptr, stream)
+            counts = True
+        if sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None:
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
-            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES)):
+            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS)):
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
@@ -480,6 +544,70 @@ class Scene:
         self.be.check(self.be._par_cast_device(self.h, C.byref(camera), C.byref(params), d_out_ptr, stream,
                                                C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+    def _upload_counts(self, nx, ny, squares, counts, d_out_ptr, stream):
+        """Copy a uint32 [ny, nx] count array into the count plane of a device frame, on `stream`."""
+        hip = _hip_runtime()
+        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        dst = C.c_void_p(_device_ptr(d_out_ptr) + (2 if squares else 1) * nx * ny * 3 * 4)
+        if hasattr(counts, "data_ptr") and getattr(counts, "is_cuda", False):
+            if tuple(counts.shape) != (ny, nx) or counts.element_size() != 4 or not counts.is_contiguous():
+                raise ValueError("counts= must be a contiguous 4-byte [ny, nx] tensor")
+            rc = hip.hipMemcpyAsync(dst, C.c_void_p(counts.data_ptr()), nx * ny * 4, 3, hs)   # 3 = hipMemcpyDeviceToDevice
+        else:
+            host = np.ascontiguousarray(counts, dtype=np.uint32)
+            if host.shape != (ny, nx):
+                raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+            rc = hip.hipMemcpyAsync(dst, C.c_void_p(host.ctypes.data), nx * ny * 4, 1, hs)   # 1 = hipMemcpyHostToDevice
+            if rc == 0:
+                rc = hip.hipStreamSynchronize(hs)   # (the host array may go away when this call returns)
+        if rc != 0:
+            raise RtError(ERR_DEVICE, "hipMemcpyAsync(count plane) failed: %d" % rc)
+
+    def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
+                 stats=None, **kw):
+        """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS), host frames.  Every slice renders `step` more
+        samples of the pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the
+        slice that ends at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest
+        per-channel standard error <= target_se): its count n_p becomes k and it gets no more samples.
+        Yields (counts, preview, stderr) after each slice: counts (uint32 [ny, nx]) the samples every pixel holds, preview
+        (float32 [ny, nx, 3]) the frame resolved per pixel -- preview[p] is bit for bit par_cast(ns = counts[p])[p] -- and
+        stderr (float64 [ny, nx, 3]) noise.standard_error_counts of every pixel.  Stops when no pixel is active, at ns, or
+        after the first slice that ends past budget_s seconds.
+        out: a CountsFrame(nx, ny, squares=True) to hold the running sums and counts (default: a new one).  stats: a list to
+        which every slice's rtg_stats (no counters) is appended.  **kw: tiling / max_bounces / t_near."""
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        _squares_supported(self.be)
+        _counts_supported(self.be)
+        f = CountsFrame(nx, ny, squares=True) if out is None else out
+        if f.planes.shape != (2, ny, nx, 3):
+            raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
+        f.counts[...] = ns
+        active = np.ones((ny, nx), dtype=bool)
+        t0 = time.perf_counter()
+        done = 0
+        while done < ns:
+            end = min(ns, done + step)
+            _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True,
+                                  partial=True, squares=True, stats=True, counters=False, **kw)
+            if stats is not None:
+                stats.append(st)
+            done = end
+            held = np.minimum(f.counts, done).astype(np.uint32)
+            se = noise.standard_error_counts(f.planes[0], f.planes[1], held)
+            retire = noise.retire(active, done, se, min_samples, target_se)
+            f.counts[retire] = done
+            active &= ~retire
+            pv = CountsFrame(nx, ny)   # resolve a copy: the running sums go on
+            pv.planes[...] = f.planes[0]
+            pv.counts[...] = held
+            self.par_cast(camera, nx, ny, done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
+            yield held, pv.planes, se
+            if not active.any():
+                return
+            if budget_s is not None and time.perf_counter() - t0 >= budget_s:
+                return
 
     def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None,
                     squares=False, target_rmse=None, **kw):

@@ -385,6 +385,164 @@ __global__ void resolve_sum_kernel(DevParams P, PixMap pm, uint32_t pix_work, fl
   o[0] = col.x, o[1] = col.y, o[2] = col.z;
 }
 
+// ---- per-pixel sample counts (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS) ------------------------------------------------
+// A counts call renders, per owned pixel p, the samples [sample_begin, e_p) with e_p = min(n_p, ns), n_p read from the count
+// plane.  The pool kernels then run over a LIST of the active pixels (e_p > sample_begin) instead of all of this rank's work
+// items: the list holds their work indices (work_to_pixel order, so surviving 8x8 blocks stay together), padded with LIST_NONE
+// to whole 256-item reservations, and `inv` maps a work index back to its list position (the pixel_to_work sites).  A work
+// item -- one sample of one list position -- whose sample is >= e_p is skipped where the pixel is fetched.  The list
+// description lives in device memory right behind the launch constants (list_consts), written once per call.
+constexpr uint32_t LIST_NONE = 0xffffffffu;
+struct ListConsts {
+  const uint32_t* list;    // list position -> work index of this rank, LIST_NONE for the padding
+  const uint32_t* inv;     // work index -> list position (pixels that are not in the list: LIST_NONE)
+  const uint32_t* counts;  // the count plane: n_p, nx * ny words, row-major, row 0 = top
+};
+RT_DEV const ListConsts* list_consts(const LaunchConsts* lc) { return reinterpret_cast<const ListConsts*>(lc + 1); }
+__global__ void write_list_consts(ListConsts* dst, ListConsts v) { *dst = v; }
+
+// The pool kernels' two work-item maps in a list launch (template flag LIST; without it the kernels evaluate today's
+// work_to_pixel / pixel_to_work expressions, written out at each site).
+// list position w (of sample `first`) -> pixel, false when the item is skipped: padding, or first >= e_p
+RT_DEV bool list_item_to_pixel(const LaunchConsts* lc, const DevParams& P, uint32_t w, uint32_t first, uint32_t& x, uint32_t& row) {
+  const ListConsts L = load_const(list_consts(lc));
+  const uint32_t v = L.list[w];
+  return v != LIST_NONE && work_to_pixel(P, load_const(&lc->pm), v, x, row) && first < P.ns && first < L.counts[(size_t)row * P.nx + x];
+}
+// pixel -> its list position (the index of its scratch rows and cost block)
+RT_DEV uint32_t list_item_of_pixel(const LaunchConsts* lc, const DevParams& P, uint32_t x, uint32_t row) {
+  return load_const(&list_consts(lc)->inv)[pixel_to_work(P, load_const(&lc->pm), x, row)];
+}
+
+// The ordered fold of a list launch: list position w folds samples [cm.s_begin, min(P.ns, e_p)) of its pixel into the running
+// sum (and, SQ, the running sum of squares), as fold_samples_kernel / fold_samples_sq_kernel do; it never divides (the
+// resolve below does, per pixel).  Positions whose pixel has no sample in this pass leave the framebuffer alone.
+template <bool SQ>
+__global__ void fold_samples_list_kernel(DevParams P, ChunkMode cm, PixMap pm, float* __restrict__ out, ListConsts L) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= cm.pix_work) return;
+  const uint32_t v = L.list[w];
+  uint32_t x, row;
+  if (v == LIST_NONE || !work_to_pixel(P, pm, v, x, row)) return;
+  const size_t p = (size_t)row * P.nx + x;
+  const uint32_t n = L.counts[p], end = n < P.ns ? n : P.ns;
+  if (end <= cm.s_begin) return;
+  float* o = out + 3ull * p;
+  float* q = o + 3ull * ((size_t)P.nx * P.ny);
+  V3 col = mk(0.f, 0.f, 0.f), sq = mk(0.f, 0.f, 0.f);
+  if (cm.s_begin != 0u) {
+    col = mk(o[0], o[1], o[2]);
+    if (SQ) sq = mk(q[0], q[1], q[2]);
+  }
+  const float* c = cm.scratch + 3ull * ((size_t)cm.s_begin * cm.pix_work + w);
+  const size_t step = 3ull * cm.pix_work;
+  for (uint32_t s = cm.s_begin; s < end; s++, c += step) {
+    const V3 cv = mk(RT_SCRATCH_LOAD(c), RT_SCRATCH_LOAD(c + 1), RT_SCRATCH_LOAD(c + 2));
+    col = vadd(col, cv);
+    if (SQ) sq = vadd(sq, vmul(cv, cv));
+  }
+  o[0] = col.x, o[1] = col.y, o[2] = col.z;
+  if (SQ) q[0] = sq.x, q[1] = sq.y, q[2] = sq.z;
+}
+
+// The end of a counts call without RTG_FLAG_PARTIAL: every owned pixel with e_p > 0 becomes its running sum divided by e_p
+// (lib.rs:374 with ns = e_p); pixels with n_p = 0 stay as they are.  Work items as in resolve_sum_kernel.
+__global__ void resolve_counts_kernel(DevParams P, PixMap pm, uint32_t pix_work, float* __restrict__ out, const uint32_t* __restrict__ counts) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= pix_work) return;
+  uint32_t x, row;
+  if (!work_to_pixel(P, pm, w, x, row)) return;
+  const size_t p = (size_t)row * P.nx + x;
+  const uint32_t n = counts[p], e = n < P.ns ? n : P.ns;
+  if (e == 0u) return;
+  float* o = out + 3ull * p;
+  const V3 col = sdiv(mk(o[0], o[1], o[2]), (float)e);
+  o[0] = col.x, o[1] = col.y, o[2] = col.z;
+}
+
+// Compaction of a counts call, three kernels over this rank's work items in work_to_pixel order (blocks of 256 items):
+// count the active pixels and their samples per block, scan the block counts (one workgroup), write the list and `inv`.
+struct CompactResult {
+  uint32_t active, padded;    // active pixels; the list's length, rounded up to whole 256-item reservations
+  unsigned long long samples; // (pixel, sample) pairs the call renders: rtg_stats.samples
+};
+// samples the call renders of work item w: max(0, e_p - s_begin), 0 outside the image
+RT_DEV uint32_t call_samples(const DevParams& P, const PixMap& pm, uint32_t w, uint32_t pix_work, const uint32_t* counts, uint32_t s_begin) {
+  uint32_t x, row;
+  if (w >= pix_work || !work_to_pixel(P, pm, w, x, row)) return 0u;
+  const uint32_t n = counts[(size_t)row * P.nx + x], e = n < P.ns ? n : P.ns;
+  return e > s_begin ? e - s_begin : 0u;
+}
+__global__ __launch_bounds__(256) void compact_count_kernel(DevParams P, PixMap pm, uint32_t pix_work, const uint32_t* __restrict__ counts,
+                                                            uint32_t s_begin, uint32_t* __restrict__ blk_active,
+                                                            unsigned long long* __restrict__ blk_samples) {
+  __shared__ uint32_t s_act[4];
+  __shared__ unsigned long long s_smp[4];
+  const uint32_t k = call_samples(P, pm, blockIdx.x * 256u + threadIdx.x, pix_work, counts, s_begin);
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  unsigned long long v = k;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  const uint32_t a = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(k != 0u));
+  if (lane == 0u) s_act[wave] = a, s_smp[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    blk_active[blockIdx.x] = s_act[0] + s_act[1] + s_act[2] + s_act[3];
+    blk_samples[blockIdx.x] = s_smp[0] + s_smp[1] + s_smp[2] + s_smp[3];
+  }
+}
+// one workgroup of 1024: exclusive scan of the block counts, the totals, and the list's padding
+__global__ __launch_bounds__(1024) void compact_scan_kernel(uint32_t n_blocks, const uint32_t* __restrict__ blk_active,
+                                                            const unsigned long long* __restrict__ blk_samples, uint32_t* __restrict__ blk_offset,
+                                                            uint32_t* __restrict__ list, CompactResult* __restrict__ res) {
+  __shared__ uint32_t s_wave[16];
+  __shared__ unsigned long long s_smp[16];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
+  uint32_t carry = 0;
+  unsigned long long smp = 0;
+  for (uint32_t base = 0; base < n_blocks; base += blockDim.x) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t a = i < n_blocks ? blk_active[i] : 0u;
+    if (i < n_blocks) smp += blk_samples[i];
+    uint32_t incl = a;
+    for (int k = 1; k < 64; k <<= 1) {
+      const uint32_t t = (uint32_t)__shfl_up((int)incl, k, 64);
+      if ((int)lane >= k) incl += t;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t k = 0; k < n_waves; k++) before += k < wave ? s_wave[k] : 0u, total += s_wave[k];
+    if (i < n_blocks) blk_offset[i] = carry + before + incl - a;
+    carry += total;
+    __syncthreads();
+  }
+  for (int off = 32; off > 0; off >>= 1) smp += __shfl_xor(smp, off, 64);
+  if (lane == 0u) s_smp[wave] = smp;
+  __syncthreads();
+  const uint32_t padded = (carry + 255u) & ~255u;
+  for (uint32_t i = carry + threadIdx.x; i < padded; i += blockDim.x) list[i] = LIST_NONE;
+  if (threadIdx.x == 0u) {
+    unsigned long long t = 0;
+    for (uint32_t k = 0; k < n_waves; k++) t += s_smp[k];
+    res->active = carry, res->padded = padded, res->samples = t;
+  }
+}
+__global__ __launch_bounds__(256) void compact_write_kernel(DevParams P, PixMap pm, uint32_t pix_work, const uint32_t* __restrict__ counts,
+                                                            uint32_t s_begin, const uint32_t* __restrict__ blk_offset,
+                                                            uint32_t* __restrict__ list, uint32_t* __restrict__ inv) {
+  __shared__ uint32_t s_act[4];
+  const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+  const bool on = call_samples(P, pm, w, pix_work, counts, s_begin) != 0u;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint64_t m = __builtin_amdgcn_ballot_w64(on);
+  if (lane == 0u) s_act[wave] = (uint32_t)__builtin_popcountll(m);
+  __syncthreads();
+  uint32_t pos = blk_offset[blockIdx.x] + lane_rank(m);
+  for (uint32_t k = 0; k < wave; k++) pos += s_act[k];
+  if (w < pix_work) inv[w] = on ? pos : LIST_NONE;
+  if (on) list[pos] = w;
+}
+
 struct PoolTuning {
   uint32_t refill_min;   // idle lanes before the wave services (finish / shade / refill)
   uint32_t sphere_min;   // parked lanes before a sphere pass
@@ -524,7 +682,7 @@ RT_DEV uint4 fetch_hi_global(const DevScene& sc, uint32_t idx) {  // pc-scaled s
 // from the winning SPHERE record (the flattener copies the material kind into its flag word).
 // HOT_LDS: the hot slot fields -- the ray (o, d) and (best, best_pc), see pool_lds_bytes -- live in LDS when the
 // program leaves room; the cold fields stay in the global SoA region.
-template <bool USE_LDS, bool COUNT, bool HOT_LDS, bool WIDE = false>
+template <bool USE_LDS, bool COUNT, bool HOT_LDS, bool WIDE = false, bool LIST = false>
 __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void render_lean_pool(
     DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out, uint32_t total_work, uint32_t* __restrict__ queue,
     unsigned long long* counters, PoolTuning tune, uint32_t* __restrict__ g_slots) {
@@ -885,7 +1043,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
           if (COUNT) total_draws += rng.draws;
           if (COUNT && tr_slot) tr_slot[j] += rng.draws;
           lpt_on = !deferred && s < cm.lpt_samples && bounces == cm.lpt_deep;  // phase 1 of the cost-ordered queue: a deep scatter event
-          if (lpt_on) lpt_blk = pixel_to_work(P, load_const(&lc->pm), xy & 0xffffu, xy >> 16) >> 8;
+          if (lpt_on) lpt_blk = (LIST ? list_item_of_pixel(lc, P, xy & 0xffffu, xy >> 16) : pixel_to_work(P, load_const(&lc->pm), xy & 0xffffu, xy >> 16)) >> 8;
           if (deferred) {
             bump_bpc_tries(j);
           } else if (scattered) {
@@ -953,10 +1111,10 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
               }
             }
             if (cm.scratch) {  // chunk mode: park the sample colour, folded in order afterwards
-              float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + pixel_to_work(P, load_const(&lc->pm), x, row));
+              float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)));
               RT_SCRATCH_STORE(sp, result);
               if (COUNT && tr_out) {
-                uint32_t* tp = tr_out + 4ull * ((size_t)s * cm.pix_work + pixel_to_work(P, load_const(&lc->pm), x, row));
+                uint32_t* tp = tr_out + 4ull * ((size_t)s * cm.pix_work + (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)));
                 tp[0] = SLOT_U(PF_BOUNCES, j), tp[1] = tr_slot[j], tp[2] = tr_slot[POOL + j], tp[3] = tr_slot[2u * POOL + j];
               }
             } else {
@@ -1004,7 +1162,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
                 w += w_delta;
                 first = cm.s_begin + w_chunk * cm.chunk;
               }
-              if (work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns) {
+              if ((LIST ? list_item_to_pixel(lc, P, w, first, x, row) : work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns)) {
                 s = first;
                 col = mk(0.f, 0.f, 0.f);
                 st = ST_GEN;

@@ -86,7 +86,7 @@ RT_DEV uint4 p2_record(uint32_t lds_addr) {  // 16 bytes at a 16-byte aligned ab
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-template <bool TEX, bool COUNT>
+template <bool TEX, bool COUNT, bool LIST = false>
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_pool2(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                          uint32_t total_work, uint32_t* __restrict__ queue,
                                                          unsigned long long* counters, Pool2Tuning tune,
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             if (COUNT && tr_slot) tr_slot[P2POOL + id] += h_aabb, tr_slot[2u * P2POOL + id] += h_prim;
           }
           if (ended) {  // both early returns of color() yield accum (lib.rs:90,94)
-            const uint32_t w = pixel_to_work(P, load_const(&lc->pm), x, row);
+            const uint32_t w = LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row);
             float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + w);
             RT_SCRATCH_STORE(sp, accum);
             if (COUNT && tr_out) {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             SL_ST1(id, PS_SAMPLE, s);
           }
         }
-        if (cm.lpt_samples) lpt_count(cm, lpt_on, lpt_on ? pixel_to_work(P, load_const(&lc->pm), x, row) >> 8 : 0u);
+        if (cm.lpt_samples) lpt_count(cm, lpt_on, lpt_on ? (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)) >> 8 : 0u);
         const uint64_t m_live = __builtin_amdgcn_ballot_w64(live), m_end = __builtin_amdgcn_ballot_w64(ended), m_def = __builtin_amdgcn_ballot_w64(deferred);
         if (live) te[t_count + lane_rank(m_live)] = (uint16_t)id;
         if (ended) te[P2POOL - 1u - (e_count + lane_rank(m_end))] = (uint16_t)(id | ((s == P.ns || s % cm.chunk == 0u) ? E_ITEM : E_NEXT));
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             x = xy & 0xffffu, row = xy >> 16;
             st = ST_GEN;
             if ((ent & E_NEXT) == 0u) {  // E_MISS: the path's colour is black, accum is discarded (lib.rs:100)
-              const uint32_t w = pixel_to_work(P, load_const(&lc->pm), x, row);
+              const uint32_t w = LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row);
               float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + w);
               RT_SCRATCH_STORE(sp, mk(0.f, 0.f, 0.f));
               if (COUNT && tr_out) {
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             if (r < avail) {
               const uint32_t w = w_next + r + w_delta;
               const uint32_t first = cm.s_begin + w_chunk * cm.chunk;
-              if (work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns) {
+              if ((LIST ? list_item_to_pixel(lc, P, w, first, x, row) : work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns)) {
                 s = first;
                 st = ST_GEN;
               }

@@ -193,7 +193,7 @@ RT_DEV void full_push_finished(const QueueRsrc qr, uint32_t& s_count, uint32_t& 
 // and resume the main walk behind the stream.  The boundary's BOX records run in the box loop and its primitives in the
 // slow passes like any others, so a complex boundary is scheduled as well as the rest of the scene.  A template variant:
 // 5 more VGPRs, paid only by scenes that need it.
-template <int PROG, bool TEX, bool COUNT, bool GENB = false>
+template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false>
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_pool(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -539,16 +539,16 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
           if (COUNT) trd += rng.draws;
           live = !ended && !deferred;
           if (ended) {
-            float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + pixel_to_work(P, load_const(&lc->pm), x, row));
+            float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)));
             RT_SCRATCH_STORE(sp, result);
             if (COUNT && tr_out) {
-              uint32_t* tp = tr_out + 4ull * ((size_t)s * cm.pix_work + pixel_to_work(P, load_const(&lc->pm), x, row));
+              uint32_t* tp = tr_out + 4ull * ((size_t)s * cm.pix_work + (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)));
               tp[0] = bounces, tp[1] = trd, tp[2] = tra, tp[3] = trp;
             }
             s++;
           }
         }
-        if (cm.lpt_samples) lpt_count(cm, lpt_on, lpt_on ? pixel_to_work(P, load_const(&lc->pm), x, row) >> 8 : 0u);
+        if (cm.lpt_samples) lpt_count(cm, lpt_on, lpt_on ? (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)) >> 8 : 0u);
         const uint64_t m_live = __builtin_amdgcn_ballot_w64(live), m_end = __builtin_amdgcn_ballot_w64(ended);
         RT_TL_SHADE(take, m_live);
         if (live) {  // push onto T
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
               uint32_t w = w_next + r;
               w += w_delta;
               const uint32_t first = cm.s_begin + w_chunk * cm.chunk;
-              if (work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns) {
+              if ((LIST ? list_item_to_pixel(lc, P, w, first, x, row) : work_to_pixel(P, load_const(&lc->pm), w, x, row) && first < P.ns)) {
                 s = first;
                 st = ST_GEN;
               }

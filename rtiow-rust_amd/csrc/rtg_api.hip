@@ -77,6 +77,11 @@ struct LaunchCtx {
   LptQueue lpt_desc{};          // descriptor of the last launch (RTG_VERBOSE histogram)
   KernelKind last_kernel = KernelKind::baseline;  // what launch_render chose last
   uint32_t last_pix_work = 0;   // pixel work items of that launch (tiles x tile area), 0 when it kept no per-sample scratch
+  uint32_t* d_list = nullptr;   // RTG_FLAG_SAMPLE_COUNTS: the active-pixel list and its inverse (rt_pool.h ListConsts), 2 x the rank's work items
+  size_t list_bytes = 0;
+  uint32_t* d_compact = nullptr;  // ... the compaction's per-block counts, offsets and samples, and its CompactResult
+  size_t compact_bytes = 0;
+  unsigned long long counts_samples = 0;  // ... rtg_stats.samples of the last counts call
 };
 
 struct rtg_scene {
@@ -145,8 +150,11 @@ static void ctx_free_buffers(LaunchCtx* c) {
   if (c->d_slots) (void)hipFree(c->d_slots);
   if (c->d_stack) (void)hipFree(c->d_stack);
   if (c->d_lpt) (void)hipFree(c->d_lpt);
+  if (c->d_list) (void)hipFree(c->d_list);
+  if (c->d_compact) (void)hipFree(c->d_compact);
   c->d_scratch = nullptr, c->scratch_bytes = 0, c->d_slots = nullptr, c->slots_bytes = 0;
   c->d_stack = nullptr, c->stack_bytes = 0, c->d_lpt = nullptr, c->lpt_bytes = 0;
+  c->d_list = nullptr, c->list_bytes = 0, c->d_compact = nullptr, c->compact_bytes = 0;
 }
 
 // Take the next launch context of the ring: create its small buffers on first use, wait for the frame that used it last.
@@ -155,7 +163,7 @@ static int ctx_acquire(rtg_scene* s) {
   s->next_ctx = (s->next_ctx + 1) % s->n_ctx;
   if (!c->d_counters) {
     if (hipMalloc((void**)&c->d_counters, 64 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->d_counters, 0, 64 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void**)&c->d_consts, sizeof(LaunchConsts)) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
+        hipMalloc((void**)&c->d_consts, sizeof(LaunchConsts) + sizeof(ListConsts)) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess || hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess)
       return fail(RTG_ERR_DEVICE, "scene: launch-context allocation failed");
   }
@@ -181,6 +189,9 @@ struct SampleSlice {
   uint32_t begin = 0;   // first sample this call renders; the framebuffer holds the running sum of [0, begin) when it is > 0
   bool divide = true;   // false under RTG_FLAG_PARTIAL: the running sum stays in the framebuffer
   bool squares = false; // RTG_FLAG_SUM_SQUARES: the framebuffer has a second plane, the running sum of the squared colours
+  bool counts = false;  // RTG_FLAG_SAMPLE_COUNTS: the framebuffer ends with the count plane; the pool kernels run over a list
+  uint32_t list_work = 0;  // ... set by the launcher (launch_counts): the list's length, a multiple of 256
+  ListConsts list{};       // ... and where the list, its inverse and the count plane are
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -188,6 +199,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_RESUME) sl.begin = p->sample_begin;
   if (p->flags & RTG_FLAG_PARTIAL) sl.divide = false;
   if (p->flags & RTG_FLAG_SUM_SQUARES) sl.squares = true;
+  if (p->flags & RTG_FLAG_SAMPLE_COUNTS) sl.counts = true;
   return sl;
 }
 
@@ -790,7 +802,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
     }
 #endif
     stats->kernel_ms = ms;
-    stats->samples = owned_pixels(d) * (d.ns - sl.begin);
+    stats->samples = sl.counts ? s->cx->counts_samples : owned_pixels(d) * (d.ns - sl.begin);
     unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (count) HIP_TRY(hipMemcpy(h, s->cx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
     stats->aabb_tests = h[0], stats->prim_tests = h[1], stats->shaded_hits = h[2], stats->rays = h[3], stats->draws = h[4];
@@ -807,16 +819,19 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     if (rc0) return rc0;
   }
   HIP_TRY(hipSetDevice(s->device));
-  // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares)
-  size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (slice_of(params).squares ? 2 : 1);
+  const SampleSlice sl = slice_of(params);
+  // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares; RTG_FLAG_SAMPLE_COUNTS adds the count plane, which
+  // travels to the device and is never copied back)
+  size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (sl.squares ? 2 : 1);
+  const size_t in_bytes = bytes + (sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0);
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
-  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, bytes ? bytes : 16);
+  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, in_bytes ? in_bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
   float* d_out = s->d_frame;
   // pixels of other ranks stay as the caller left them; a single rank overwrites every pixel -- unless it resumes a progressive
-  // frame, whose running sums are in out_rgb
-  const bool upload = params->nranks > 1 || slice_of(params).begin != 0u;
-  if (upload) e = hipMemcpy(d_out, out_rgb, bytes, hipMemcpyHostToDevice);
+  // frame, whose running sums are in out_rgb, or renders per-pixel counts (pixels with n_p = 0 stay as they are)
+  const bool upload = params->nranks > 1 || sl.begin != 0u || sl.counts;
+  if (upload) e = hipMemcpy(d_out, out_rgb, in_bytes, hipMemcpyHostToDevice);
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();

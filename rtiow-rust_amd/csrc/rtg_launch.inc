@@ -157,7 +157,12 @@ static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, 
     e = issue(s0, dp, cm, grid, (uint32_t)total_work);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (cm.scratch) {  // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL; RTG_FLAG_SUM_SQUARES: the fold that also sums the squares)
+    if (cm.scratch && sl.counts) {  // RTG_FLAG_SAMPLE_COUNTS: the list's fold, per pixel up to e_p, never dividing (launch_counts resolves)
+      void (*fold)(DevParams, ChunkMode, PixMap, float*, ListConsts) = sl.squares ? fold_samples_list_kernel<true> : fold_samples_list_kernel<false>;
+      hipLaunchKernelGGL(fold, dim3((uint32_t)(((uint64_t)cm.pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out, sl.list);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    } else if (cm.scratch) {  // (ns_frame 0 = never divide: RTG_FLAG_PARTIAL; RTG_FLAG_SUM_SQUARES: the fold that also sums the squares)
       void (*fold)(DevParams, ChunkMode, PixMap, float*, uint32_t) = sl.squares ? fold_samples_sq_kernel : fold_samples_kernel;
       hipLaunchKernelGGL(fold, dim3((uint32_t)(((uint64_t)cm.pix_work + 255) / 256)), dim3(256), 0, stream, dp, cm, make_pixmap(dp), d_out,
                          sl.divide ? d.ns : 0u);
@@ -170,11 +175,13 @@ static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, 
 
 // Lean scenes, ray-pool kernel (rt_pool.h): one persistent 1024-thread workgroup per CU.
 // `sl`: the samples [sl.begin, d.ns) of a progressive frame's slice -- pass sizing, chunking and launch geometry follow this
-// call's samples, not the frame's.
+// call's samples, not the frame's.  A counts call (sl.counts) runs over its list of active pixels: `pix_work` is the list's
+// length, and the kernel the list variant (LIST; the 4-wide walk of option bvh4 is not instantiated for it: such a call takes
+// the binary walk and reports its counters).
 template <bool COUNT>
 static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
                               hipStream_t stream, const SampleSlice& sl) {
-  const uint64_t pix_work = rank_pix_work(d);
+  const uint64_t pix_work = sl.counts ? sl.list_work : rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   // Sample-chunk mode (see rt_pool.h).  Default: one sample per work item.  Work items are then ~100x more numerous than
@@ -186,15 +193,16 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   if (n_chunks > ns_call) n_chunks = ns_call;
   // else (ns = 1, or option chunks = 1): a slot folds its pixel's samples itself -- from +0, dividing at the end; a slice of a
   // progressive frame takes the chunk mode instead, whose fold kernel continues the running sum and divides only when asked,
-  // and so does a call that sums the squares (the fold kernel squares every sample colour: one sample per work item)
-  const bool use_scratch = n_chunks > 1 || sl.sliced() || sl.squares;
+  // and so does a call that sums the squares (the fold kernel squares every sample colour: one sample per work item), or
+  // renders per-pixel counts (the fold stops at each pixel's own count)
+  const bool use_scratch = n_chunks > 1 || sl.sliced() || sl.squares || sl.counts;
   uint32_t per_pass = d.ns, chunk = d.ns;
   if (use_scratch) {
     per_pass = samples_per_pass(s, pix_work, ns_call);
     chunk = (uint32_t)((ns_call + n_chunks - 1) / n_chunks);
     // several passes: one sample per work item; the same when the slice does not begin on a chunk boundary (the kernel ends a
     // work item where s % chunk == 0)
-    if (per_pass < ns_call || sl.begin % chunk != 0u || sl.squares) chunk = 1u;
+    if (per_pass < ns_call || sl.begin % chunk != 0u || sl.squares || sl.counts) chunk = 1u;
     hipError_t ea = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
     if (ea != hipSuccess) return ea;
   }
@@ -206,7 +214,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   const int bt = geo.bt;
   const uint32_t waves = (uint32_t)bt / 64;
   const size_t lds_limit = 160 * 1024;
-  const bool wide = s->bvh4 && s->wide_bytes != 0;
+  const bool wide = s->bvh4 && s->wide_bytes != 0 && !sl.counts;
   const uint32_t image = wide ? s->wide_bytes : s->dev.lds_image_bytes;
   DevScene dev = s->dev;
   if (wide) dev.lds_off = (const uint32_t*)s->buffers[7], dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
@@ -218,7 +226,10 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   if (s->verbose && s->ray_lds && !ray_lds && use_lds && image >= (1u << 17) && pool_lds_bytes(image, s->n_mat, waves, use_lds, true) <= lds_limit)
     fprintf(stderr, "[rtg] pool: the LDS image is %u B (>= 128 KB): the slots' hot fields stay in global memory although they would fit LDS (their 16-bit best_pc holds image offsets / 8 < 2^14)\n", image);
   void (*kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, uint32_t*);
-  if (wide) kernel = ray_lds ? render_lean_pool<true, COUNT, true, true> : render_lean_pool<true, COUNT, false, true>;
+  if (sl.counts) {
+    if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true, false, true> : render_lean_pool<false, COUNT, true, false, true>;
+    else kernel = use_lds ? render_lean_pool<true, COUNT, false, false, true> : render_lean_pool<false, COUNT, false, false, true>;
+  } else if (wide) kernel = ray_lds ? render_lean_pool<true, COUNT, true, true> : render_lean_pool<true, COUNT, false, true>;
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
   PoolLaunch L{KernelKind::lean_pool, bt, 0, lds, geo, POOL};
@@ -355,11 +366,11 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipS
 
 // Full-feature scenes, ray-pool kernel (rt_pool_full.h) or, for list worlds without a Bvh, the lock-step kernel
 // (rt_sync_full.h): always one sample per work item + ordered fold, in as many sample passes as the scratch budget asks for.
-// (`sl`: as in launch_pool)
+// (`sl`: as in launch_pool; a counts call takes the LIST variant of whichever kernel its list's work picks)
 template <bool COUNT>
 static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
                                    hipStream_t stream, const SampleSlice& sl) {
-  const uint64_t pix_work = rank_pix_work(d);
+  const uint64_t pix_work = sl.counts ? sl.list_work : rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   const uint32_t ns_call = d.ns - sl.begin;  // samples of this call
@@ -392,7 +403,15 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   void (*kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, uint32_t*, float*,
                  uint32_t);
   const bool genb = (s->features & FEAT_BOUNDARY) != 0;  // a medium bounded by an object graph: the nested-walk variant
-  if (genb) {
+  if (sl.counts && genb) {
+    if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, true, true> : render_full_pool<0, false, COUNT, true, true>;
+    else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, true, true> : render_full_pool<1, false, COUNT, true, true>;
+    else kernel = tex ? render_full_pool<2, true, COUNT, true, true> : render_full_pool<2, false, COUNT, true, true>;
+  } else if (sl.counts) {
+    if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, false, true> : render_full_pool<0, false, COUNT, false, true>;
+    else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, false, true> : render_full_pool<1, false, COUNT, false, true>;
+    else kernel = tex ? render_full_pool<2, true, COUNT, false, true> : render_full_pool<2, false, COUNT, false, true>;
+  } else if (genb) {
     if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, true> : render_full_pool<0, false, COUNT, true>;
     else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, true> : render_full_pool<1, false, COUNT, true>;
     else kernel = tex ? render_full_pool<2, true, COUNT, true> : render_full_pool<2, false, COUNT, true>;
@@ -428,7 +447,9 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
   if (lock_step) {
     L.kind = KernelKind::lock_step;
-    if (genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true> : render_full_sync<1, false, COUNT, true>;
+    if (sl.counts && genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true, true> : render_full_sync<1, false, COUNT, true, true>;
+    else if (sl.counts) sync_kernel = tex ? render_full_sync<1, true, COUNT, false, true> : render_full_sync<1, false, COUNT, false, true>;
+    else if (genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true> : render_full_sync<1, false, COUNT, true>;
     else sync_kernel = tex ? render_full_sync<1, true, COUNT, false> : render_full_sync<1, false, COUNT, false>;
     L.lds = (size_t)window * 32;
     // the lock-step kernel keeps ONE path per lane (64 per wave, not the pool kernel's FPOOL): its grid comes from that, and
@@ -438,7 +459,8 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
     e = kernel_setup(s, (const void*)sync_kernel, bt, L.lds, &L.per_cu);
   } else if (pool2) {
     L.kind = KernelKind::pool2;
-    pool2_kernel = tex ? render_full_pool2<true, COUNT> : render_full_pool2<false, COUNT>;
+    if (sl.counts) pool2_kernel = tex ? render_full_pool2<true, COUNT, true> : render_full_pool2<false, COUNT, true>;
+    else pool2_kernel = tex ? render_full_pool2<true, COUNT> : render_full_pool2<false, COUNT>;
     L.lds = lds3;
     const uint32_t tab = s->n_prog2 * 32u + DC_WORDS * 4u;
     consts.mat_lds = mats3 ? tab + P2_TABLE_BYTES : 0u;
@@ -496,6 +518,76 @@ static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t s
   return hipGetLastError();
 }
 
+// RTG_FLAG_SAMPLE_COUNTS (include/rtiow_gpu.h): compact this rank's active pixels (e_p > sl.begin) into the list the pool
+// kernels run over (rt_pool.h compact_*), read back its length and the call's sample count -- the one synchronisation of the
+// stream a counts call makes -- render the list with the kernel the features pick (the baseline kernel walks every pixel and
+// skips the inactive ones itself), then, without RTG_FLAG_PARTIAL, divide every owned pixel with e_p > 0 by e_p.
+template <bool COUNT>
+static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
+                                const SampleSlice& sl, uint32_t geom, bool pool_ok) {
+  s->cx->counts_samples = 0;
+  const uint64_t pix_work = rank_pix_work(d);
+  if (pix_work == 0) return hipSuccess;  // this rank owns no tile
+  if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
+  SampleSlice ls = sl;
+  ls.list.counts = reinterpret_cast<const uint32_t*>(d_out + (sl.squares ? 6ull : 3ull) * d.nx * d.ny);
+  const PixMap pm = make_pixmap(d);
+  const uint32_t n_blk = (uint32_t)(pix_work / 256u);
+  hipError_t e;
+  if (sl.begin < d.ns) {
+    e = grow((void**)&s->cx->d_list, &s->cx->list_bytes, 2 * pix_work * sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    // [blk_samples: u64 x n_blk] [CompactResult] [blk_active: n_blk] [blk_offset: n_blk]
+    e = grow((void**)&s->cx->d_compact, &s->cx->compact_bytes, (size_t)n_blk * 16u + sizeof(CompactResult));
+    if (e != hipSuccess) return e;
+    unsigned long long* blk_samples = reinterpret_cast<unsigned long long*>(s->cx->d_compact);
+    CompactResult* res = reinterpret_cast<CompactResult*>(blk_samples + n_blk);
+    uint32_t* blk_active = reinterpret_cast<uint32_t*>(res + 1);
+    uint32_t* blk_offset = blk_active + n_blk;
+    uint32_t* list = s->cx->d_list;
+    uint32_t* inv = list + pix_work;
+    ls.list.list = list, ls.list.inv = inv;
+    hipLaunchKernelGGL(compact_count_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, ls.list.counts, sl.begin, blk_active, blk_samples);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, stream, n_blk, blk_active, blk_samples, blk_offset, list, res);
+    hipLaunchKernelGGL(compact_write_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, ls.list.counts, sl.begin, blk_offset, list, inv);
+    hipLaunchKernelGGL(write_list_consts, dim3(1), dim3(1), 0, stream, reinterpret_cast<ListConsts*>(s->cx->d_consts + 1), ls.list);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    CompactResult h{};
+    e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    s->cx->counts_samples = h.samples;
+    ls.list_work = h.padded;
+    if (s->verbose)
+      fprintf(stderr, "[rtg] sample counts: samples [%u, %u): %u of %llu owned pixels active (list of %u work items), %llu samples\n",
+              sl.begin, d.ns, h.active, (unsigned long long)owned_pixels(d), h.padded, h.samples);
+    if (h.active != 0u) {
+      if (geom != 0 && pool_ok) {
+        s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)
+        e = launch_full_pool<COUNT>(s, cam, d, d_out, stream, ls);
+      } else if (geom == 0 && pool_ok) {
+        s->cx->last_kernel = KernelKind::lean_pool;
+        e = launch_pool<COUNT>(s, cam, d, d_out, stream, ls);
+      } else {
+        // the baseline kernel (FEAT_DEEP graphs on the largest general walk, as the slices)
+        constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+        const dim3 grid(((d.nx + 15) / 16) * ((d.ny + 15) / 16)), block(256);
+        void (*k)(DevScene, DevCamera, DevParams, float*, unsigned long long*, uint32_t, const uint32_t*);
+        if (s->features & FEAT_DEEP) k = sl.squares ? render_counts_kernel<D, COUNT, true> : render_counts_kernel<D, COUNT, false>;
+        else if (geom == 0) k = sl.squares ? render_counts_kernel<0u, COUNT, true> : render_counts_kernel<0u, COUNT, false>;
+        else k = sl.squares ? render_counts_kernel<FEAT_ALL, COUNT, true> : render_counts_kernel<FEAT_ALL, COUNT, false>;
+        hipLaunchKernelGGL(k, grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, ls.list.counts);
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess) return e;
+    }
+  }
+  if (!sl.divide) return hipSuccess;
+  hipLaunchKernelGGL(resolve_counts_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, d_out, ls.list.counts);
+  return hipGetLastError();
+}
+
 // `sl` (rtg_api.hip SampleSlice): the samples of a progressive frame this call renders; the default is the whole frame.
 template <bool COUNT>
 static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
@@ -507,6 +599,7 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
   s->cx->last_kernel = KernelKind::baseline;
+  if (sl.counts) return launch_counts<COUNT>(s, cam, d, d_out, stream, sl, geom, pool_ok);
   if (sl.begin == d.ns) return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;  // nothing to render
   if (geom != 0 && pool_ok) {
     s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)

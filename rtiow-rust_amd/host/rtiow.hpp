@@ -17,6 +17,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <stdexcept>
@@ -320,6 +321,23 @@ inline SquaresImage par_cast_squares(size_t nx, size_t ny, size_t ns, const Came
   r.image.rgb.assign(planes.begin(), planes.begin() + nx * ny * 3);
   r.sum_sq.assign(planes.begin() + nx * ny * 3, planes.end());
   return r;
+}
+
+// Not in the reference: par_cast with RTG_FLAG_SAMPLE_COUNTS.  `counts` (nx * ny, row 0 = top) gives every pixel its own sample
+// count n_p: pixel p of the result is par_cast(nx, ny, min(n_p, ns), ...) at p, bit for bit; pixels with n_p = 0 stay black.
+inline Image par_cast_counts(size_t nx, size_t ny, size_t ns, const std::vector<uint32_t>& counts, const Camera& camera,
+                             const Scene& world, const CastOptions& opt = CastOptions()) {
+  if (counts.size() != nx * ny) throw Error(RTG_ERR_INVALID, "par_cast_counts: counts must hold nx * ny values");
+  SceneHandle s = make_scene(world, opt);
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_SAMPLE_COUNTS;
+  std::vector<float> frame(4 * nx * ny, 0.f);  // the image, then the count plane (uint32_t words)
+  std::memcpy(frame.data() + 3 * nx * ny, counts.data(), counts.size() * sizeof(uint32_t));
+  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  Image img;
+  img.nx = nx, img.ny = ny;
+  img.rgb.assign(frame.begin(), frame.begin() + 3 * nx * ny);
+  return img;
 }
 
 // Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /

@@ -27,6 +27,8 @@ pub const RTG_FLAG_PARTIAL: u32 = 4;
 pub const RTG_FLAG_RESUME: u32 = 8;
 /// The framebuffer has a second plane of `nx * ny * 3` floats: the running sum of the squared sample colours (see the header).
 pub const RTG_FLAG_SUM_SQUARES: u32 = 16;
+/// The framebuffer ends with a count plane of `nx * ny` `u32`: every pixel's own sample count (see the header).
+pub const RTG_FLAG_SAMPLE_COUNTS: u32 = 32;
 
 #[repr(C)]
 pub struct rtg_builder {

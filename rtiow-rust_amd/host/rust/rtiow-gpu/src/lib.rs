@@ -261,6 +261,25 @@ impl GpuScene {
         Ok((Image { nx, ny, rgb: planes }, sum_sq))
     }
 
+    /// Not in the reference: par_cast with `RTG_FLAG_SAMPLE_COUNTS`.  `counts` (`nx * ny`, row 0 = top) gives every pixel its
+    /// own sample count n_p: pixel p is `par_cast(nx, ny, min(n_p, ns), ..)` at p, bit for bit; pixels with n_p = 0 stay black.
+    /// (Uncompiled, like the rest of this crate.)
+    pub fn par_cast_counts(&mut self, nx: usize, ny: usize, ns: usize, counts: &[u32], camera: &Camera, options: &CastOptions) -> Result<Image> {
+        let n = nx * ny;
+        if counts.len() != n {
+            return Err(Error { code: sys::RTG_ERR_INVALID, message: "par_cast_counts: counts must hold nx * ny values".into() });
+        }
+        let mut frame = vec![0f32; 4 * n]; // the image, then the count plane (u32 words)
+        for (w, &c) in frame[3 * n..].iter_mut().zip(counts) {
+            *w = f32::from_bits(c);
+        }
+        let mut p = params(nx, ny, ns, options);
+        p.flags = sys::RTG_FLAG_SAMPLE_COUNTS;
+        check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, frame.as_mut_ptr(), ptr::null_mut()) })?;
+        frame.truncate(3 * n);
+        Ok(Image { nx, ny, rgb: frame })
+    }
+
     /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).
     /// After each slice `on_preview(n_done, &preview)` gets the frame resolved at `n_done` samples -- bit-identical to
     /// `par_cast(nx, ny, n_done, ..)` -- and returns `false` to stop early (time budget, cancel).  The preview at
