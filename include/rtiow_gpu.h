@@ -201,13 +201,16 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
 void rtg_scene_destroy(rtg_scene* s);
 /* Scheduling / measurement switches of one scene handle -- kernel generation, cost-ordered work queue, pool
  * thresholds, workgroup size (names: DESIGN.md section 4 "Knobs").  None of them changes a bit of the result.  The
- * library reads no environment variable for these.  "bvh4" = 1 (scenes that are ONE Bvh of spheres; RTG_ERR_INVALID
- * otherwise) traverses the reference's tree (bvh.rs:22-120) as 4-wide nodes: the same framebuffer, other
- * rtg_stats.aabb_tests / prim_tests than the reference's walk. */
+ * library reads no environment variable for these.  "box_chains" = 0 stages the full LDS image of a lean
+ * program (default 1: the image without box-chain followers; the same framebuffer and counters).  "bvh4" = 1 (scenes
+ * that are ONE Bvh of spheres; RTG_ERR_INVALID otherwise) traverses the reference's tree (bvh.rs:22-120) as 4-wide
+ * nodes: the same framebuffer, other rtg_stats.aabb_tests / prim_tests than the reference's walk. */
 int rtg_scene_set_option(rtg_scene* s, const char* name, int value);
-/* size of the flattened program (for DESIGN.md's byte accounting / tests) */
+/* size of the flattened program (for DESIGN.md's byte accounting / tests); n_box_followers: BOX records of a lean program
+ * that repeat the BOX before them bit for bit and are no skip target ("box chains") -- the records production
+ * launches leave out of the LDS image.  Every pointer may be NULL. */
 int rtg_scene_info(const rtg_scene* s, uint32_t* n_instructions, uint32_t* n_materials,
-                   uint32_t* n_textures, uint64_t* hbm_bytes);
+                   uint32_t* n_textures, uint64_t* hbm_bytes, uint32_t* n_box_followers);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* par_cast (lib.rs:363): out_rgb is caller-owned HOST memory, nx*ny*3 floats, row 0 = top

@@ -24,6 +24,7 @@
 // samples are folded in sample order.
 #pragma once
 #include <type_traits>
+#include <vector>
 
 #include "rt_trace.h"
 
@@ -581,15 +582,39 @@ constexpr uint32_t WIDE_NODE_BYTES = 208, WIDE_SPHERE_BYTES = 32, WIDE_NO_PARENT
 typedef __attribute__((address_space(3))) const char* lds_cptr;
 
 // byte offset of every record inside the image (host side, at scene creation); returns the image size (multiple of 16).
-// Only lean programs (BOX / SPHERE / END) have an image.
-inline uint32_t lds_image_offsets(const uint32_t* op_words, size_t n, uint32_t* off) {
+// Only lean programs (BOX / SPHERE / END) have an image.  `drop` (optional): records that take 0 bytes -- the box-chain
+// followers below; such a record shares its offset with the record behind it, and the staging loop writes no bytes for it.
+inline uint32_t lds_image_offsets(const uint32_t* op_words, size_t n, uint32_t* off, const uint8_t* drop = nullptr) {
   uint32_t at = 0;
   for (size_t i = 0; i < n; i++) {
     off[i] = at;
+    if (drop && drop[i]) continue;
     const uint32_t op = op_words[i] & 0xffu;
     at += op == OP_BOX ? LDS_BOX_BYTES : (op == OP_SPHERE ? LDS_SPHERE_BYTES : LDS_END_BYTES);
   }
   return (at + 15u) & ~15u;
+}
+
+// Box chains (option box_chains): record j of a lean program is a FOLLOWER when
+//   j is a BOX, record j - 1 is a BOX with bitwise the same six planes, and no BOX's skip pointer targets j.
+// j is then reached only through j - 1's pass edge, right after it, with the same ray, t_near and best (bvh.rs:91-94 hands
+// the left child the unchanged t range): Aabb::hit repeats the same IEEE arithmetic on the same operands and passes again.
+// The production image gives a follower 0 bytes, so j - 1's pass edge (pc + 56) lands on the record behind the chain; its
+// own skip pointer is never taken.  (Record 0, the entry, has no predecessor.)  lo = (min.x, max.x, min.y, max.y),
+// hi = (min.z, max.z, skip, flags).  Returns how many records are followers.
+inline uint32_t box_chain_followers(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size_t n, uint8_t* follower) {
+  std::vector<uint8_t> target(n, 0);
+  for (size_t i = 0; i < n; i++)
+    if ((hi[i][3] & 0xffu) == OP_BOX && hi[i][2] < n) target[hi[i][2]] = 1;
+  uint32_t count = 0;
+  for (size_t j = 0; j < n; j++) {
+    follower[j] = 0;
+    if (j == 0 || target[j] || (hi[j][3] & 0xffu) != OP_BOX || (hi[j - 1][3] & 0xffu) != OP_BOX) continue;
+    if (lo[j][0] == lo[j - 1][0] && lo[j][1] == lo[j - 1][1] && lo[j][2] == lo[j - 1][2] && lo[j][3] == lo[j - 1][3] &&
+        hi[j][0] == hi[j - 1][0] && hi[j][1] == hi[j - 1][1])
+      follower[j] = 1, count++;
+  }
+  return count;
 }
 
 // dynamic LDS bytes for a workgroup of `waves` waves: [program image | materials] [T-, S-, E-list] [slot rays] [slot best]
@@ -700,8 +725,10 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
     for (uint32_t i = threadIdx.x; i < image / 4u; i += blockDim.x) s_words[i] = sc.lds_off[i];  // (the 4-wide image itself)
   } else if (USE_LDS) {
     for (uint32_t i = threadIdx.x; i < n_prog; i += blockDim.x) {
+      const uint32_t at = sc.lds_off[i];
+      if (i + 1u < n_prog && sc.lds_off[i + 1u] == at) continue;  // a box-chain follower (0 bytes): the next record lives here
       const uint4 l = sc.lo[i], h = sc.hi[i];
-      uint32_t* r = s_words + (sc.lds_off[i] >> 2);
+      uint32_t* r = s_words + (at >> 2);
       const uint32_t op = h.w & 0xffu;
       if (op == OP_BOX) {  // lo = (min.x, max.x, min.y, max.y), hi = (min.z, max.z, skip, flags)
         r[0] = pc0 + sc.lds_off[h.z], r[1] = h.w | LDS_BOX_BIT;

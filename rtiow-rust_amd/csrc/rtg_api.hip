@@ -90,7 +90,7 @@ struct rtg_scene {
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   uint64_t bytes = 0;
-  void* buffers[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  void* buffers[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const uint32_t* d_parent = nullptr;  // buffers[8]: the wrapper around every program record (rt_pool_full.h rebuild_hit)
   hipStream_t own_stream = nullptr;  // rtg_par_cast_multi: this scene's launch stream (created on first use)
   int num_cus = 0;
@@ -110,6 +110,10 @@ struct rtg_scene {
   size_t recv_bytes = 0;
   int bvh4 = 0;                // 1: traverse the 4-wide collapse of the Bvh (same image, other counters; needs wide_bytes)
   uint32_t wide_bytes = 0;     // size of the 4-wide image in buffers[7], 0 = the scene has none
+  int box_chains = 1;          // production launches of the lean pool kernel stage the image without box-chain followers (rt_pool.h); 0 = off
+  uint32_t n_followers = 0;    // ... records that image drops (0: it is the full image, and buffers[12] is not allocated)
+  const uint32_t* d_chain_off = nullptr;  // buffers[12]: the record offsets of that image
+  uint32_t chain_bytes = 0;    // ... and its size
   int sync_full = -1;          // full-feature scenes on the pool-free lock-step kernel (rt_sync_full.h): -1 = when the program holds no BOX record, 0 / 1 = never / always
   uint32_t n_box = 0;          // BOX records of the flat program
   int lpt = 2;                 // RTG_LPT=0: natural order throughout; 1 / 2 = LptQueue::mode
@@ -560,6 +564,16 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
       return rc;
     }
     s->dev.lds_off = (const uint32_t*)s->buffers[6];
+    std::vector<uint8_t> follower(fs.hi.size());
+    s->n_followers = box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(fs.lo.data()), reinterpret_cast<const uint32_t (*)[4]>(fs.hi.data()), fs.hi.size(), follower.data());
+    if (s->n_followers) {  // the production image: every follower 0 bytes (the counting launches keep the full one)
+      s->chain_bytes = lds_image_offsets(ops.data(), ops.size(), off.data(), follower.data());
+      if ((rc = upload(&s->buffers[12], off.data(), off.size() * sizeof(uint32_t), &s->bytes))) {
+        rtg_scene_destroy(s);
+        return rc;
+      }
+      s->d_chain_off = (const uint32_t*)s->buffers[12];
+    }
     std::vector<uint32_t> wide;
     if (build_wide_image(fs.lo.data(), fs.hi.data(), fs.hi.size(), wide)) {
       if ((rc = upload(&s->buffers[7], wide.data(), wide.size() * sizeof(uint32_t), &s->bytes))) {
@@ -597,6 +611,7 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "lpt_deep") s->lpt_deep = value;
   else if (k == "lpt_shift") s->lpt_shift = std::min(6, std::max(0, value));
   else if (k == "ray_lds") s->ray_lds = value;
+  else if (k == "box_chains") s->box_chains = value;            // 0: production launches stage the full image, box-chain followers included (A/B switch)
   else if (k == "bvh4") {
     if (value && !s->wide_bytes) return fail(RTG_ERR_INVALID, "bvh4: the scene is not one Bvh of spheres (no 4-wide image)");
     if (value && pool_lds_bytes(s->wide_bytes, s->n_mat, (uint32_t)(s->pool_threads > 0 ? s->pool_threads : RT_POOL_MAX_THREADS) / 64u, true, false) > 160 * 1024)
@@ -643,12 +658,13 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
 }
 
 int rtg_scene_info(const rtg_scene* s, uint32_t* n_instructions, uint32_t* n_materials, uint32_t* n_textures,
-                   uint64_t* hbm_bytes) {
+                   uint64_t* hbm_bytes, uint32_t* n_box_followers) {
   if (!s) return fail(RTG_ERR_INVALID, "null argument");
   if (n_instructions) *n_instructions = s->n_prog;
   if (n_materials) *n_materials = s->n_mat;
   if (n_textures) *n_textures = s->n_tex;
   if (hbm_bytes) *hbm_bytes = s->bytes;
+  if (n_box_followers) *n_box_followers = s->n_followers;
   return RTG_OK;
 }
 
