@@ -110,7 +110,7 @@ typedef struct rtg_params {
 /* Per-pixel sample counts (adaptive sampling).  With RTG_FLAG_SAMPLE_COUNTS `out` ends with a count plane of nx * ny uint32_t
  * words in pixel order (row 0 = top): it starts right after the float planes, at word 3 * nx * ny without
  * RTG_FLAG_SUM_SQUARES and at word 6 * nx * ny with it.  Its value n_p is pixel p's target count; let e_p = min(n_p, ns).  The
- * library only reads the count plane, never writes it.
+ * library only reads the count plane, never writes it (RTG_FLAG_RETIRE, below, is the one exception).
  *   - Precondition: the running sum of p holds samples [0, min(e_p, sample_begin)) (sample_begin = 0 without RTG_FLAG_RESUME).
  *   - The call renders samples [sample_begin, e_p) of p and continues the left fold in order (both planes under
  *     RTG_FLAG_SUM_SQUARES).  Pixels with e_p <= sample_begin get no samples.
@@ -128,6 +128,45 @@ typedef struct rtg_params {
  *     call, to read back how many pixels are active (the ray-pool kernels run over a compacted list of them).
  *     rtg_par_cast_multi returns RTG_ERR_UNSUPPORTED and writes and enqueues nothing; rtg_debug_samples returns
  *     RTG_ERR_INVALID. */
+
+#define RTG_FLAG_RETIRE 64u /* after the slice, retire converged pixels: n_p := ns in the count plane (below) */
+#define RTG_RETIRE_MAX_RADIUS 8u
+
+/* Adaptive sampling in the library.  RTG_FLAG_RETIRE needs RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES (else RTG_ERR_INVALID,
+ * nothing written or enqueued).  `out` then ends with a 64-byte retire block (rtg_retire) behind the count plane, at word
+ * 7 * nx * ny rounded up to an even word (8-byte aligned; compute the offset in 64 bits).  Let k = ns of the call and, for a
+ * pixel q, e_q = min(n_q, k).  Its standard errors se_q,c (c = the 3 channels) are computed in float64 from the running sums
+ * (S, Q) and e_q, in this order and without contraction:  m = S / e;  v = (Q - (e * m) * m) / (e - 1);  v = 0 where v <= 0 (NaN
+ * stays NaN);  se = sqrt(v / e);  se = +inf when e_q < 2 -- rtiow-rust_amd/noise.py standard_error_counts, bit for bit.  q is
+ * OK when e_q >= 2 and all three se_q,c <= target_se (NaN is never OK).  Pixel p RETIRES when it is owned, n_p > k,
+ * k >= min_samples, and every pixel q with n_q > 0 of the (2 radius + 1)^2 window around p (clipped to the image) is OK --
+ * pixels with n_q == 0 are not part of the frame and are ignored.  A retiring pixel gets n_p := k: the only write the library
+ * ever makes to the count plane.  radius = 0 is noise.retire's rule.
+ *   - Order: the call renders its slice, applies the rule to the undivided running sums, then divides (without
+ *     RTG_FLAG_PARTIAL; the division uses e_p, which retiring does not change).  sample_begin == ns with RTG_FLAG_PARTIAL
+ *     renders nothing and only applies the rule (re-deciding with another target, say).
+ *   - RTG_ERR_INVALID, nothing written: radius > RTG_RETIRE_MAX_RADIUS, a NaN or negative target_se, radius > 0 with
+ *     nranks > 1 (the neighbours live on other ranks).  With radius = 0 each rank decides for its own pixels.
+ *   - Every accepted call writes every out-field of the block, a rank that owns no tile included (zeros); it never writes the
+ *     in-fields or reserved2.  The integer fields are exact; sum_se2 is summed in a fixed order (the same inputs give the same
+ *     bits, whichever entry point and however the kernels are scheduled).
+ *   - rtg_par_cast uploads the block with the planes and copies back the planes, the count plane and the block's out-fields.
+ *     rtg_par_cast_device reads the in-fields back on `hip_stream` together with the compaction's result -- still one
+ *     synchronisation of the stream per call (the render-less call syncs for the in-fields alone).
+ *   - rtg_stats as without the flag; kernel_ms also covers the retire kernels.  rtg_par_cast_multi returns
+ *     RTG_ERR_UNSUPPORTED and rtg_debug_samples RTG_ERR_INVALID. */
+typedef struct rtg_retire {
+  double target_se;      /* in:  the largest standard error of a converged pixel's channel                       */
+  uint32_t min_samples;  /* in:  no pixel retires before k >= min_samples                                         */
+  uint32_t radius;       /* in:  0 .. RTG_RETIRE_MAX_RADIUS: the window every pixel of which must be OK          */
+  uint32_t active;       /* out: owned pixels with n_p > k after the call                                         */
+  uint32_t retired;      /* out: owned pixels whose n_p this call set to k                                        */
+  uint32_t estimated;    /* out: owned pixels with e_p >= 2 and three finite standard errors                      */
+  uint32_t reserved;     /* out: 0                                                                                */
+  double sum_se2;        /* out: sum of se^2 over those pixels' 3 channels (estimated RMSE: sqrt(sum_se2 / (3 estimated))) */
+  uint64_t samples_held; /* out: sum of e_p over the owned pixels                                                 */
+  uint64_t reserved2[2];
+} rtg_retire;
 
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */

@@ -24,6 +24,8 @@ FLAG_PARTIAL = 4   # leave the unnormalised running sum of the samples in the fr
 FLAG_RESUME = 8    # the framebuffer holds the running sum of samples [0, sample_begin): render [sample_begin, ns)
 FLAG_SUM_SQUARES = 16   # the framebuffer has a second plane: the running sum of the squared sample colours
 FLAG_SAMPLE_COUNTS = 32  # the framebuffer ends with a count plane: every pixel's own sample count (uint32)
+FLAG_RETIRE = 64         # after the slice, retire converged pixels in the count plane; the framebuffer ends with a Retire block
+RETIRE_MAX_RADIUS = 8
 
 
 class Camera(C.Structure):
@@ -41,6 +43,32 @@ class Params(C.Structure):
                 ("nranks", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32)]
 
 
+class Retire(C.Structure):
+    """include/rtiow_gpu.h rtg_retire: the block behind the count plane of an RTG_FLAG_RETIRE frame (64 bytes).  The caller
+    sets target_se / min_samples / radius; every accepted call writes the out-fields active .. samples_held."""
+    _fields_ = [("target_se", C.c_double), ("min_samples", C.c_uint32), ("radius", C.c_uint32),
+                ("active", C.c_uint32), ("retired", C.c_uint32), ("estimated", C.c_uint32), ("reserved", C.c_uint32),
+                ("sum_se2", C.c_double), ("samples_held", C.c_uint64), ("reserved2", C.c_uint64 * 2)]
+    OUT_FIELDS = ("active", "retired", "estimated", "reserved", "sum_se2", "samples_held")
+
+    def as_dict(self):
+        """The out-fields, plus est_rmse = sqrt(sum_se2 / (3 estimated)) (inf when no pixel has an estimate)."""
+        d = {k: getattr(self, k) for k in self.OUT_FIELDS}
+        d["est_rmse"] = float(np.sqrt(self.sum_se2 / (3 * self.estimated))) if self.estimated else float("inf")
+        return d
+
+
+def retire_block_offset(nx, ny):
+    """Byte offset of the Retire block in an RTG_FLAG_RETIRE frame: word 7 * nx * ny (two float planes and the count plane),
+    rounded up to an even word."""
+    return ((7 * nx * ny + 1) & ~1) * 4
+
+
+def retire_frame_bytes(nx, ny):
+    """Bytes of an RTG_FLAG_RETIRE frame: two float planes, the count plane, padding to 8 bytes, the 64-byte Retire block."""
+    return retire_block_offset(nx, ny) + C.sizeof(Retire)
+
+
 class Stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kernel_ms", C.c_float), ("samples", C.c_uint64),
                 ("aabb_tests", C.c_uint64), ("prim_tests", C.c_uint64), ("shaded_hits", C.c_uint64),
@@ -51,12 +79,12 @@ class Stats(C.Structure):
 
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
-                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False):
+                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False):
     """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
     RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
-    the count plane at the framebuffer's end."""
+    the count plane at the framebuffer's end; `retire`: RTG_FLAG_RETIRE, the retire block behind it."""
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
-    flags |= FLAG_SAMPLE_COUNTS if counts else 0
+    flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0)
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.nx, p.ny, p.ns = nx, ny, ns
@@ -82,6 +110,7 @@ def _hip_runtime():
         _hip = C.CDLL("libamdhip64.so")
         _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+        _hip.hipMemsetD32Async.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     return _hip
 
 
@@ -96,6 +125,12 @@ def _squares_supported(be):
         raise ValueError("squares=True: %s (prefix %s) does not implement RTG_FLAG_SUM_SQUARES" % (be.path, be.prefix))
 
 
+def _retire_supported(be):
+    """RTG_FLAG_RETIRE is the HIP library's (prefix rtg_), like the flags it builds on."""
+    if be.prefix != "rtg_":
+        raise ValueError("retire=: %s (prefix %s) does not implement RTG_FLAG_RETIRE" % (be.path, be.prefix))
+
+
 def _counts_supported(be):
     """RTG_FLAG_SAMPLE_COUNTS is the HIP library's (prefix rtg_), like RTG_FLAG_SUM_SQUARES: another library would ignore the
     count plane and render every pixel to ns."""
@@ -106,32 +141,40 @@ def _counts_supported(be):
 class CountsFrame:
     """One contiguous host framebuffer for RTG_FLAG_SAMPLE_COUNTS: the float planes ([ny, nx, 3], or [2, ny, nx, 3] with
     squares) followed by the count plane (uint32 [ny, nx]), as include/rtiow_gpu.h lays them out.  `planes` and `counts` are
-    views of `buf`; passing them as par_cast(out=frame.planes, counts=frame.counts) renders in place, without copies."""
+    views of `buf`; passing them as par_cast(out=frame.planes, counts=frame.counts) renders in place, without copies.
+    retire=True (needs squares): `buf` also holds the RTG_FLAG_RETIRE block, and `retire` is a Retire view of it
+    (par_cast(..., retire=frame.retire) renders in place too)."""
 
-    def __init__(self, nx, ny, squares=False):
+    def __init__(self, nx, ny, squares=False, retire=False):
+        if retire and not squares:
+            raise ValueError("a retire frame has two float planes: squares=True")
         n_f = (2 if squares else 1) * ny * nx * 3
-        self.buf = np.zeros(n_f + ny * nx, dtype=np.float32)
+        self.buf = np.zeros(retire_frame_bytes(nx, ny) // 4 if retire else n_f + ny * nx, dtype=np.float32)
         self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
-        self.counts = self.buf[n_f:].view(np.uint32).reshape(ny, nx)
+        self.counts = self.buf[n_f:n_f + ny * nx].view(np.uint32).reshape(ny, nx)
+        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
 
 
-def counts_frame(nx, ny, squares=False):
-    """A zeroed CountsFrame (float planes + count plane in one buffer)."""
-    return CountsFrame(nx, ny, squares)
+def counts_frame(nx, ny, squares=False, retire=False):
+    """A zeroed CountsFrame (float planes + count plane in one buffer; retire=True: + the Retire block)."""
+    return CountsFrame(nx, ny, squares, retire)
 
 
-def _counts_call(out, counts, nx, ny, squares):
-    """(buffer to render into, float planes view): `out` / `counts` themselves when the count plane already follows the
-    float planes in memory (a CountsFrame), else a staging CountsFrame holding copies of both."""
+def _counts_call(out, counts, nx, ny, squares, retire=None):
+    """(buffer to render into, float planes view): `out` / `counts` (/ `retire`) themselves when they already lie in memory
+    as include/rtiow_gpu.h lays out the frame (a CountsFrame's views), else a staging CountsFrame holding copies of them."""
     counts = np.asarray(counts)
     if counts.shape != (ny, nx):
         raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
     if (out.dtype == np.float32 and out.flags.c_contiguous and counts.dtype == np.uint32 and counts.flags.c_contiguous
-            and out.ctypes.data + out.nbytes == counts.ctypes.data):
+            and out.ctypes.data + out.nbytes == counts.ctypes.data
+            and (retire is None or C.addressof(retire) == out.ctypes.data + retire_block_offset(nx, ny))):
         return out, None
-    f = CountsFrame(nx, ny, squares)
+    f = CountsFrame(nx, ny, squares, retire is not None)
     f.planes[...] = out
     f.counts[...] = counts
+    if retire is not None:
+        C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
     return f.planes, f
 
 
@@ -486,7 +529,7 @@ class Scene:
         return args
 
     def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, counts=None, counters=None,
-                 **kw):
+                 retire=None, **kw):
         """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
         One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
         continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h).
@@ -495,17 +538,24 @@ class Scene:
         counts= (RTG_FLAG_SAMPLE_COUNTS): uint32 [ny, nx], every pixel's own sample count n_p -- the call renders samples
         [sample_begin, min(n_p, ns)) of each pixel; pixels with n_p = 0 are left as `out` holds them.  `out` and `counts` of
         one CountsFrame are rendered in place; anything else goes through a staging copy.
+        retire= (RTG_FLAG_RETIRE; needs counts= and squares=True): a Retire whose target_se / min_samples / radius the call
+        applies after its slice -- retiring pixels get n_p = ns in `counts` -- and whose out-fields it fills.  counts= must then
+        be a uint32 array the call can write (a CountsFrame(retire=True)'s counts and retire render in place).
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
         if kw.get("squares"):
             _squares_supported(self.be)
         if counts is not None:
             _counts_supported(self.be)
+        if retire is not None:
+            _retire_supported(self.be)
+            if counts is None or not kw.get("squares") or not isinstance(counts, np.ndarray):
+                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
         if counters is None:
             counters = stats
         p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, counts=counts is not None,
-                        **kw)
+                        retire=retire is not None, **kw)
         out = _host_frame(out, nx, ny, kw)
-        dst, staging = (out, None) if counts is None else _counts_call(out, counts, nx, ny, kw.get("squares"))
+        dst, staging = (out, None) if counts is None else _counts_call(out, counts, nx, ny, kw.get("squares"), retire)
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), dst.ctypes.data_as(c_f32p), C.byref(st)],
@@ -513,29 +563,44 @@ class Scene:
         self.be.check(self.be._par_cast(*args))
         if staging is not None:
             out[...] = staging.planes
+            if retire is not None:   # (the library wrote the count plane and the block's out-fields)
+                counts[...] = staging.counts
+                C.memmove(C.addressof(retire), C.addressof(staging.retire), C.sizeof(Retire))
         return (out, st.as_dict()) if stats else out
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None, counts=None):
+                        resume=None, squares=None, counts=None, retire=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
         With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
         counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
         (copied device to device) -- written to the count plane behind the float planes of `d_out_ptr` on `stream` before the
-        call; True: the flag alone, the caller has filled the count plane.  `d_out_ptr` then holds nx * ny more words."""
+        call; True: the flag alone, the caller has filled the count plane.  `d_out_ptr` then holds nx * ny more words.
+        retire= (RTG_FLAG_RETIRE): True, the flag alone (the caller has written the block's in-fields on the device); a Retire,
+        written to the block before the call and filled from it afterwards (the call then synchronises `stream`).  `d_out_ptr`
+        then holds retire_frame_bytes(nx, ny)."""
         if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
             _squares_supported(self.be)
         if counts is not None and counts is not False:
             _counts_supported(self.be)
+        block = None
+        if retire is not None and retire is not False:
+            _retire_supported(self.be)
+            if retire is not True:
+                block = retire
+                self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=True)
+                retire = True
         if counts is not None and counts is not True and counts is not False:
             sq = squares if squares is not None else bool(params.flags & FLAG_SUM_SQUARES)
             self._upload_counts(params.nx, params.ny, sq, counts, d_out_ptr, stream)
             counts = True
-        if sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None:
+        if (sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None
+                or retire is not None):
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
-            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS)):
+            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS),
+                            (retire, FLAG_RETIRE)):
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
@@ -543,7 +608,21 @@ class Scene:
         st.struct_size = C.sizeof(Stats)
         self.be.check(self.be._par_cast_device(self.h, C.byref(camera), C.byref(params), d_out_ptr, stream,
                                                C.byref(st) if want_stats else None))
+        if block is not None:
+            self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=False)
         return st.as_dict() if want_stats else None
+
+    def _block_copy(self, nx, ny, d_out_ptr, block, stream, to_device):
+        """Copy a Retire to (or from) the retire block of a device frame on `stream`, and wait for it (`block` is host memory)."""
+        hip = _hip_runtime()
+        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        dev = C.c_void_p(_device_ptr(d_out_ptr) + retire_block_offset(nx, ny))
+        host = C.c_void_p(C.addressof(block))
+        rc = hip.hipMemcpyAsync(*((dev, host, C.sizeof(Retire), 1) if to_device else (host, dev, C.sizeof(Retire), 2)), hs)
+        if rc == 0:
+            rc = hip.hipStreamSynchronize(hs)
+        if rc != 0:
+            raise RtError(ERR_DEVICE, "hipMemcpyAsync(retire block) failed: %d" % rc)
 
     def _upload_counts(self, nx, ny, squares, counts, d_out_ptr, stream):
         """Copy a uint32 [ny, nx] count array into the count plane of a device frame, on `stream`."""
@@ -565,21 +644,36 @@ class Scene:
             raise RtError(ERR_DEVICE, "hipMemcpyAsync(count plane) failed: %d" % rc)
 
     def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
-                 stats=None, **kw):
-        """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS), host frames.  Every slice renders `step` more
-        samples of the pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the
-        slice that ends at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest
-        per-channel standard error <= target_se): its count n_p becomes k and it gets no more samples.
-        Yields (counts, preview, stderr) after each slice: counts (uint32 [ny, nx]) the samples every pixel holds, preview
-        (float32 [ny, nx, 3]) the frame resolved per pixel -- preview[p] is bit for bit par_cast(ns = counts[p])[p] -- and
-        stderr (float64 [ny, nx, 3]) noise.standard_error_counts of every pixel.  Stops when no pixel is active, at ns, or
-        after the first slice that ends past budget_s seconds.
-        out: a CountsFrame(nx, ny, squares=True) to hold the running sums and counts (default: a new one).  stats: a list to
-        which every slice's rtg_stats (no counters) is appended.  **kw: tiling / max_bounces / t_near."""
+                 stats=None, radius=0, preview=None, stream=None, **kw):
+        """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS).  Every slice renders `step` more samples of the
+        pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the slice that ends
+        at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest per-channel standard
+        error <= target_se -- with radius > 0, that of every pixel of its (2 radius + 1)^2 window): its count n_p becomes k and
+        it gets no more samples.  Stops when no pixel is active, at ns, or after the first slice that ends past budget_s seconds.
+        Host frames (default): yields (counts, preview, stderr) after each slice: counts (uint32 [ny, nx]) the samples every
+        pixel holds, preview (float32 [ny, nx, 3]) the frame resolved per pixel -- preview[p] is bit for bit
+        par_cast(ns = counts[p])[p] -- and stderr (float64 [ny, nx, 3]) noise.standard_error_counts of every pixel.  out: a
+        CountsFrame(nx, ny, squares=True) to hold the running sums and counts (default: a new one).
+        Device frames: `out` is a device buffer of retire_frame_bytes(nx, ny) and `preview` one of 4 * nx * ny words (a
+        pointer, or an object with data_ptr()), `stream` a hipStream_t (int, an object with .cuda_stream, or None).  The rule
+        runs in the library (RTG_FLAG_RETIRE): a slice is one RETIRE call on `out`, a device-to-device copy of plane 0 and the
+        count plane into `preview`, the resolve-only counts call on `preview`, and one read-back of the retire block.  Yields
+        (k, preview, info), info = Retire.as_dict() of the block (active, retired, estimated, sum_se2, samples_held,
+        est_rmse).  The slices, counts and previews are those of the host loop.
+        stats: a list to which every slice's rtg_stats (no counters) is appended.  **kw: tiling / max_bounces / t_near."""
         if step < 1:
             raise ValueError("step must be >= 1")
         _squares_supported(self.be)
         _counts_supported(self.be)
+        if not 0 <= radius <= RETIRE_MAX_RADIUS:
+            raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
+        if out is not None and not isinstance(out, CountsFrame):
+            _retire_supported(self.be)
+            if preview is None:
+                raise ValueError("a device frame needs a device preview buffer (preview=)")
+            yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
+                                             radius, preview, stream, kw)
+            return
         f = CountsFrame(nx, ny, squares=True) if out is None else out
         if f.planes.shape != (2, ny, nx, 3):
             raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
@@ -596,7 +690,10 @@ class Scene:
             done = end
             held = np.minimum(f.counts, done).astype(np.uint32)
             se = noise.standard_error_counts(f.planes[0], f.planes[1], held)
-            retire = noise.retire(active, done, se, min_samples, target_se)
+            if radius:
+                retire = noise.retire(active, done, se, min_samples, target_se, radius=radius, present=f.counts > 0)
+            else:
+                retire = noise.retire(active, done, se, min_samples, target_se)
             f.counts[retire] = done
             active &= ~retire
             pv = CountsFrame(nx, ny)   # resolve a copy: the running sums go on
@@ -605,6 +702,45 @@ class Scene:
             self.par_cast(camera, nx, ny, done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
             yield held, pv.planes, se
             if not active.any():
+                return
+            if budget_s is not None and time.perf_counter() - t0 >= budget_s:
+                return
+
+    def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
+                         stream, kw):
+        hip = _hip_runtime()
+        d_out, d_pv = _device_ptr(out), _device_ptr(preview)
+        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        plane = nx * ny
+        counts_at = d_out + 6 * plane * 4
+
+        def ok(rc, what):
+            if rc != 0:
+                raise RtError(ERR_DEVICE, "%s failed: %d" % (what, rc))
+        # every pixel's target count is ns; the block's in-fields are written once (the library never writes them)
+        ok(hip.hipMemsetD32Async(C.c_void_p(counts_at), ns - (1 << 32) if ns >= 1 << 31 else ns, plane, hs), "hipMemsetD32Async(counts)")
+        block = Retire()
+        block.target_se, block.min_samples, block.radius = float(target_se), int(min_samples), int(radius)
+        self._block_copy(nx, ny, d_out, block, stream, to_device=True)
+        t0 = time.perf_counter()
+        done = 0
+        while done < ns:
+            end = min(ns, done + step)
+            st = self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
+                                                          squares=True, counts=True, retire=True, **kw), d_out, hs,
+                                      want_stats=stats is not None)
+            if stats is not None:
+                stats.append(st)
+            done = end
+            # the preview: plane 0 and the count plane, resolved per pixel (e_p = min(n_p, k): the samples each pixel holds)
+            ok(hip.hipMemcpyAsync(C.c_void_p(d_pv), C.c_void_p(d_out), plane * 3 * 4, 3, hs), "hipMemcpyAsync(preview)")
+            ok(hip.hipMemcpyAsync(C.c_void_p(d_pv + plane * 3 * 4), C.c_void_p(counts_at), plane * 4, 3, hs), "hipMemcpyAsync(preview counts)")
+            self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, counts=True, **kw),
+                                 d_pv, hs)
+            self._block_copy(nx, ny, d_out, block, stream, to_device=False)
+            info = block.as_dict()
+            yield done, preview, info
+            if info["active"] == 0:
                 return
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return

@@ -20,6 +20,7 @@
 
 #include "../../include/rtiow_gpu.h"
 #include "rt_pool.h"
+#include "rt_retire.h"
 #include "rt_pool_full.h"
 #include "rt_sync_full.h"
 #include "rt_pool2.h"
@@ -82,6 +83,9 @@ struct LaunchCtx {
   uint32_t* d_compact = nullptr;  // ... the compaction's per-block counts, offsets and samples, and its CompactResult
   size_t compact_bytes = 0;
   unsigned long long counts_samples = 0;  // ... rtg_stats.samples of the last counts call
+  void* d_retire = nullptr;     // RTG_FLAG_RETIRE: the OK bit plane and the retire kernels' per-block partials (rt_retire.h)
+  size_t retire_bytes = 0;
+  const char* refusal = nullptr;  // ... set by launch_counts when the block's in-fields are refused (RTG_ERR_INVALID, nothing written)
 };
 
 struct rtg_scene {
@@ -156,9 +160,11 @@ static void ctx_free_buffers(LaunchCtx* c) {
   if (c->d_lpt) (void)hipFree(c->d_lpt);
   if (c->d_list) (void)hipFree(c->d_list);
   if (c->d_compact) (void)hipFree(c->d_compact);
+  if (c->d_retire) (void)hipFree(c->d_retire);
   c->d_scratch = nullptr, c->scratch_bytes = 0, c->d_slots = nullptr, c->slots_bytes = 0;
   c->d_stack = nullptr, c->stack_bytes = 0, c->d_lpt = nullptr, c->lpt_bytes = 0;
   c->d_list = nullptr, c->list_bytes = 0, c->d_compact = nullptr, c->compact_bytes = 0;
+  c->d_retire = nullptr, c->retire_bytes = 0;
 }
 
 // Take the next launch context of the ring: create its small buffers on first use, wait for the frame that used it last.
@@ -196,6 +202,7 @@ struct SampleSlice {
   bool counts = false;  // RTG_FLAG_SAMPLE_COUNTS: the framebuffer ends with the count plane; the pool kernels run over a list
   uint32_t list_work = 0;  // ... set by the launcher (launch_counts): the list's length, a multiple of 256
   ListConsts list{};       // ... and where the list, its inverse and the count plane are
+  bool retire = false;  // RTG_FLAG_RETIRE: the framebuffer ends with an rtg_retire block; the retire step runs before the division
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -204,7 +211,18 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_PARTIAL) sl.divide = false;
   if (p->flags & RTG_FLAG_SUM_SQUARES) sl.squares = true;
   if (p->flags & RTG_FLAG_SAMPLE_COUNTS) sl.counts = true;
+  if (p->flags & RTG_FLAG_RETIRE) sl.retire = true;
   return sl;
+}
+
+// RTG_FLAG_RETIRE: the retire block's word offset in the framebuffer (7 nx ny words of planes and counts, rounded up to an even
+// word: 8-byte aligned), and why its in-fields are refused (nullptr: accepted)
+static uint64_t retire_block_word(uint32_t nx, uint32_t ny) { return ((uint64_t)7 * nx * ny + 1u) & ~1ull; }
+static const char* retire_refusal(const rtg_retire& r, uint32_t nranks) {
+  if (r.radius > RTG_RETIRE_MAX_RADIUS) return "RTG_FLAG_RETIRE: radius > RTG_RETIRE_MAX_RADIUS";
+  if (!(r.target_se >= 0.0)) return "RTG_FLAG_RETIRE: target_se is NaN or negative";
+  if (r.radius > 0u && nranks > 1u) return "RTG_FLAG_RETIRE: radius > 0 needs nranks = 1 (the neighbours live on other ranks)";
+  return nullptr;
 }
 
 #include "rtg_launch.inc"
@@ -702,6 +720,8 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   d.rank = p->rank;
   if (d.rank >= d.nranks) return fail(RTG_ERR_INVALID, "rank >= nranks");
   if ((p->flags & RTG_FLAG_RESUME) && p->sample_begin > p->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
+  if ((p->flags & RTG_FLAG_RETIRE) && (~p->flags & (RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES)))
+    return fail(RTG_ERR_INVALID, "RTG_FLAG_RETIRE needs RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES");
   *out = d;
   return RTG_OK;
 }
@@ -795,12 +815,14 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   }
 #endif
   if (stats) HIP_TRY_CTX(hipEventRecord(s->cx->ev0, stream));
+  s->cx->refusal = nullptr;
   HIP_TRY_CTX(count ? launch_render<true>(s, cam, d, d_out, stream, sl) : launch_render<false>(s, cam, d, d_out, stream, sl));
   if ((rc = ctx_release(s, stream))) {
     (void)hipStreamSynchronize(stream);
     return rc;
   }
 #undef HIP_TRY_CTX
+  if (s->cx->refusal) return fail(RTG_ERR_INVALID, s->cx->refusal);  // (read back on the stream: nothing of the frame was enqueued)
   if (stats) {
     HIP_TRY(hipEventRecord(s->cx->ev1, stream));
     HIP_TRY(hipEventSynchronize(s->cx->ev1));
@@ -834,12 +856,20 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     const int rc0 = check_params(s, camera, params, &d);
     if (rc0) return rc0;
   }
-  HIP_TRY(hipSetDevice(s->device));
   const SampleSlice sl = slice_of(params);
+  // RTG_FLAG_RETIRE: the block's in-fields are checked here, before anything is uploaded
+  const size_t block_bytes = sl.retire ? retire_block_word(params->nx, params->ny) * sizeof(float) : 0;
+  if (sl.retire) {
+    rtg_retire r;
+    memcpy(&r, reinterpret_cast<const char*>(out_rgb) + block_bytes, sizeof(r));
+    if (const char* why = retire_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
+  }
+  HIP_TRY(hipSetDevice(s->device));
   // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares; RTG_FLAG_SAMPLE_COUNTS adds the count plane, which
-  // travels to the device and is never copied back)
+  // travels to the device and is copied back only under RTG_FLAG_RETIRE, together with the out-fields of the retire block)
   size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (sl.squares ? 2 : 1);
-  const size_t in_bytes = bytes + (sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0);
+  const size_t count_bytes = sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0;
+  const size_t in_bytes = sl.retire ? block_bytes + sizeof(rtg_retire) : bytes + count_bytes;
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
   hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, in_bytes ? in_bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
@@ -851,7 +881,12 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sl.retire ? bytes + count_bytes : bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && sl.retire) {  // the out-fields only: active .. samples_held
+      const size_t lo = offsetof(rtg_retire, active), hi = offsetof(rtg_retire, reserved2);
+      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + block_bytes + lo, reinterpret_cast<const char*>(d_out) + block_bytes + lo, hi - lo,
+                    hipMemcpyDeviceToHost);
+    }
     if (e != hipSuccess) rc = hip_fail(e, "render / copy back");
   }
   return rc;

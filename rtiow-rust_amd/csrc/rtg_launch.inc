@@ -525,23 +525,55 @@ static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t s
   return hipGetLastError();
 }
 
+// RTG_FLAG_RETIRE (include/rtiow_gpu.h): the retire step of a counts call over this rank's work items (rt_retire.h) -- mark the
+// OK bits and the estimate's partials, retire the candidates whose window is OK, sum the partials into the caller's block.
+// `r`: the block's in-fields, already validated.  A rank without work items (pix_work = 0) only writes the block's zeros.
+static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, uint64_t pix_work, const rtg_retire& r) {
+  const uint32_t n_blk = (uint32_t)(pix_work / 256u);
+  const uint64_t plane = (uint64_t)d.nx * d.ny;
+  RetireBufs b;
+  b.pitch = (d.nx + 31u) / 32u + 1u;
+  // [blk_se2: f64 x n_blk] [blk_held: u64 x n_blk] [blk_u32: 3 x n_blk] [okbits: ny x pitch words]
+  hipError_t e = grow(&s->cx->d_retire, &s->cx->retire_bytes, (size_t)n_blk * 28u + (size_t)d.ny * b.pitch * 4u);
+  if (e != hipSuccess) return e;
+  b.blk_se2 = reinterpret_cast<double*>(s->cx->d_retire);
+  b.blk_held = reinterpret_cast<unsigned long long*>(b.blk_se2 + n_blk);
+  b.blk_u32 = reinterpret_cast<uint32_t*>(b.blk_held + n_blk);
+  b.okbits = b.blk_u32 + 3ull * n_blk;
+  b.planes = d_out;
+  b.counts = reinterpret_cast<uint32_t*>(d_out + 6ull * plane);
+  b.block = reinterpret_cast<uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
+  const RetireArgs a{r.target_se, d.ns, r.min_samples, r.radius};
+  if (n_blk != 0u) {
+    const PixMap pm = make_pixmap(d);
+    hipLaunchKernelGGL(retire_mark_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b);
+    hipLaunchKernelGGL(retire_apply_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b);
+  }
+  hipLaunchKernelGGL(retire_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
+  return hipGetLastError();
+}
+
 // RTG_FLAG_SAMPLE_COUNTS (include/rtiow_gpu.h): compact this rank's active pixels (e_p > sl.begin) into the list the pool
 // kernels run over (rt_pool.h compact_*), read back its length and the call's sample count -- the one synchronisation of the
 // stream a counts call makes -- render the list with the kernel the features pick (the baseline kernel walks every pixel and
 // skips the inactive ones itself), then, without RTG_FLAG_PARTIAL, divide every owned pixel with e_p > 0 by e_p.
+// RTG_FLAG_RETIRE: the block's in-fields come back with that read-back (on their own when the call renders nothing); refused
+// ones end the call before it renders (s->cx->refusal), accepted ones run the retire step between the render and the division.
 template <bool COUNT>
 static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
                                 const SampleSlice& sl, uint32_t geom, bool pool_ok) {
   s->cx->counts_samples = 0;
   const uint64_t pix_work = rank_pix_work(d);
-  if (pix_work == 0) return hipSuccess;  // this rank owns no tile
+  if (pix_work == 0 && !sl.retire) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
+  rtg_retire rin{};  // (RTG_FLAG_RETIRE: the in-fields, read back below)
+  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
   SampleSlice ls = sl;
   ls.list.counts = reinterpret_cast<const uint32_t*>(d_out + (sl.squares ? 6ull : 3ull) * d.nx * d.ny);
   const PixMap pm = make_pixmap(d);
   const uint32_t n_blk = (uint32_t)(pix_work / 256u);
   hipError_t e;
-  if (sl.begin < d.ns) {
+  if (sl.begin < d.ns && pix_work != 0) {
     e = grow((void**)&s->cx->d_list, &s->cx->list_bytes, 2 * pix_work * sizeof(uint32_t));
     if (e != hipSuccess) return e;
     // [blk_samples: u64 x n_blk] [CompactResult] [blk_active: n_blk] [blk_offset: n_blk]
@@ -562,8 +594,10 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     if (e != hipSuccess) return e;
     CompactResult h{};
     e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && sl.retire) e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
+    if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
     s->cx->counts_samples = h.samples;
     ls.list_work = h.padded;
     if (s->verbose)
@@ -589,8 +623,17 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
       }
       if (e != hipSuccess) return e;
     }
+  } else if (sl.retire) {
+    e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    if ((s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
   }
-  if (!sl.divide) return hipSuccess;
+  if (sl.retire) {
+    e = launch_retire(s, d, d_out, stream, pix_work, rin);
+    if (e != hipSuccess) return e;
+  }
+  if (!sl.divide || pix_work == 0) return hipSuccess;
   hipLaunchKernelGGL(resolve_counts_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, d_out, ls.list.counts);
   return hipGetLastError();
 }

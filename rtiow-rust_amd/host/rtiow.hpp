@@ -340,6 +340,58 @@ inline Image par_cast_counts(size_t nx, size_t ny, size_t ns, const std::vector<
   return img;
 }
 
+// Not in the reference: adaptive sampling with the retire rule in the library (RTG_FLAG_RETIRE).  Every pixel starts at n_p = ns;
+// each slice renders `step` more samples of the pixels still active and retires, in the same call, those whose (2 radius + 1)^2
+// window has every standard error <= target_se (once k >= min_samples).  Stops when no pixel is active or at ns.  `image` is the
+// frame resolved per pixel (pixel p = par_cast(nx, ny, counts[p], ...) at p, bit for bit), `counts` the samples each pixel got,
+// `block` the retire block of the last slice.
+struct AdaptiveImage {
+  Image image;
+  std::vector<uint32_t> counts;  // ny * nx
+  size_t slices = 0;
+  rtg_retire block{};
+};
+
+inline AdaptiveImage par_cast_adaptive(size_t nx, size_t ny, size_t ns, size_t step, double target_se, uint32_t min_samples,
+                                       uint32_t radius, const Camera& camera, const Scene& world,
+                                       const CastOptions& opt = CastOptions()) {
+  if (step == 0) throw Error(RTG_ERR_INVALID, "par_cast_adaptive: step must be > 0");
+  SceneHandle s = make_scene(world, opt);
+  const size_t n = nx * ny, block_word = (7 * n + 1) & ~size_t(1);  // planes, count plane, padding to 8 bytes, the block
+  std::vector<float> frame(block_word + sizeof(rtg_retire) / sizeof(float), 0.f);
+  std::vector<uint32_t> counts(n, (uint32_t)ns);
+  std::memcpy(frame.data() + 6 * n, counts.data(), n * sizeof(uint32_t));
+  rtg_retire r{};
+  r.target_se = target_se, r.min_samples = min_samples, r.radius = radius;
+  std::memcpy(frame.data() + block_word, &r, sizeof(r));
+  AdaptiveImage out;
+  size_t done = 0;
+  while (done < ns) {
+    const size_t end = std::min(ns, done + step);
+    rtg_params p = cast_params(nx, ny, end, opt);
+    p.flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RETIRE | RTG_FLAG_PARTIAL | RTG_FLAG_RESUME;
+    p.sample_begin = (uint32_t)done;
+    check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+    done = end, out.slices++;
+    std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_retire));
+    if (out.block.active == 0) break;
+  }
+  // resolve a copy of plane 0 with the count plane: each pixel divided by the samples it holds
+  std::memcpy(counts.data(), frame.data() + 6 * n, n * sizeof(uint32_t));
+  for (uint32_t& c : counts) c = std::min<uint32_t>(c, (uint32_t)done);
+  std::vector<float> pv(4 * n);
+  std::memcpy(pv.data(), frame.data(), 3 * n * sizeof(float));
+  std::memcpy(pv.data() + 3 * n, counts.data(), n * sizeof(uint32_t));
+  rtg_params p = cast_params(nx, ny, done, opt);
+  p.flags = RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RESUME;
+  p.sample_begin = (uint32_t)done;
+  check(rtg_par_cast(s.get(), &camera.c, &p, pv.data(), nullptr));
+  out.image.nx = nx, out.image.ny = ny;
+  out.image.rgb.assign(pv.begin(), pv.begin() + 3 * n);
+  out.counts = std::move(counts);
+  return out;
+}
+
 // Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /
 // (n - 1)), se = sqrt(s2 / n); +inf for n = 1.  `mean` = sum / n (par_cast's image; a PARTIAL running sum divided by n).
 inline double standard_error(double mean, double sum_sq, size_t n) {

@@ -29,6 +29,9 @@ pub const RTG_FLAG_RESUME: u32 = 8;
 pub const RTG_FLAG_SUM_SQUARES: u32 = 16;
 /// The framebuffer ends with a count plane of `nx * ny` `u32`: every pixel's own sample count (see the header).
 pub const RTG_FLAG_SAMPLE_COUNTS: u32 = 32;
+/// After the slice, retire converged pixels in the count plane; the framebuffer ends with an `rtg_retire` block (see the header).
+pub const RTG_FLAG_RETIRE: u32 = 64;
+pub const RTG_RETIRE_MAX_RADIUS: u32 = 8;
 
 #[repr(C)]
 pub struct rtg_builder {
@@ -71,6 +74,22 @@ pub struct rtg_params {
     pub nranks: u32,
     pub flags: u32,
     pub sample_begin: u32, // read under RTG_FLAG_RESUME only
+}
+
+/// 64 bytes, at word `7 * nx * ny` rounded up to an even word of an `RTG_FLAG_RETIRE` frame.
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct rtg_retire {
+    pub target_se: f64,
+    pub min_samples: u32,
+    pub radius: u32,
+    pub active: u32,
+    pub retired: u32,
+    pub estimated: u32,
+    pub reserved: u32,
+    pub sum_se2: f64,
+    pub samples_held: u64,
+    pub reserved2: [u64; 2],
 }
 
 /// 56 bytes.

@@ -280,6 +280,49 @@ impl GpuScene {
         Ok(Image { nx, ny, rgb: frame })
     }
 
+    /// Not in the reference: adaptive sampling with the retire rule in the library (`RTG_FLAG_RETIRE`, see the header).  Every
+    /// slice renders `step` more samples of the active pixels and retires, in the same call, those whose `(2 radius + 1)^2`
+    /// window has every standard error `<= target_se` (once `k >= min_samples`).  Returns the running sums' frame resolved per
+    /// pixel (pixel p = `par_cast(nx, ny, counts[p], ..)` at p, bit for bit), the samples each pixel got and the last slice's
+    /// block.  (Uncompiled, like the rest of this crate.)
+    pub fn par_cast_adaptive(&mut self, nx: usize, ny: usize, ns: usize, step: usize, target_se: f64, min_samples: u32, radius: u32,
+                             camera: &Camera, options: &CastOptions) -> Result<(Image, Vec<u32>, sys::rtg_retire)> {
+        if step == 0 {
+            return Err(Error { code: sys::RTG_ERR_INVALID, message: "par_cast_adaptive: step must be > 0".into() });
+        }
+        let n = nx * ny;
+        let block_word = (7 * n + 1) & !1; // planes, count plane, padding to 8 bytes, then the block
+        let mut frame = vec![0f32; block_word + 16];
+        for w in frame[6 * n..7 * n].iter_mut() {
+            *w = f32::from_bits(ns as u32);
+        }
+        let mut block = sys::rtg_retire { target_se, min_samples, radius, ..Default::default() };
+        unsafe { ptr::write_unaligned(frame.as_mut_ptr().add(block_word) as *mut sys::rtg_retire, block) };
+        let mut done = 0;
+        while done < ns {
+            let end = ns.min(done + step);
+            let mut p = params(nx, ny, end, options);
+            p.flags = sys::RTG_FLAG_SUM_SQUARES | sys::RTG_FLAG_SAMPLE_COUNTS | sys::RTG_FLAG_RETIRE | sys::RTG_FLAG_PARTIAL | sys::RTG_FLAG_RESUME;
+            p.sample_begin = done as u32;
+            check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, frame.as_mut_ptr(), ptr::null_mut()) })?;
+            done = end;
+            block = unsafe { ptr::read_unaligned(frame.as_ptr().add(block_word) as *const sys::rtg_retire) };
+            if block.active == 0 {
+                break;
+            }
+        }
+        // resolve a copy of plane 0 with the count plane: each pixel divided by the samples it holds
+        let counts: Vec<u32> = frame[6 * n..7 * n].iter().map(|w| w.to_bits().min(done as u32)).collect();
+        let mut pv = frame[..3 * n].to_vec();
+        pv.extend(counts.iter().map(|&c| f32::from_bits(c)));
+        let mut p = params(nx, ny, done, options);
+        p.flags = sys::RTG_FLAG_SAMPLE_COUNTS | sys::RTG_FLAG_RESUME;
+        p.sample_begin = done as u32;
+        check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, pv.as_mut_ptr(), ptr::null_mut()) })?;
+        pv.truncate(3 * n);
+        Ok((Image { nx, ny, rgb: pv }, counts, block))
+    }
+
     /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).
     /// After each slice `on_preview(n_done, &preview)` gets the frame resolved at `n_done` samples -- bit-identical to
     /// `par_cast(nx, ny, n_done, ..)` -- and returns `false` to stop early (time budget, cancel).  The preview at

@@ -9,7 +9,8 @@ of squares Q = sum c_i^2 (plane 1).  From (S, Q, n):
 
 and the frame's estimated RMS error against the converged image is sqrt(mean over pixels and channels of se^2).
 Everything is computed in float64.  With RTG_FLAG_SAMPLE_COUNTS every pixel has its own n (standard_error_counts), and
-adaptive sampling retires a pixel once its estimate is good enough (retire).
+adaptive sampling retires a pixel once its estimate -- or, with a radius, every estimate around it -- is good enough (retire;
+RTG_FLAG_RETIRE runs the same rule on the device).
 """
 import numpy as np
 
@@ -49,10 +50,33 @@ def standard_error_counts(sum_, sq, counts):
     return np.where(ok, np.sqrt(var / nn), np.inf)
 
 
-def retire(active, k, stderr, min_samples, target_se):
+def retire(active, k, stderr, min_samples, target_se, radius=0, present=None):
     """The retire rule of adaptive sampling (Scene.adaptive), after the slice that ends at k samples: the active pixels with
-    k >= min_samples whose largest per-channel standard error is <= target_se.  Returns a bool mask of the pixel grid."""
+    k >= min_samples whose largest per-channel standard error is <= target_se.  Returns a bool mask of the pixel grid.
+    radius > 0: every pixel of the (2 radius + 1)^2 window around a pixel (clipped to the image) must meet the target, not only
+    the pixel itself.  present: bool mask of the pixels that are part of the frame (n > 0; default: all); the others never
+    veto a window.  This is the rule include/rtiow_gpu.h RTG_FLAG_RETIRE applies on the device (with a finite target_se)."""
     active = np.asarray(active, dtype=bool)
     if k < min_samples:
         return np.zeros_like(active)
-    return active & (np.max(np.asarray(stderr, dtype=np.float64), axis=-1) <= target_se)
+    ok = np.max(np.asarray(stderr, dtype=np.float64), axis=-1) <= target_se
+    if present is not None:
+        ok |= ~np.asarray(present, dtype=bool)
+    if radius:
+        ok = window_all(ok, int(radius))
+    return active & ok
+
+
+def window_all(ok, radius):
+    """AND of a bool [ny, nx] grid over the (2 radius + 1)^2 window of every pixel, clipped to the grid (rows, then columns)."""
+    ny, nx = ok.shape
+    r = int(radius)
+    pad = np.ones((ny + 2 * r, nx + 2 * r), dtype=bool)
+    pad[r:r + ny, r:r + nx] = ok
+    rows = np.ones((ny + 2 * r, nx), dtype=bool)
+    for d in range(2 * r + 1):
+        rows &= pad[:, d:d + nx]
+    out = np.ones((ny, nx), dtype=bool)
+    for d in range(2 * r + 1):
+        out &= rows[d:d + ny]
+    return out
