@@ -26,6 +26,9 @@ FLAG_SUM_SQUARES = 16   # the framebuffer has a second plane: the running sum of
 FLAG_SAMPLE_COUNTS = 32  # the framebuffer ends with a count plane: every pixel's own sample count (uint32)
 FLAG_RETIRE = 64         # after the slice, retire converged pixels in the count plane; the framebuffer ends with a Retire block
 RETIRE_MAX_RADIUS = 8
+FLAG_DENOISE = 128       # after the slice, filter the frame: the framebuffer ends with a Denoise block and the output plane
+DENOISE_MAX_RADIUS = 8
+DENOISE_MAX_PATCH = 3
 
 
 class Camera(C.Structure):
@@ -69,6 +72,48 @@ def retire_frame_bytes(nx, ny):
     return retire_block_offset(nx, ny) + C.sizeof(Retire)
 
 
+class Denoise(C.Structure):
+    """include/rtiow_gpu.h rtg_denoise: the block in front of the output plane of an RTG_FLAG_DENOISE frame (64 bytes).  The
+    caller sets k / radius / patch; every accepted call writes the out-fields filtered / passed."""
+    _fields_ = [("k", C.c_float), ("radius", C.c_uint32), ("patch", C.c_uint32), ("reserved_in", C.c_uint32),
+                ("filtered", C.c_uint32), ("passed", C.c_uint32), ("reserved", C.c_uint32 * 10)]
+    OUT_FIELDS = ("filtered", "passed")
+    OUT_OFFSET = 16   # bytes: the in-fields end here
+
+    def as_dict(self):
+        """The out-fields."""
+        return {k: getattr(self, k) for k in self.OUT_FIELDS}
+
+
+def make_denoise(denoise=None, k=0.7, radius=5, patch=2):
+    """A Denoise with the in-fields set: from a Denoise (copied), a dict of k / radius / patch, or True / None (the defaults
+    0.7, 5, 2)."""
+    d = Denoise()
+    if isinstance(denoise, Denoise):
+        C.memmove(C.addressof(d), C.addressof(denoise), C.sizeof(Denoise))
+        return d
+    if isinstance(denoise, dict):
+        unknown = set(denoise) - {"k", "radius", "patch"}
+        if unknown:
+            raise ValueError("denoise=: unknown key(s) %s (k, radius, patch)" % sorted(unknown))
+        k, radius, patch = denoise.get("k", k), denoise.get("radius", radius), denoise.get("patch", patch)
+    d.k, d.radius, d.patch = float(k), int(radius), int(patch)
+    return d
+
+
+def denoise_block_offset(nx, ny, counts=False, retire=False):
+    """Byte offset of the Denoise block in an RTG_FLAG_DENOISE frame: the first even word behind the two float planes, the
+    count plane (counts=True) or the Retire block (retire=True, which implies the count plane)."""
+    if retire:
+        return retire_block_offset(nx, ny) + C.sizeof(Retire)
+    return (((7 if counts else 6) * nx * ny + 1) & ~1) * 4
+
+
+def denoise_frame_bytes(nx, ny, counts=False, retire=False):
+    """Bytes of an RTG_FLAG_DENOISE frame: everything the other flags put in it, the 64-byte Denoise block, the output plane."""
+    return denoise_block_offset(nx, ny, counts, retire) + C.sizeof(Denoise) + nx * ny * 3 * 4
+
+
 class Stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kernel_ms", C.c_float), ("samples", C.c_uint64),
                 ("aabb_tests", C.c_uint64), ("prim_tests", C.c_uint64), ("shaded_hits", C.c_uint64),
@@ -79,10 +124,13 @@ class Stats(C.Structure):
 
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
-                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False):
+                nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False,
+                denoise=False):
     """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
     RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
-    the count plane at the framebuffer's end; `retire`: RTG_FLAG_RETIRE, the retire block behind it."""
+    the count plane at the framebuffer's end; `retire`: RTG_FLAG_RETIRE, the retire block behind it; `denoise`:
+    RTG_FLAG_DENOISE, the denoise block and the output plane at the framebuffer's end."""
+    flags |= FLAG_DENOISE if denoise else 0
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
     flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0)
     p = Params()
@@ -131,6 +179,12 @@ def _retire_supported(be):
         raise ValueError("retire=: %s (prefix %s) does not implement RTG_FLAG_RETIRE" % (be.path, be.prefix))
 
 
+def _denoise_supported(be):
+    """RTG_FLAG_DENOISE is the HIP library's (prefix rtg_), like the flags it builds on."""
+    if be.prefix != "rtg_":
+        raise ValueError("denoise=: %s (prefix %s) does not implement RTG_FLAG_DENOISE" % (be.path, be.prefix))
+
+
 def _counts_supported(be):
     """RTG_FLAG_SAMPLE_COUNTS is the HIP library's (prefix rtg_), like RTG_FLAG_SUM_SQUARES: another library would ignore the
     count plane and render every pixel to ns."""
@@ -153,6 +207,32 @@ class CountsFrame:
         self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
         self.counts = self.buf[n_f:n_f + ny * nx].view(np.uint32).reshape(ny, nx)
         self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
+
+
+class DenoiseFrame:
+    """A sibling of CountsFrame (always two float planes; the count plane is optional).  One contiguous host framebuffer for RTG_FLAG_DENOISE, as include/rtiow_gpu.h lays it out: the two float planes
+    (`planes`, [2, ny, nx, 3]), with counts=True the count plane (`counts`, uint32 [ny, nx], else None), with retire=True
+    (implies counts) the Retire block (`retire`, else None), then the Denoise block (`denoise`) and the output plane
+    (`denoised`, float32 [ny, nx, 3]).  All are views of `buf`; par_cast(out=frame, denoise=...) renders in place."""
+
+    def __init__(self, nx, ny, counts=False, retire=False, denoise=None):
+        counts = bool(counts or retire)
+        n = nx * ny
+        off = denoise_block_offset(nx, ny, counts, retire)
+        self.nx, self.ny = nx, ny
+        self.buf = np.zeros(denoise_frame_bytes(nx, ny, counts, retire) // 4, dtype=np.float32)
+        self.planes = self.buf[:6 * n].reshape(2, ny, nx, 3)
+        self.counts = self.buf[6 * n:7 * n].view(np.uint32).reshape(ny, nx) if counts else None
+        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
+        self.denoise = Denoise.from_buffer(self.buf, off)
+        self.denoised = self.buf[off // 4 + 16:off // 4 + 16 + 3 * n].reshape(ny, nx, 3)
+        block = make_denoise(denoise)
+        C.memmove(C.addressof(self.denoise), C.addressof(block), Denoise.OUT_OFFSET)
+
+
+def denoise_frame(nx, ny, counts=False, retire=False, denoise=None):
+    """A zeroed DenoiseFrame whose block holds the in-fields of `denoise` (make_denoise: the defaults when None)."""
+    return DenoiseFrame(nx, ny, counts, retire, denoise)
 
 
 def counts_frame(nx, ny, squares=False, retire=False):
@@ -529,7 +609,7 @@ class Scene:
         return args
 
     def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, counts=None, counters=None,
-                 retire=None, **kw):
+                 retire=None, denoise=None, **kw):
         """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
         One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
         continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h).
@@ -541,7 +621,17 @@ class Scene:
         retire= (RTG_FLAG_RETIRE; needs counts= and squares=True): a Retire whose target_se / min_samples / radius the call
         applies after its slice -- retiring pixels get n_p = ns in `counts` -- and whose out-fields it fills.  counts= must then
         be a uint32 array the call can write (a CountsFrame(retire=True)'s counts and retire render in place).
+        denoise= (RTG_FLAG_DENOISE; needs squares=True): the call also filters the frame (denoise.nlm) and returns a DenoiseFrame
+        instead of an array -- views `planes`, `counts`, `retire`, `denoise` (the block, out-fields filled) and `denoised` (the
+        output plane).  denoise: a Denoise or a dict of k / radius / patch (True: the defaults).  out= a DenoiseFrame is
+        rendered in place and returned (denoise=True: its block as it stands; its own counts / retire views are used); with
+        any other out / counts / retire a new frame carries copies of them, and they are written back as without denoise=.
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
+        if denoise is not None and denoise is not False:
+            if not kw.get("squares"):
+                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
+            _denoise_supported(self.be)
+            return self._par_cast_denoise(camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, kw)
         if kw.get("squares"):
             _squares_supported(self.be)
         if counts is not None:
@@ -568,8 +658,55 @@ class Scene:
                 C.memmove(C.addressof(retire), C.addressof(staging.retire), C.sizeof(Retire))
         return (out, st.as_dict()) if stats else out
 
+    def _par_cast_denoise(self, camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, kw):
+        _squares_supported(self.be)
+        in_place = isinstance(out, DenoiseFrame)
+        if in_place:
+            f = out
+            if (f.nx, f.ny) != (nx, ny):
+                raise ValueError("out= is a DenoiseFrame of another size")
+            if counts is not None or retire is not None:
+                raise ValueError("out= a DenoiseFrame brings its own counts / retire views")
+            if denoise is not True:
+                block = make_denoise(denoise)
+                C.memmove(C.addressof(f.denoise), C.addressof(block), Denoise.OUT_OFFSET)
+        else:
+            if retire is not None and (counts is None or not isinstance(counts, np.ndarray)):
+                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
+            f = DenoiseFrame(nx, ny, counts is not None, retire is not None, None if denoise is True else denoise)
+            if out is not None:
+                f.planes[...] = _host_frame(out, nx, ny, kw)
+            elif _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
+            if counts is not None:
+                counts = np.asarray(counts)
+                if counts.shape != (ny, nx):
+                    raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+                f.counts[...] = counts
+            if retire is not None:
+                C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
+        if f.counts is not None:
+            _counts_supported(self.be)
+        if f.retire is not None:
+            _retire_supported(self.be)
+        if counters is None:
+            counters = stats
+        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, counts=f.counts is not None,
+                        retire=f.retire is not None, denoise=True, **kw)
+        st = Stats()
+        st.struct_size = C.sizeof(Stats)
+        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), f.buf.ctypes.data_as(c_f32p), C.byref(st)], threads)
+        self.be.check(self.be._par_cast(*args))
+        if not in_place:
+            if out is not None:
+                out[...] = f.planes
+            if retire is not None:
+                counts[...] = f.counts
+                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
+        return (f, st.as_dict()) if stats else f
+
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None, counts=None, retire=None):
+                        resume=None, squares=None, counts=None, retire=None, denoise=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
         With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
         counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
@@ -577,14 +714,29 @@ class Scene:
         call; True: the flag alone, the caller has filled the count plane.  `d_out_ptr` then holds nx * ny more words.
         retire= (RTG_FLAG_RETIRE): True, the flag alone (the caller has written the block's in-fields on the device); a Retire,
         written to the block before the call and filled from it afterwards (the call then synchronises `stream`).  `d_out_ptr`
-        then holds retire_frame_bytes(nx, ny)."""
+        then holds retire_frame_bytes(nx, ny).
+        denoise= (RTG_FLAG_DENOISE): True, the flag alone (the caller has written the block's in-fields on the device); a
+        Denoise, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
+        `d_out_ptr` then holds denoise_frame_bytes(nx, ny, counts, retire) for the flags the call ends up with."""
+        dblock = None   # (every refusal first: a refused call has written nothing to the caller's frame)
+        if denoise is not None and denoise is not False:
+            _denoise_supported(self.be)
         if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
             _squares_supported(self.be)
         if counts is not None and counts is not False:
             _counts_supported(self.be)
-        block = None
         if retire is not None and retire is not False:
             _retire_supported(self.be)
+        if denoise is not None and denoise is not False:
+            has = [bool(params.flags & bit) if on is None else on is not False
+                   for on, bit in ((counts, FLAG_SAMPLE_COUNTS), (retire, FLAG_RETIRE))]
+            d_off = denoise_block_offset(params.nx, params.ny, has[0], has[1])
+            if denoise is not True:
+                dblock = denoise
+                self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
+                denoise = True
+        block = None
+        if retire is not None and retire is not False:
             if retire is not True:
                 block = retire
                 self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=True)
@@ -594,13 +746,13 @@ class Scene:
             self._upload_counts(params.nx, params.ny, sq, counts, d_out_ptr, stream)
             counts = True
         if (sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None
-                or retire is not None):
+                or retire is not None or denoise is not None):
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
             for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS),
-                            (retire, FLAG_RETIRE)):
+                            (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE)):
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
@@ -610,19 +762,23 @@ class Scene:
                                                C.byref(st) if want_stats else None))
         if block is not None:
             self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=False)
+        if dblock is not None:
+            self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=False, offset=d_off, nbytes=C.sizeof(Denoise))
         return st.as_dict() if want_stats else None
 
-    def _block_copy(self, nx, ny, d_out_ptr, block, stream, to_device):
-        """Copy a Retire to (or from) the retire block of a device frame on `stream`, and wait for it (`block` is host memory)."""
+    def _block_copy(self, nx, ny, d_out_ptr, block, stream, to_device, offset=None, nbytes=None):
+        """Copy a Retire to (or from) the retire block of a device frame on `stream`, and wait for it (`block` is host memory);
+        offset / nbytes: another block of the frame (a Denoise) and how much of it."""
         hip = _hip_runtime()
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
-        dev = C.c_void_p(_device_ptr(d_out_ptr) + retire_block_offset(nx, ny))
+        dev = C.c_void_p(_device_ptr(d_out_ptr) + (retire_block_offset(nx, ny) if offset is None else offset))
         host = C.c_void_p(C.addressof(block))
-        rc = hip.hipMemcpyAsync(*((dev, host, C.sizeof(Retire), 1) if to_device else (host, dev, C.sizeof(Retire), 2)), hs)
+        n = C.sizeof(Retire) if nbytes is None else nbytes
+        rc = hip.hipMemcpyAsync(*((dev, host, n, 1) if to_device else (host, dev, n, 2)), hs)
         if rc == 0:
             rc = hip.hipStreamSynchronize(hs)
         if rc != 0:
-            raise RtError(ERR_DEVICE, "hipMemcpyAsync(retire block) failed: %d" % rc)
+            raise RtError(ERR_DEVICE, "hipMemcpyAsync(%s block) failed: %d" % (type(block).__name__.lower(), rc))
 
     def _upload_counts(self, nx, ny, squares, counts, d_out_ptr, stream):
         """Copy a uint32 [ny, nx] count array into the count plane of a device frame, on `stream`."""
@@ -644,7 +800,7 @@ class Scene:
             raise RtError(ERR_DEVICE, "hipMemcpyAsync(count plane) failed: %d" % rc)
 
     def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
-                 stats=None, radius=0, preview=None, stream=None, **kw):
+                 stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, **kw):
         """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS).  Every slice renders `step` more samples of the
         pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the slice that ends
         at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest per-channel standard
@@ -660,21 +816,41 @@ class Scene:
         count plane into `preview`, the resolve-only counts call on `preview`, and one read-back of the retire block.  Yields
         (k, preview, info), info = Retire.as_dict() of the block (active, retired, estimated, sum_se2, samples_held,
         est_rmse).  The slices, counts and previews are those of the host loop.
-        stats: a list to which every slice's rtg_stats (no counters) is appended.  **kw: tiling / max_bounces / t_near."""
+        stats: a list to which every slice's rtg_stats (no counters) is appended.  **kw: tiling / max_bounces / t_near.
+        denoise= (a Denoise, a dict of k / radius / patch, or True; RTG_FLAG_DENOISE): every slice's call also filters the
+        frame, and the loop yields the filtered frame as a fourth item.  Host frames: `out`, when given, is a
+        DenoiseFrame(nx, ny, counts=True); the item is a copy of its output plane.  Device frames: `out` holds
+        denoise_frame_bytes(nx, ny, counts=True, retire=True) and `denoised` is a device buffer of nx * ny * 3 floats, rewritten
+        every slice by a device-to-device copy of the output plane."""
         if step < 1:
             raise ValueError("step must be >= 1")
         _squares_supported(self.be)
         _counts_supported(self.be)
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
-        if out is not None and not isinstance(out, CountsFrame):
+        if denoise is not None and denoise is not False:
+            _denoise_supported(self.be)
+            denoise = make_denoise(None if denoise is True else denoise)
+        else:
+            denoise = None
+        if out is not None and not isinstance(out, (CountsFrame, DenoiseFrame)):
             _retire_supported(self.be)
             if preview is None:
                 raise ValueError("a device frame needs a device preview buffer (preview=)")
+            if denoise is not None and denoised is None:
+                raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
-                                             radius, preview, stream, kw)
+                                             radius, preview, stream, kw, denoise, denoised)
             return
-        f = CountsFrame(nx, ny, squares=True) if out is None else out
+        if denoise is not None:
+            f = DenoiseFrame(nx, ny, counts=True) if out is None else out
+            if not isinstance(f, DenoiseFrame) or f.counts is None or f.retire is not None:
+                raise ValueError("denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)")
+            C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+        else:
+            f = CountsFrame(nx, ny, squares=True) if out is None else out
+            if not isinstance(f, CountsFrame):
+                raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
         if f.planes.shape != (2, ny, nx, 3):
             raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
         f.counts[...] = ns
@@ -683,8 +859,12 @@ class Scene:
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True,
-                                  partial=True, squares=True, stats=True, counters=False, **kw)
+            if denoise is not None:
+                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f, denoise=True, sample_begin=done, resume=True,
+                                      partial=True, squares=True, stats=True, counters=False, **kw)
+            else:
+                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True,
+                                      partial=True, squares=True, stats=True, counters=False, **kw)
             if stats is not None:
                 stats.append(st)
             done = end
@@ -700,14 +880,17 @@ class Scene:
             pv.planes[...] = f.planes[0]
             pv.counts[...] = held
             self.par_cast(camera, nx, ny, done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
-            yield held, pv.planes, se
+            if denoise is not None:
+                yield held, pv.planes, se, f.denoised.copy()
+            else:
+                yield held, pv.planes, se
             if not active.any():
                 return
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
-                         stream, kw):
+                         stream, kw, denoise=None, denoised=None):
         hip = _hip_runtime()
         d_out, d_pv = _device_ptr(out), _device_ptr(preview)
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
@@ -722,13 +905,19 @@ class Scene:
         block = Retire()
         block.target_se, block.min_samples, block.radius = float(target_se), int(min_samples), int(radius)
         self._block_copy(nx, ny, d_out, block, stream, to_device=True)
+        if denoise is not None:   # (likewise: its in-fields once; the output plane sits 64 bytes behind the block)
+            d_off = denoise_block_offset(nx, ny, True, True)
+            self._block_copy(nx, ny, d_out, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
             st = self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
-                                                          squares=True, counts=True, retire=True, **kw), d_out, hs,
-                                      want_stats=stats is not None)
+                                                          squares=True, counts=True, retire=True, denoise=denoise is not None,
+                                                          **kw), d_out, hs, want_stats=stats is not None)
+            if denoise is not None:
+                ok(hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_out + d_off + C.sizeof(Denoise)), plane * 3 * 4,
+                                      3, hs), "hipMemcpyAsync(denoised)")
             if stats is not None:
                 stats.append(st)
             done = end
@@ -739,14 +928,17 @@ class Scene:
                                  d_pv, hs)
             self._block_copy(nx, ny, d_out, block, stream, to_device=False)
             info = block.as_dict()
-            yield done, preview, info
+            if denoise is not None:
+                yield done, preview, info, denoised
+            else:
+                yield done, preview, info
             if info["active"] == 0:
                 return
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
     def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None,
-                    squares=False, target_rmse=None, **kw):
+                    squares=False, target_rmse=None, denoise=None, denoised=None, **kw):
         """Render a frame `step` samples at a time (include/rtiow_gpu.h progressive rendering).  Yields (n_done, preview)
         after each slice: the preview is bit-identical to par_cast(ns = n_done), and the one at n_done == ns is the final
         image, bit-identical to par_cast(ns).  Stops at ns, or after the first slice that ends past `budget_s` seconds.
@@ -760,10 +952,21 @@ class Scene:
         noise.standard_error of every pixel and channel (float64 [ny, nx, 3]); on the device it is `out` itself, the two
         planes the estimate is computed from (no device-side reduction).
         target_rmse (host frames; implies squares): stop after the first slice whose noise.estimated_rmse is <= target_rmse
-        -- or at ns, or at budget_s, whichever comes first.  **kw: tiling / max_bounces / t_near."""
+        -- or at ns, or at budget_s, whichever comes first.  **kw: tiling / max_bounces / t_near.
+        denoise= (a Denoise, a dict of k / radius / patch, or True; RTG_FLAG_DENOISE; implies squares): every slice's call also
+        filters the frame (denoise.nlm of the running sums), and the loop yields (n_done, preview, stderr, denoised).  Host
+        frames: denoised is a new float32 [ny, nx, 3] array per slice.  Device frames: `out` holds denoise_frame_bytes(nx, ny)
+        and `denoised` is a device buffer of nx * ny * 3 floats, rewritten every slice by a device-to-device copy of the
+        output plane, and yielded as the fourth item."""
         if step < 1:
             raise ValueError("step must be >= 1")
-        squares = bool(squares) or target_rmse is not None
+        if denoise is not None and denoise is not False:
+            _squares_supported(self.be)
+            _denoise_supported(self.be)
+            denoise = make_denoise(None if denoise is True else denoise)
+        else:
+            denoise = None
+        squares = bool(squares) or target_rmse is not None or denoise is not None
         if squares:
             _squares_supported(self.be)
         if out is not None and not isinstance(out, np.ndarray):
@@ -771,45 +974,72 @@ class Scene:
                 raise ValueError("target_rmse needs host frames: there is no device-side error reduction")
             if preview is None:
                 raise ValueError("a device running sum needs a device preview buffer (preview=)")
-            yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, squares, kw)
+            if denoise is not None and denoised is None:
+                raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
+            yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, squares, kw,
+                                                denoise, denoised)
             return
         shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
         acc = np.zeros(shape, dtype=np.float32) if out is None else out
+        frame = None
+        if denoise is not None:   # the slices render into a DenoiseFrame; a caller's `out` is kept up to date beside it
+            frame = DenoiseFrame(nx, ny, denoise=denoise)
+            frame.planes[...] = acc
         sums = acc[0] if squares else acc
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, squares=squares, **kw)
+            if frame is not None:
+                self.par_cast(camera, nx, ny, end, seed=seed, out=frame, denoise=True, sample_begin=done, resume=True, partial=True,
+                              squares=True, **kw)
+                acc[...] = frame.planes
+            else:
+                self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, squares=squares, **kw)
             done = end
-            frame = sums.copy()   # resolve a copy: the running sum goes on
-            self.par_cast(camera, nx, ny, done, seed=seed, out=frame, sample_begin=done, resume=True, **kw)
+            pv = sums.copy()   # resolve a copy: the running sum goes on
+            self.par_cast(camera, nx, ny, done, seed=seed, out=pv, sample_begin=done, resume=True, **kw)
             if squares:
                 se = noise.standard_error(acc[0], acc[1], done)
-                yield done, frame, se
+                if frame is not None:
+                    yield done, pv, se, frame.denoised.copy()
+                else:
+                    yield done, pv, se
                 if target_rmse is not None and float(np.sqrt(np.mean(se * se))) <= target_rmse:
                     return
             else:
-                yield done, frame
+                yield done, pv
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
-    def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw):
+    def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw, denoise=None,
+                            denoised=None):
         hip = _hip_runtime()
         d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        if denoise is not None:   # the block's in-fields are written once (the library never writes them)
+            d_off = denoise_block_offset(nx, ny)
+            self._block_copy(nx, ny, acc, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
             self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
-                                                     squares=squares, **kw), d_acc, hs)
+                                                     squares=squares, denoise=denoise is not None, **kw), d_acc, hs)
             done = end
+            if denoise is not None:
+                rc = hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_acc.value + d_off + C.sizeof(Denoise)),
+                                        nx * ny * 3 * 4, 3, hs)
+                if rc != 0:
+                    raise RtError(ERR_DEVICE, "hipMemcpyAsync(denoised) failed: %d" % rc)
             rc = hip.hipMemcpyAsync(d_preview, d_acc, nx * ny * 3 * 4, 3, hs)   # plane 0; 3 = hipMemcpyDeviceToDevice
             if rc != 0:
                 raise RtError(ERR_DEVICE, "hipMemcpyAsync(preview) failed: %d" % rc)
             self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, **kw), d_preview, hs)
-            yield (done, preview, acc) if squares else (done, preview)
+            if denoise is not None:
+                yield done, preview, acc, denoised
+            else:
+                yield (done, preview, acc) if squares else (done, preview)
             if budget_s is not None:
                 if hip.hipStreamSynchronize(hs) != 0:
                     raise RtError(ERR_DEVICE, "hipStreamSynchronize failed")

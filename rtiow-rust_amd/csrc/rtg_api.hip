@@ -21,6 +21,7 @@
 #include "../../include/rtiow_gpu.h"
 #include "rt_pool.h"
 #include "rt_retire.h"
+#include "rt_denoise.h"
 #include "rt_pool_full.h"
 #include "rt_sync_full.h"
 #include "rt_pool2.h"
@@ -86,6 +87,9 @@ struct LaunchCtx {
   void* d_retire = nullptr;     // RTG_FLAG_RETIRE: the OK bit plane and the retire kernels' per-block partials (rt_retire.h)
   size_t retire_bytes = 0;
   const char* refusal = nullptr;  // ... set by launch_counts when the block's in-fields are refused (RTG_ERR_INVALID, nothing written)
+  void* d_denoise = nullptr;    // RTG_FLAG_DENOISE: the per-pixel (m, v, valid) records and the prepare kernel's per-block counts (rt_denoise.h)
+  size_t denoise_bytes = 0;
+  rtg_denoise denoise_in{};     // ... the block's in-fields of a call without a count plane, read back before its first kernel
 };
 
 struct rtg_scene {
@@ -161,10 +165,12 @@ static void ctx_free_buffers(LaunchCtx* c) {
   if (c->d_list) (void)hipFree(c->d_list);
   if (c->d_compact) (void)hipFree(c->d_compact);
   if (c->d_retire) (void)hipFree(c->d_retire);
+  if (c->d_denoise) (void)hipFree(c->d_denoise);
   c->d_scratch = nullptr, c->scratch_bytes = 0, c->d_slots = nullptr, c->slots_bytes = 0;
   c->d_stack = nullptr, c->stack_bytes = 0, c->d_lpt = nullptr, c->lpt_bytes = 0;
   c->d_list = nullptr, c->list_bytes = 0, c->d_compact = nullptr, c->compact_bytes = 0;
   c->d_retire = nullptr, c->retire_bytes = 0;
+  c->d_denoise = nullptr, c->denoise_bytes = 0;
 }
 
 // Take the next launch context of the ring: create its small buffers on first use, wait for the frame that used it last.
@@ -203,6 +209,7 @@ struct SampleSlice {
   uint32_t list_work = 0;  // ... set by the launcher (launch_counts): the list's length, a multiple of 256
   ListConsts list{};       // ... and where the list, its inverse and the count plane are
   bool retire = false;  // RTG_FLAG_RETIRE: the framebuffer ends with an rtg_retire block; the retire step runs before the division
+  bool denoise = false; // RTG_FLAG_DENOISE: the framebuffer ends with an rtg_denoise block and the output plane; the filter runs before the division
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -212,6 +219,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_SUM_SQUARES) sl.squares = true;
   if (p->flags & RTG_FLAG_SAMPLE_COUNTS) sl.counts = true;
   if (p->flags & RTG_FLAG_RETIRE) sl.retire = true;
+  if (p->flags & RTG_FLAG_DENOISE) sl.denoise = true;
   return sl;
 }
 
@@ -222,6 +230,22 @@ static const char* retire_refusal(const rtg_retire& r, uint32_t nranks) {
   if (r.radius > RTG_RETIRE_MAX_RADIUS) return "RTG_FLAG_RETIRE: radius > RTG_RETIRE_MAX_RADIUS";
   if (!(r.target_se >= 0.0)) return "RTG_FLAG_RETIRE: target_se is NaN or negative";
   if (r.radius > 0u && nranks > 1u) return "RTG_FLAG_RETIRE: radius > 0 needs nranks = 1 (the neighbours live on other ranks)";
+  return nullptr;
+}
+
+// RTG_FLAG_DENOISE: the denoise block's word offset in the framebuffer -- the first even word behind the planes (6 nx ny words),
+// the count plane (7 nx ny) or the retire block (its word + 16) -- the output plane 16 words behind it, and why the block's
+// in-fields are refused (nullptr: accepted)
+static uint64_t denoise_block_word(uint32_t nx, uint32_t ny, bool counts, bool retire) {
+  if (retire) return retire_block_word(nx, ny) + 16u;
+  return ((uint64_t)(counts ? 7 : 6) * nx * ny + 1u) & ~1ull;
+}
+static const char* denoise_refusal(const rtg_denoise& r, uint32_t nranks) {
+  if (r.radius > RTG_DENOISE_MAX_RADIUS) return "RTG_FLAG_DENOISE: radius > RTG_DENOISE_MAX_RADIUS";
+  if (r.patch > RTG_DENOISE_MAX_PATCH) return "RTG_FLAG_DENOISE: patch > RTG_DENOISE_MAX_PATCH";
+  if (!(r.k > 0.f) || !std::isfinite(r.k)) return "RTG_FLAG_DENOISE: k is NaN, infinite or <= 0";
+  if (r.reserved_in != 0u) return "RTG_FLAG_DENOISE: reserved_in != 0";
+  if (nranks > 1u) return "RTG_FLAG_DENOISE needs nranks = 1 (the neighbours live on other ranks)";
   return nullptr;
 }
 
@@ -722,6 +746,8 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   if ((p->flags & RTG_FLAG_RESUME) && p->sample_begin > p->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   if ((p->flags & RTG_FLAG_RETIRE) && (~p->flags & (RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES)))
     return fail(RTG_ERR_INVALID, "RTG_FLAG_RETIRE needs RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES");
+  if ((p->flags & RTG_FLAG_DENOISE) && !(p->flags & RTG_FLAG_SUM_SQUARES)) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE needs RTG_FLAG_SUM_SQUARES");
+  if ((p->flags & RTG_FLAG_DENOISE) && d.nranks > 1u) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE needs nranks = 1 (the neighbours live on other ranks)");
   *out = d;
   return RTG_OK;
 }
@@ -798,6 +824,14 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
       return hip_fail(e_, #expr);                       \
     }                                                   \
   } while (0)
+  if (sl.denoise && !sl.counts) {
+    // RTG_FLAG_DENOISE without a count plane: the block's in-fields come back now, before anything of the frame is enqueued
+    // and outside the timed span (a counts call reads them with its compaction result: launch_counts)
+    const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, false, false);
+    HIP_TRY(hipMemcpyAsync(&s->cx->denoise_in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (const char* why = denoise_refusal(s->cx->denoise_in, d.nranks)) return fail(RTG_ERR_INVALID, why);
+  }
   if (count) {
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), stream));
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), stream));
@@ -864,12 +898,20 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     memcpy(&r, reinterpret_cast<const char*>(out_rgb) + block_bytes, sizeof(r));
     if (const char* why = retire_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
   }
+  // RTG_FLAG_DENOISE: likewise; the block and the output plane end the frame
+  const size_t dblock_bytes = sl.denoise ? denoise_block_word(params->nx, params->ny, sl.counts, sl.retire) * sizeof(float) : 0;
+  const size_t plane_bytes = (size_t)params->nx * params->ny * 3 * sizeof(float);
+  if (sl.denoise) {
+    rtg_denoise r;
+    memcpy(&r, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(r));
+    if (const char* why = denoise_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
+  }
   HIP_TRY(hipSetDevice(s->device));
   // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares; RTG_FLAG_SAMPLE_COUNTS adds the count plane, which
   // travels to the device and is copied back only under RTG_FLAG_RETIRE, together with the out-fields of the retire block)
   size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (sl.squares ? 2 : 1);
   const size_t count_bytes = sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0;
-  const size_t in_bytes = sl.retire ? block_bytes + sizeof(rtg_retire) : bytes + count_bytes;
+  const size_t in_bytes = sl.denoise ? dblock_bytes + sizeof(rtg_denoise) + plane_bytes : sl.retire ? block_bytes + sizeof(rtg_retire) : bytes + count_bytes;
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
   hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, in_bytes ? in_bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
@@ -878,6 +920,8 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
   // frame, whose running sums are in out_rgb, or renders per-pixel counts (pixels with n_p = 0 stay as they are)
   const bool upload = params->nranks > 1 || sl.begin != 0u || sl.counts;
   if (upload) e = hipMemcpy(d_out, out_rgb, in_bytes, hipMemcpyHostToDevice);
+  else if (sl.denoise)  // (the block alone: a whole frame without counts writes every pixel of every plane)
+    e = hipMemcpy(reinterpret_cast<char*>(d_out) + dblock_bytes, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(rtg_denoise), hipMemcpyHostToDevice);
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();
@@ -886,6 +930,10 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
       const size_t lo = offsetof(rtg_retire, active), hi = offsetof(rtg_retire, reserved2);
       e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + block_bytes + lo, reinterpret_cast<const char*>(d_out) + block_bytes + lo, hi - lo,
                     hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess && sl.denoise) {  // the out-fields (filtered .. reserved) and the output plane behind them
+      const size_t lo = dblock_bytes + offsetof(rtg_denoise, filtered);
+      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + lo, reinterpret_cast<const char*>(d_out) + lo, in_bytes - lo, hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) rc = hip_fail(e, "render / copy back");
   }

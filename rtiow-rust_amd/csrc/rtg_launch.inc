@@ -553,12 +553,49 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
   return hipGetLastError();
 }
 
+// RTG_FLAG_DENOISE (include/rtiow_gpu.h): the filter step over the whole frame (rt_denoise.h; nranks = 1) -- the per-pixel
+// records and the pass-through pixels, the filter into the output plane, the block's out-fields.  It reads the UNDIVIDED
+// running sums: the callers run it after the slice (and the retire step) and before the division.  `in`: the block's
+// in-fields, already validated.
+static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const rtg_denoise& in) {
+  const uint64_t n_pix = (uint64_t)d.nx * d.ny;
+  const uint32_t n_blk = (uint32_t)((n_pix + 255u) / 256u);
+  // [records: 32 B x n_pix] [blk_u32: 2 x n_blk]
+  hipError_t e = grow(&s->cx->d_denoise, &s->cx->denoise_bytes, (size_t)n_pix * 32u + (size_t)n_blk * 8u);
+  if (e != hipSuccess) return e;
+  uint32_t* words = reinterpret_cast<uint32_t*>(d_out);
+  DenoiseBufs b;
+  b.planes = d_out;
+  b.counts = sl.counts ? words + 6ull * n_pix : nullptr;
+  b.rec = reinterpret_cast<float4*>(s->cx->d_denoise);
+  b.blk_u32 = reinterpret_cast<uint32_t*>(b.rec + 2ull * n_pix);
+  b.block = words + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
+  b.outp = reinterpret_cast<float*>(b.block + 16);
+  const DenoiseArgs a{in.k, in.radius, in.patch, d.ns};
+  const size_t lds = denoise_lds_bytes(in.radius, in.patch);
+  int per_cu = 0;
+  e = kernel_setup(s, (const void*)denoise_filter_kernel, (int)DN_THREADS, lds, &per_cu);  // (the raise of the dynamic-LDS limit)
+  if (e != hipSuccess) return e;
+  const uint64_t tiles = (uint64_t)((d.nx + DN_TW - 1u) / DN_TW) * ((d.ny + DN_TH - 1u) / DN_TH);
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(denoise_prepare_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
+  hipLaunchKernelGGL(denoise_filter_kernel, dim3((uint32_t)tiles), dim3(DN_THREADS), lds, stream, d.nx, d.ny, a, b);
+  hipLaunchKernelGGL(denoise_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
+  return hipGetLastError();
+}
+// ... and the read-back of its in-fields on the launch stream, with a counts call's other read-backs
+static hipError_t read_denoise_block(const DevParams& d, const float* d_out, hipStream_t stream, const SampleSlice& sl, rtg_denoise* in) {
+  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
+  return hipMemcpyAsync(in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream);
+}
+
 // RTG_FLAG_SAMPLE_COUNTS (include/rtiow_gpu.h): compact this rank's active pixels (e_p > sl.begin) into the list the pool
 // kernels run over (rt_pool.h compact_*), read back its length and the call's sample count -- the one synchronisation of the
 // stream a counts call makes -- render the list with the kernel the features pick (the baseline kernel walks every pixel and
 // skips the inactive ones itself), then, without RTG_FLAG_PARTIAL, divide every owned pixel with e_p > 0 by e_p.
 // RTG_FLAG_RETIRE: the block's in-fields come back with that read-back (on their own when the call renders nothing); refused
 // ones end the call before it renders (s->cx->refusal), accepted ones run the retire step between the render and the division.
+// RTG_FLAG_DENOISE: its in-fields travel in the same read-back; the filter runs after the retire step, before the division.
 template <bool COUNT>
 static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
                                 const SampleSlice& sl, uint32_t geom, bool pool_ok) {
@@ -567,6 +604,7 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
   if (pix_work == 0 && !sl.retire) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   rtg_retire rin{};  // (RTG_FLAG_RETIRE: the in-fields, read back below)
+  rtg_denoise din{};  // (RTG_FLAG_DENOISE: likewise)
   const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
   SampleSlice ls = sl;
   ls.list.counts = reinterpret_cast<const uint32_t*>(d_out + (sl.squares ? 6ull : 3ull) * d.nx * d.ny);
@@ -595,9 +633,11 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     CompactResult h{};
     e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && sl.retire) e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
+    if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
     s->cx->counts_samples = h.samples;
     ls.list_work = h.padded;
     if (s->verbose)
@@ -623,14 +663,20 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
       }
       if (e != hipSuccess) return e;
     }
-  } else if (sl.retire) {
-    e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
+  } else if (sl.retire || sl.denoise) {
+    e = sl.retire ? hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream) : hipSuccess;
+    if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
-    if ((s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
+    if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
+    if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
   }
   if (sl.retire) {
     e = launch_retire(s, d, d_out, stream, pix_work, rin);
+    if (e != hipSuccess) return e;
+  }
+  if (sl.denoise) {
+    e = launch_denoise(s, d, d_out, stream, sl, din);
     if (e != hipSuccess) return e;
   }
   if (!sl.divide || pix_work == 0) return hipSuccess;
@@ -650,6 +696,17 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
   s->cx->last_kernel = KernelKind::baseline;
   if (sl.counts) return launch_counts<COUNT>(s, cam, d, d_out, stream, sl, geom, pool_ok);
+  if (sl.denoise) {
+    // RTG_FLAG_DENOISE without a count plane (the block's in-fields were read back and checked by rtg_par_cast_device): render
+    // the slice as a PARTIAL one, whichever kernel takes it, filter the undivided sums, then divide as the resolve step does
+    const rtg_denoise din = s->cx->denoise_in;
+    SampleSlice render = sl;
+    render.denoise = false, render.divide = false;
+    hipError_t e = launch_render<COUNT>(s, cam, d, d_out, stream, render);
+    if (e == hipSuccess) e = launch_denoise(s, d, d_out, stream, sl, din);
+    if (e != hipSuccess) return e;
+    return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;
+  }
   if (sl.begin == d.ns) return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;  // nothing to render
   if (geom != 0 && pool_ok) {
     s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)

@@ -392,6 +392,33 @@ inline AdaptiveImage par_cast_adaptive(size_t nx, size_t ny, size_t ns, size_t s
   return out;
 }
 
+// Not in the reference: par_cast with RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE.  `image` is exactly what par_cast returns;
+// `denoised` is the frame filtered by the library's variance-driven non-local-means filter (strength k, search radius `radius`,
+// patch radius `patch`: see the header), `block` the denoise block with its out-fields.
+struct DenoisedImage {
+  Image image, denoised;
+  rtg_denoise block{};
+};
+
+inline DenoisedImage par_cast_denoised(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, float k = 0.7f,
+                                       uint32_t radius = 5, uint32_t patch = 2, const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  const size_t n = nx * ny, block_word = (6 * n + 1) & ~size_t(1);  // two planes, padding to 8 bytes, the block, the output plane
+  std::vector<float> frame(block_word + sizeof(rtg_denoise) / sizeof(float) + 3 * n, 0.f);
+  rtg_denoise d{};
+  d.k = k, d.radius = radius, d.patch = patch;
+  std::memcpy(frame.data() + block_word, &d, sizeof(d));
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE;
+  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  DenoisedImage out;
+  out.image.nx = out.denoised.nx = nx, out.image.ny = out.denoised.ny = ny;
+  out.image.rgb.assign(frame.begin(), frame.begin() + 3 * n);
+  out.denoised.rgb.assign(frame.begin() + block_word + 16, frame.end());
+  std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_denoise));
+  return out;
+}
+
 // Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /
 // (n - 1)), se = sqrt(s2 / n); +inf for n = 1.  `mean` = sum / n (par_cast's image; a PARTIAL running sum divided by n).
 inline double standard_error(double mean, double sum_sq, size_t n) {

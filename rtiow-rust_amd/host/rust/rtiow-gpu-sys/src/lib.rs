@@ -32,6 +32,10 @@ pub const RTG_FLAG_SAMPLE_COUNTS: u32 = 32;
 /// After the slice, retire converged pixels in the count plane; the framebuffer ends with an `rtg_retire` block (see the header).
 pub const RTG_FLAG_RETIRE: u32 = 64;
 pub const RTG_RETIRE_MAX_RADIUS: u32 = 8;
+/// After the slice, filter the frame: the framebuffer ends with an `rtg_denoise` block and an output plane (see the header).
+pub const RTG_FLAG_DENOISE: u32 = 128;
+pub const RTG_DENOISE_MAX_RADIUS: u32 = 8;
+pub const RTG_DENOISE_MAX_PATCH: u32 = 3;
 
 #[repr(C)]
 pub struct rtg_builder {
@@ -90,6 +94,20 @@ pub struct rtg_retire {
     pub sum_se2: f64,
     pub samples_held: u64,
     pub reserved2: [u64; 2],
+}
+
+/// 64 bytes, at the first even word behind the planes / count plane / retire block of an `RTG_FLAG_DENOISE` frame; the output
+/// plane (`nx * ny * 3` floats) starts 16 words behind it.
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct rtg_denoise {
+    pub k: c_float,
+    pub radius: u32,
+    pub patch: u32,
+    pub reserved_in: u32,
+    pub filtered: u32,
+    pub passed: u32,
+    pub reserved: [u32; 10],
 }
 
 /// 56 bytes.

@@ -323,6 +323,25 @@ impl GpuScene {
         Ok((Image { nx, ny, rgb: pv }, counts, block))
     }
 
+    /// Not in the reference: par_cast with `RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE` (see the header): the image exactly as
+    /// `par_cast` returns it, the frame filtered by the library's variance-driven non-local-means filter (strength `k`, search
+    /// radius `radius`, patch radius `patch`), and the block with its out-fields.  (Uncompiled, like the rest of this crate.)
+    pub fn par_cast_denoised(&mut self, nx: usize, ny: usize, ns: usize, k: f32, radius: u32, patch: u32, camera: &Camera,
+                             options: &CastOptions) -> Result<(Image, Image, sys::rtg_denoise)> {
+        let n = nx * ny;
+        let block_word = (6 * n + 1) & !1; // two planes, padding to 8 bytes, the block, then the output plane
+        let mut frame = vec![0f32; block_word + 16 + 3 * n];
+        let block = sys::rtg_denoise { k, radius, patch, ..Default::default() };
+        unsafe { ptr::write_unaligned(frame.as_mut_ptr().add(block_word) as *mut sys::rtg_denoise, block) };
+        let mut p = params(nx, ny, ns, options);
+        p.flags = sys::RTG_FLAG_SUM_SQUARES | sys::RTG_FLAG_DENOISE;
+        check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, frame.as_mut_ptr(), ptr::null_mut()) })?;
+        let block = unsafe { ptr::read_unaligned(frame.as_ptr().add(block_word) as *const sys::rtg_denoise) };
+        let denoised = frame[block_word + 16..].to_vec();
+        frame.truncate(3 * n);
+        Ok((Image { nx, ny, rgb: frame }, Image { nx, ny, rgb: denoised }, block))
+    }
+
     /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).
     /// After each slice `on_preview(n_done, &preview)` gets the frame resolved at `n_done` samples -- bit-identical to
     /// `par_cast(nx, ny, n_done, ..)` -- and returns `false` to stop early (time budget, cancel).  The preview at
