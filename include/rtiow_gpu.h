@@ -216,6 +216,62 @@ typedef struct rtg_denoise {
   uint32_t reserved[10]; /* out: 0                                                                                 */
 } rtg_denoise;
 
+#define RTG_FLAG_FEATURES 256u /* out ends with first-hit feature planes: albedo, normal, depth (below) */
+#define RTG_FEATURES_MAX_GRID 4u
+
+/* Feature planes (what a denoiser or compositor wants beside the colour).  RTG_FLAG_FEATURES needs no other flag and combines
+ * freely with PARTIAL, RESUME, SUM_SQUARES, SAMPLE_COUNTS, RETIRE, DENOISE and COUNTERS.  `out` then grows at its end by a
+ * 64-byte features block (rtg_features) and three float planes in the pixel layout of plane 0: albedo (nx * ny * 3 floats),
+ * normal (nx * ny * 3) and depth (nx * ny).  The block starts at the first even word (8-byte aligned) behind everything the
+ * call's other flags put in the frame: behind the float planes (word 3 * nx * ny, or 6 * nx * ny with RTG_FLAG_SUM_SQUARES), the
+ * count plane, the retire block (its word + 16) or, with RTG_FLAG_DENOISE, that flag's output plane (the denoise block's word
+ * + 16 + 3 * nx * ny).  The albedo plane starts 16 words behind the block, the normal plane 3 * nx * ny words behind that, the
+ * depth plane another 3 * nx * ny words on.  Compute the offsets in 64 bits.
+ * The planes are deterministic and do not depend on the frame's samples: with grid = g every pixel sends g * g primary rays
+ * through the centres of a g x g grid of its area, from the lens centre, at the middle of the exposure.  For pixel (x, row),
+ * y = ny - 1 - row, and the rays j = 0 .. g - 1 (outer), i = 0 .. g - 1 (inner), everything float32, every operation rounded on
+ * its own, no contraction:  su = (i + 0.5) / g;  sv = (j + 0.5) / g;  u = (x + su) / nx;  v = (y + sv) / ny;  origin =
+ * camera.origin;  direction = ((lower_left_corner + u * horizontal) + v * vertical) - origin (Camera::get_ray, camera.rs:52-63,
+ * with a zero lens offset);  time = exposure_start + 0.5 * (exposure_end - exposure_start).  Each ray is one hit_top (lib.rs:33)
+ * from params.t_near, its RNG keyed (params.seed, pixel = y * nx + x, sample 0) at event 1 -- rtg_debug_hit_top's stream for
+ * ray index y * nx + x, so media draw the same numbers.  A hit gives seven values: the albedo (Lambertian and Isotropic: the
+ * texture at the hit point; Metal: its albedo; Dielectric: (1, 1, 1); DiffuseLight: brightness * texture, what emitted()
+ * returns), the normal of the hit record and its t; a miss gives seven +0.  A plane holds per pixel the left fold of its values
+ * over the rays, from +0, divided by (float)(g * g).  rtiow-rust_amd/features.py subpixel_rays is the rays in numpy.
+ *   - Everything in front of the features block ends bit for bit as in the same call without the flag, with one exception:
+ *     under RTG_FLAG_DENOISE the output plane is the GUIDED filter's.  That filter is the one above with one more factor: for
+ *     a displacement, pixels p and q = p + delta, the feature values (a, n, z) of both, and the block's three sigmas,
+ *     xn = ((dn0^2 + dn1^2) + dn2^2) / (sigma_normal^2) with dn = n_p - n_q;  xa likewise from the albedo and sigma_albedo;
+ *     dz = z_p - z_q;  s = z_p + z_q;  xz = ((dz * dz) / (s * s + 1e-20)) / (sigma_depth^2);  x = xn;  x = xa > x ? xa : x;
+ *     x = xz > x ? xz : x;  u = 1 - x * 0.25;  u = u > 0 ? u : 0;  wf = (u * u) * (u * u);  wf = 1 when any of the fourteen
+ *     values is not finite;  w = wf < w ? wf : w.  rtiow-rust_amd/denoise.py nlm_guided is this in numpy; the output plane
+ *     equals it bit for bit on the feature planes the frame holds when the filter runs.
+ *   - compute = 1 traces the planes in this call, for every pixel the call owns (rank / tiles), whatever a count plane says;
+ *     pixels of other ranks stay untouched.  compute = 0 leaves the planes alone: they hold what an earlier call traced (a
+ *     progressive or adaptive loop computes them on its first slice only) or what the caller put there.  nranks > 1 is fine
+ *     without RTG_FLAG_DENOISE.
+ *   - RTG_ERR_INVALID, nothing written or enqueued: grid 0 or > RTG_FEATURES_MAX_GRID, compute > 1, reserved_in != 0 and, under
+ *     RTG_FLAG_DENOISE, a sigma that is NaN, infinite or <= 0 (without that flag the sigmas are not read).
+ *   - Every accepted call writes every out-field of the block and never its in-fields.
+ *   - rtg_par_cast uploads the block (and, with compute = 0 under RTG_FLAG_DENOISE, the feature planes), copies back the feature
+ *     planes when compute = 1, and always the block's out-fields.  rtg_par_cast_device reads the in-fields back on
+ *     `hip_stream` in the copy-and-wait of the denoise / retire / counts read-backs; a call that has none of those gains one
+ *     synchronisation, made before its first kernel.
+ *   - rtg_stats: the counters are those of the call without the flag (feature rays are not counted); kernel_ms also covers the
+ *     feature kernel.  rtg_par_cast_multi returns RTG_ERR_UNSUPPORTED and rtg_debug_samples RTG_ERR_INVALID, both writing
+ *     nothing. */
+typedef struct rtg_features {
+  uint32_t grid;        /* in:  g, 1 .. RTG_FEATURES_MAX_GRID: g * g feature rays per pixel                            */
+  uint32_t compute;     /* in:  1 = trace the planes in this call; 0 = the planes already hold them: left alone        */
+  float sigma_normal;   /* in:  read only with RTG_FLAG_DENOISE: finite and > 0 (large = that feature is off)          */
+  float sigma_albedo;   /* in:  likewise                                                                                */
+  float sigma_depth;    /* in:  likewise                                                                                */
+  uint32_t reserved_in; /* in:  must be 0                                                                               */
+  uint32_t traced;      /* out: owned pixels whose features this call wrote (0 when compute = 0)                        */
+  uint32_t missed;      /* out: of those, pixels none of whose rays hit anything                                        */
+  uint32_t reserved[8]; /* out: 0                                                                                       */
+} rtg_features;
+
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */

@@ -29,6 +29,8 @@ RETIRE_MAX_RADIUS = 8
 FLAG_DENOISE = 128       # after the slice, filter the frame: the framebuffer ends with a Denoise block and the output plane
 DENOISE_MAX_RADIUS = 8
 DENOISE_MAX_PATCH = 3
+FLAG_FEATURES = 256      # the framebuffer ends with a Features block and the first-hit albedo / normal / depth planes
+FEATURES_MAX_GRID = 4
 
 
 class Camera(C.Structure):
@@ -114,6 +116,62 @@ def denoise_frame_bytes(nx, ny, counts=False, retire=False):
     return denoise_block_offset(nx, ny, counts, retire) + C.sizeof(Denoise) + nx * ny * 3 * 4
 
 
+class Features(C.Structure):
+    """include/rtiow_gpu.h rtg_features: the block in front of the albedo / normal / depth planes of an RTG_FLAG_FEATURES frame
+    (64 bytes).  The caller sets grid / compute and, for the guided filter (RTG_FLAG_DENOISE in the same call), the three
+    sigmas; every accepted call writes the out-fields traced / missed."""
+    _fields_ = [("grid", C.c_uint32), ("compute", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("reserved_in", C.c_uint32), ("traced", C.c_uint32), ("missed", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+    OUT_FIELDS = ("traced", "missed")
+    OUT_OFFSET = 24   # bytes: the in-fields end here
+
+    def as_dict(self):
+        """The out-fields."""
+        return {k: getattr(self, k) for k in self.OUT_FIELDS}
+
+
+FEATURES_DEFAULTS = {"grid": 2, "compute": 1, "sigma_normal": 1.0, "sigma_albedo": 1.0, "sigma_depth": 1.0}
+
+
+def make_features(features=None, **fields):
+    """A Features with the in-fields set: from a Features (copied), a dict of grid / compute / sigma_normal / sigma_albedo /
+    sigma_depth, or True / None (FEATURES_DEFAULTS: a 2 x 2 grid, traced in the call; the sigmas DESIGN.md section 6 chose)."""
+    f = Features()
+    if isinstance(features, Features):
+        C.memmove(C.addressof(f), C.addressof(features), C.sizeof(Features))
+        return f
+    v = dict(FEATURES_DEFAULTS)
+    for src in (features if isinstance(features, dict) else {}, fields):
+        unknown = set(src) - set(v)
+        if unknown:
+            raise ValueError("features=: unknown key(s) %s (%s)" % (sorted(unknown), ", ".join(FEATURES_DEFAULTS)))
+        v.update(src)
+    f.grid, f.compute = int(v["grid"]), int(v["compute"])
+    f.sigma_normal, f.sigma_albedo, f.sigma_depth = float(v["sigma_normal"]), float(v["sigma_albedo"]), float(v["sigma_depth"])
+    return f
+
+
+def features_block_offset(nx, ny, squares=False, counts=False, retire=False, denoise=False):
+    """Byte offset of the Features block in an RTG_FLAG_FEATURES frame: the first even word behind everything the call's other
+    flags put in the frame -- the float planes (one, or two with squares), the count plane, the Retire block (implies counts
+    and squares) or the Denoise block and its output plane (implies squares)."""
+    n = nx * ny
+    if denoise:
+        end = denoise_block_offset(nx, ny, counts or retire, retire) // 4 + 16 + 3 * n
+    elif retire:
+        end = retire_block_offset(nx, ny) // 4 + 16
+    else:
+        end = ((6 if squares else 3) + (1 if counts else 0)) * n
+    return ((end + 1) & ~1) * 4
+
+
+def features_frame_bytes(nx, ny, squares=False, counts=False, retire=False, denoise=False):
+    """Bytes of an RTG_FLAG_FEATURES frame: everything the other flags put in it, the 64-byte Features block, the albedo,
+    normal and depth planes (7 floats per pixel)."""
+    return features_block_offset(nx, ny, squares, counts, retire, denoise) + C.sizeof(Features) + nx * ny * 7 * 4
+
+
 class Stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kernel_ms", C.c_float), ("samples", C.c_uint64),
                 ("aabb_tests", C.c_uint64), ("prim_tests", C.c_uint64), ("shaded_hits", C.c_uint64),
@@ -125,12 +183,13 @@ class Stats(C.Structure):
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
                 nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False,
-                denoise=False):
-    """`partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
+                denoise=False, features=False):
+    """`features`: RTG_FLAG_FEATURES, the features block and the albedo / normal / depth planes at the framebuffer's end.
+    `partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
     RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
     the count plane at the framebuffer's end; `retire`: RTG_FLAG_RETIRE, the retire block behind it; `denoise`:
     RTG_FLAG_DENOISE, the denoise block and the output plane at the framebuffer's end."""
-    flags |= FLAG_DENOISE if denoise else 0
+    flags |= (FLAG_DENOISE if denoise else 0) | (FLAG_FEATURES if features else 0)
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
     flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0)
     p = Params()
@@ -185,6 +244,12 @@ def _denoise_supported(be):
         raise ValueError("denoise=: %s (prefix %s) does not implement RTG_FLAG_DENOISE" % (be.path, be.prefix))
 
 
+def _features_supported(be):
+    """RTG_FLAG_FEATURES is the HIP library's (prefix rtg_): another library would ignore the flag and write no plane."""
+    if be.prefix != "rtg_":
+        raise ValueError("features=: %s (prefix %s) does not implement RTG_FLAG_FEATURES" % (be.path, be.prefix))
+
+
 def _counts_supported(be):
     """RTG_FLAG_SAMPLE_COUNTS is the HIP library's (prefix rtg_), like RTG_FLAG_SUM_SQUARES: another library would ignore the
     count plane and render every pixel to ns."""
@@ -228,6 +293,51 @@ class DenoiseFrame:
         self.denoised = self.buf[off // 4 + 16:off // 4 + 16 + 3 * n].reshape(ny, nx, 3)
         block = make_denoise(denoise)
         C.memmove(C.addressof(self.denoise), C.addressof(block), Denoise.OUT_OFFSET)
+
+
+class FeaturesFrame:
+    """One contiguous host framebuffer for RTG_FLAG_FEATURES, as include/rtiow_gpu.h lays it out, with the views of its
+    siblings: `planes` ([ny, nx, 3], or [2, ny, nx, 3] with squares), `counts` (uint32 [ny, nx]) with counts=True, `retire`
+    with retire=True (implies counts and squares), `denoise` / `denoised` with denoise= (a Denoise, a dict or True; implies
+    squares) -- each None when the frame has no such part -- then `features` (the Features block) and the planes `albedo`,
+    `normal` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]).  All are views of `buf`;
+    par_cast(out=frame, features=True) renders in place."""
+
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
+        has_dn = denoise is not None and denoise is not False
+        counts, squares = bool(counts or retire), bool(squares or retire or has_dn)
+        n = nx * ny
+        self.nx, self.ny, self.squares = nx, ny, squares
+        off = features_block_offset(nx, ny, squares, counts, retire, has_dn)
+        self.buf = np.zeros(features_frame_bytes(nx, ny, squares, counts, retire, has_dn) // 4, dtype=np.float32)
+        n_f = (6 if squares else 3) * n
+        self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
+        self.counts = self.buf[n_f:n_f + n].view(np.uint32).reshape(ny, nx) if counts else None
+        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
+        self.denoise = self.denoised = None
+        if has_dn:
+            d_off = denoise_block_offset(nx, ny, counts, retire)
+            self.denoise = Denoise.from_buffer(self.buf, d_off)
+            self.denoised = self.buf[d_off // 4 + 16:d_off // 4 + 16 + 3 * n].reshape(ny, nx, 3)
+            block = make_denoise(None if denoise is True else denoise)
+            C.memmove(C.addressof(self.denoise), C.addressof(block), Denoise.OUT_OFFSET)
+        self.features = Features.from_buffer(self.buf, off)
+        w = off // 4 + 16
+        self.albedo = self.buf[w:w + 3 * n].reshape(ny, nx, 3)
+        self.normal = self.buf[w + 3 * n:w + 6 * n].reshape(ny, nx, 3)
+        self.depth = self.buf[w + 6 * n:w + 7 * n].reshape(ny, nx)
+        block = make_features(None if features is True else features)
+        C.memmove(C.addressof(self.features), C.addressof(block), Features.OUT_OFFSET)
+
+    def flags(self):
+        """make_params keywords of the parts the frame has."""
+        return {"squares": self.squares, "counts": self.counts is not None, "retire": self.retire is not None,
+                "denoise": self.denoise is not None, "features": True}
+
+
+def features_frame(nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
+    """A zeroed FeaturesFrame whose blocks hold the in-fields of `features` (make_features) and `denoise` (make_denoise)."""
+    return FeaturesFrame(nx, ny, squares, counts, retire, denoise, features)
 
 
 def denoise_frame(nx, ny, counts=False, retire=False, denoise=None):
@@ -609,7 +719,7 @@ class Scene:
         return args
 
     def par_cast(self, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, threads=0, counts=None, counters=None,
-                 retire=None, denoise=None, **kw):
+                 retire=None, denoise=None, features=None, **kw):
         """par_cast, lib.rs:363.  Returns float32 [ny, nx, 3], row 0 = top, linear radiance.
         One slice of a progressive frame: partial=True leaves the running sum in `out`; resume=True, sample_begin=k
         continues the running sum of samples [0, k) that `out` holds (include/rtiow_gpu.h).
@@ -626,7 +736,19 @@ class Scene:
         output plane).  denoise: a Denoise or a dict of k / radius / patch (True: the defaults).  out= a DenoiseFrame is
         rendered in place and returned (denoise=True: its block as it stands; its own counts / retire views are used); with
         any other out / counts / retire a new frame carries copies of them, and they are written back as without denoise=.
+        features= (RTG_FLAG_FEATURES): the call also traces the first-hit albedo, normal and depth planes and returns a
+        FeaturesFrame -- the views above where the frame has them, plus `features` (the block, out-fields filled), `albedo`,
+        `normal` and `depth`.  features: a Features or a dict of grid / compute / sigma_* (True: FEATURES_DEFAULTS).  With
+        denoise= the filter is the guided one (denoise.nlm_guided) over the frame's feature planes.  out= a FeaturesFrame is
+        rendered in place and returned (features=True / denoise=True: its blocks as they stand); anything else is copied into
+        a new frame and written back as without features=.
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
+        if features is not None and features is not False:
+            if denoise is not None and denoise is not False and not kw.get("squares"):
+                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
+            _features_supported(self.be)
+            return self._par_cast_features(camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise,
+                                           features, kw)
         if denoise is not None and denoise is not False:
             if not kw.get("squares"):
                 raise ValueError("denoise= needs squares=True (the filter reads both planes)")
@@ -705,8 +827,63 @@ class Scene:
                 C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
         return (f, st.as_dict()) if stats else f
 
+    def _par_cast_features(self, camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, features, kw):
+        has_dn = denoise is not None and denoise is not False
+        in_place = isinstance(out, FeaturesFrame)
+        if in_place:
+            f = out
+            if (f.nx, f.ny) != (nx, ny):
+                raise ValueError("out= is a FeaturesFrame of another size")
+            if counts is not None or retire is not None:
+                raise ValueError("out= a FeaturesFrame brings its own counts / retire views")
+            if has_dn != (f.denoise is not None) or bool(kw.get("squares")) != f.squares:
+                raise ValueError("out= a FeaturesFrame: squares= / denoise= must say what the frame holds")
+            if has_dn and denoise is not True:
+                block = make_denoise(denoise)
+                C.memmove(C.addressof(f.denoise), C.addressof(block), Denoise.OUT_OFFSET)
+            if features is not True:
+                block = make_features(features)
+                C.memmove(C.addressof(f.features), C.addressof(block), Features.OUT_OFFSET)
+        else:
+            if retire is not None and (counts is None or not kw.get("squares") or not isinstance(counts, np.ndarray)):
+                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
+            if isinstance(out, (DenoiseFrame, CountsFrame)):
+                raise ValueError("features=: out= must be a FeaturesFrame or an array")
+            f = FeaturesFrame(nx, ny, kw.get("squares"), counts is not None, retire is not None, denoise if has_dn else None,
+                              None if features is True else features)
+            if out is not None:
+                f.planes[...] = _host_frame(out, nx, ny, kw)
+            elif _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
+            if counts is not None:
+                counts = np.asarray(counts)
+                if counts.shape != (ny, nx):
+                    raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+                f.counts[...] = counts
+            if retire is not None:
+                C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
+        for part, check in ((f.squares, _squares_supported), (f.counts is not None, _counts_supported),
+                            (f.retire is not None, _retire_supported), (f.denoise is not None, _denoise_supported)):
+            if part:
+                check(self.be)
+        if counters is None:
+            counters = stats
+        kw = {k: v for k, v in kw.items() if k != "squares"}
+        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, **f.flags(), **kw)
+        st = Stats()
+        st.struct_size = C.sizeof(Stats)
+        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), f.buf.ctypes.data_as(c_f32p), C.byref(st)], threads)
+        self.be.check(self.be._par_cast(*args))
+        if not in_place:
+            if out is not None:
+                out[...] = f.planes
+            if retire is not None:
+                counts[...] = f.counts
+                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
+        return (f, st.as_dict()) if stats else f
+
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None, counts=None, retire=None, denoise=None):
+                        resume=None, squares=None, counts=None, retire=None, denoise=None, features=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
         With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
         counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
@@ -717,8 +894,13 @@ class Scene:
         then holds retire_frame_bytes(nx, ny).
         denoise= (RTG_FLAG_DENOISE): True, the flag alone (the caller has written the block's in-fields on the device); a
         Denoise, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
-        `d_out_ptr` then holds denoise_frame_bytes(nx, ny, counts, retire) for the flags the call ends up with."""
-        dblock = None   # (every refusal first: a refused call has written nothing to the caller's frame)
+        `d_out_ptr` then holds denoise_frame_bytes(nx, ny, counts, retire) for the flags the call ends up with.
+        features= (RTG_FLAG_FEATURES): True, the flag alone (the caller has written the block's in-fields on the device); a
+        Features, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
+        `d_out_ptr` then holds features_frame_bytes(nx, ny, squares, counts, retire, denoise) for the flags the call ends up with."""
+        dblock = fblock = None   # (every refusal first: a refused call has written nothing to the caller's frame)
+        if features is not None and features is not False:
+            _features_supported(self.be)
         if denoise is not None and denoise is not False:
             _denoise_supported(self.be)
         if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
@@ -735,6 +917,14 @@ class Scene:
                 dblock = denoise
                 self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
                 denoise = True
+        if features is not None and features is not False:
+            has = [bool(params.flags & bit) if on is None else on is not False
+                   for on, bit in ((squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS), (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE))]
+            f_off = features_block_offset(params.nx, params.ny, *has)
+            if features is not True:
+                fblock = features
+                self._block_copy(params.nx, params.ny, d_out_ptr, fblock, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
+                features = True
         block = None
         if retire is not None and retire is not False:
             if retire is not True:
@@ -746,13 +936,13 @@ class Scene:
             self._upload_counts(params.nx, params.ny, sq, counts, d_out_ptr, stream)
             counts = True
         if (sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None
-                or retire is not None or denoise is not None):
+                or retire is not None or denoise is not None or features is not None):
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
             for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS),
-                            (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE)):
+                            (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE), (features, FLAG_FEATURES)):
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
@@ -764,6 +954,8 @@ class Scene:
             self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=False)
         if dblock is not None:
             self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=False, offset=d_off, nbytes=C.sizeof(Denoise))
+        if fblock is not None:
+            self._block_copy(params.nx, params.ny, d_out_ptr, fblock, stream, to_device=False, offset=f_off, nbytes=C.sizeof(Features))
         return st.as_dict() if want_stats else None
 
     def _block_copy(self, nx, ny, d_out_ptr, block, stream, to_device, offset=None, nbytes=None):
@@ -800,7 +992,7 @@ class Scene:
             raise RtError(ERR_DEVICE, "hipMemcpyAsync(count plane) failed: %d" % rc)
 
     def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
-                 stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, **kw):
+                 stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, features=None, **kw):
         """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS).  Every slice renders `step` more samples of the
         pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the slice that ends
         at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest per-channel standard
@@ -821,28 +1013,47 @@ class Scene:
         frame, and the loop yields the filtered frame as a fourth item.  Host frames: `out`, when given, is a
         DenoiseFrame(nx, ny, counts=True); the item is a copy of its output plane.  Device frames: `out` holds
         denoise_frame_bytes(nx, ny, counts=True, retire=True) and `denoised` is a device buffer of nx * ny * 3 floats, rewritten
-        every slice by a device-to-device copy of the output plane."""
+        every slice by a device-to-device copy of the output plane.
+        features= (a Features, a dict of grid / sigma_*, or True; RTG_FLAG_FEATURES): the first slice's call also traces the
+        feature planes, the later ones pass compute = 0; with denoise= the filter is the guided one.  The loop yields one more
+        item at the end of its tuple.  Host frames: `out`, when given, is a FeaturesFrame(nx, ny, counts=True, squares=True,
+        denoise=...); the item is that frame (views `albedo`, `normal`, `depth`).  Device frames: `out` holds
+        features_frame_bytes(nx, ny, True, True, True, denoise) and the item is the byte offset of the features block in it
+        (the planes start 64 bytes behind it)."""
         if step < 1:
             raise ValueError("step must be >= 1")
         _squares_supported(self.be)
         _counts_supported(self.be)
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
+        if features is not None and features is not False:
+            _features_supported(self.be)
+            features = make_features(None if features is True else features)
+        else:
+            features = None
         if denoise is not None and denoise is not False:
             _denoise_supported(self.be)
             denoise = make_denoise(None if denoise is True else denoise)
         else:
             denoise = None
-        if out is not None and not isinstance(out, (CountsFrame, DenoiseFrame)):
+        if out is not None and not isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame)):
             _retire_supported(self.be)
             if preview is None:
                 raise ValueError("a device frame needs a device preview buffer (preview=)")
             if denoise is not None and denoised is None:
                 raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
-                                             radius, preview, stream, kw, denoise, denoised)
+                                             radius, preview, stream, kw, denoise, denoised, features)
             return
-        if denoise is not None:
+        if features is not None:
+            f = FeaturesFrame(nx, ny, squares=True, counts=True, denoise=denoise) if out is None else out
+            if (not isinstance(f, FeaturesFrame) or f.counts is None or f.retire is not None or not f.squares
+                    or (f.denoise is None) != (denoise is None)):
+                raise ValueError("features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)")
+            C.memmove(C.addressof(f.features), C.addressof(features), Features.OUT_OFFSET)
+            if denoise is not None:
+                C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+        elif denoise is not None:
             f = DenoiseFrame(nx, ny, counts=True) if out is None else out
             if not isinstance(f, DenoiseFrame) or f.counts is None or f.retire is not None:
                 raise ValueError("denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)")
@@ -851,6 +1062,7 @@ class Scene:
             f = CountsFrame(nx, ny, squares=True) if out is None else out
             if not isinstance(f, CountsFrame):
                 raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
+        more = () if features is None else (f,)
         if f.planes.shape != (2, ny, nx, 3):
             raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
         f.counts[...] = ns
@@ -859,7 +1071,12 @@ class Scene:
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            if denoise is not None:
+            if features is not None:
+                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f, denoise=True if denoise is not None else None,
+                                      features=True, sample_begin=done, resume=True, partial=True, squares=True, stats=True,
+                                      counters=False, **kw)
+                f.features.compute = 0   # (the planes are traced once)
+            elif denoise is not None:
                 _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f, denoise=True, sample_begin=done, resume=True,
                                       partial=True, squares=True, stats=True, counters=False, **kw)
             else:
@@ -881,16 +1098,16 @@ class Scene:
             pv.counts[...] = held
             self.par_cast(camera, nx, ny, done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
             if denoise is not None:
-                yield held, pv.planes, se, f.denoised.copy()
+                yield (held, pv.planes, se, f.denoised.copy()) + more
             else:
-                yield held, pv.planes, se
+                yield (held, pv.planes, se) + more
             if not active.any():
                 return
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
-                         stream, kw, denoise=None, denoised=None):
+                         stream, kw, denoise=None, denoised=None, features=None):
         hip = _hip_runtime()
         d_out, d_pv = _device_ptr(out), _device_ptr(preview)
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
@@ -908,13 +1125,22 @@ class Scene:
         if denoise is not None:   # (likewise: its in-fields once; the output plane sits 64 bytes behind the block)
             d_off = denoise_block_offset(nx, ny, True, True)
             self._block_copy(nx, ny, d_out, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
+        more = ()
+        if features is not None:   # (its in-fields before the first slice, and once more, with compute = 0, behind it)
+            f_off = features_block_offset(nx, ny, True, True, True, denoise is not None)
+            self._block_copy(nx, ny, d_out, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
+            more = (f_off,)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
             st = self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
                                                           squares=True, counts=True, retire=True, denoise=denoise is not None,
-                                                          **kw), d_out, hs, want_stats=stats is not None)
+                                                          features=features is not None, **kw), d_out, hs,
+                                      want_stats=stats is not None)
+            if features is not None and features.compute:
+                features.compute = 0
+                self._block_copy(nx, ny, d_out, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
             if denoise is not None:
                 ok(hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_out + d_off + C.sizeof(Denoise)), plane * 3 * 4,
                                       3, hs), "hipMemcpyAsync(denoised)")
@@ -929,16 +1155,16 @@ class Scene:
             self._block_copy(nx, ny, d_out, block, stream, to_device=False)
             info = block.as_dict()
             if denoise is not None:
-                yield done, preview, info, denoised
+                yield (done, preview, info, denoised) + more
             else:
-                yield done, preview, info
+                yield (done, preview, info) + more
             if info["active"] == 0:
                 return
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
     def progressive(self, camera, nx, ny, ns, step, seed=0xDEADBEEF, budget_s=None, out=None, preview=None, stream=None,
-                    squares=False, target_rmse=None, denoise=None, denoised=None, **kw):
+                    squares=False, target_rmse=None, denoise=None, denoised=None, features=None, **kw):
         """Render a frame `step` samples at a time (include/rtiow_gpu.h progressive rendering).  Yields (n_done, preview)
         after each slice: the preview is bit-identical to par_cast(ns = n_done), and the one at n_done == ns is the final
         image, bit-identical to par_cast(ns).  Stops at ns, or after the first slice that ends past `budget_s` seconds.
@@ -957,9 +1183,19 @@ class Scene:
         filters the frame (denoise.nlm of the running sums), and the loop yields (n_done, preview, stderr, denoised).  Host
         frames: denoised is a new float32 [ny, nx, 3] array per slice.  Device frames: `out` holds denoise_frame_bytes(nx, ny)
         and `denoised` is a device buffer of nx * ny * 3 floats, rewritten every slice by a device-to-device copy of the
-        output plane, and yielded as the fourth item."""
+        output plane, and yielded as the fourth item.
+        features= (a Features, a dict of grid / sigma_*, or True; RTG_FLAG_FEATURES): the first slice's call also traces the
+        feature planes, the later ones pass compute = 0; with denoise= the filter is the guided one (denoise.nlm_guided).  The
+        loop yields one more item at the end of its tuple.  Host frames: the FeaturesFrame the slices render into (views
+        `albedo`, `normal`, `depth`).  Device frames: `out` holds features_frame_bytes(nx, ny, squares, False, False, denoise)
+        and the item is the byte offset of the features block in it (the planes start 64 bytes behind it)."""
         if step < 1:
             raise ValueError("step must be >= 1")
+        if features is not None and features is not False:
+            _features_supported(self.be)
+            features = make_features(None if features is True else features)
+        else:
+            features = None
         if denoise is not None and denoise is not False:
             _squares_supported(self.be)
             _denoise_supported(self.be)
@@ -977,20 +1213,29 @@ class Scene:
             if denoise is not None and denoised is None:
                 raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, squares, kw,
-                                                denoise, denoised)
+                                                denoise, denoised, features)
             return
         shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
         acc = np.zeros(shape, dtype=np.float32) if out is None else out
         frame = None
-        if denoise is not None:   # the slices render into a DenoiseFrame; a caller's `out` is kept up to date beside it
+        if features is not None:   # the slices render into a FeaturesFrame; a caller's `out` is kept up to date beside it
+            frame = FeaturesFrame(nx, ny, squares, denoise=denoise, features=features)
+            frame.planes[...] = acc
+        elif denoise is not None:   # ... or into a DenoiseFrame
             frame = DenoiseFrame(nx, ny, denoise=denoise)
             frame.planes[...] = acc
+        more = () if features is None else (frame,)
         sums = acc[0] if squares else acc
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
-            if frame is not None:
+            if features is not None:
+                self.par_cast(camera, nx, ny, end, seed=seed, out=frame, denoise=True if denoise is not None else None, features=True,
+                              sample_begin=done, resume=True, partial=True, squares=squares, **kw)
+                frame.features.compute = 0   # (the planes are traced once)
+                acc[...] = frame.planes
+            elif frame is not None:
                 self.par_cast(camera, nx, ny, end, seed=seed, out=frame, denoise=True, sample_begin=done, resume=True, partial=True,
                               squares=True, **kw)
                 acc[...] = frame.planes
@@ -1001,31 +1246,40 @@ class Scene:
             self.par_cast(camera, nx, ny, done, seed=seed, out=pv, sample_begin=done, resume=True, **kw)
             if squares:
                 se = noise.standard_error(acc[0], acc[1], done)
-                if frame is not None:
-                    yield done, pv, se, frame.denoised.copy()
+                if denoise is not None:
+                    yield (done, pv, se, frame.denoised.copy()) + more
                 else:
-                    yield done, pv, se
+                    yield (done, pv, se) + more
                 if target_rmse is not None and float(np.sqrt(np.mean(se * se))) <= target_rmse:
                     return
             else:
-                yield done, pv
+                yield (done, pv) + more
             if budget_s is not None and time.perf_counter() - t0 >= budget_s:
                 return
 
     def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw, denoise=None,
-                            denoised=None):
+                            denoised=None, features=None):
         hip = _hip_runtime()
         d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
         hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
         if denoise is not None:   # the block's in-fields are written once (the library never writes them)
             d_off = denoise_block_offset(nx, ny)
             self._block_copy(nx, ny, acc, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
+        more = ()
+        if features is not None:   # (its in-fields before the first slice, and once more, with compute = 0, behind it)
+            f_off = features_block_offset(nx, ny, squares, False, False, denoise is not None)
+            self._block_copy(nx, ny, acc, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
+            more = (f_off,)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
             self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
-                                                     squares=squares, denoise=denoise is not None, **kw), d_acc, hs)
+                                                     squares=squares, denoise=denoise is not None, features=features is not None,
+                                                     **kw), d_acc, hs)
+            if features is not None and features.compute:
+                features.compute = 0
+                self._block_copy(nx, ny, acc, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
             done = end
             if denoise is not None:
                 rc = hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_acc.value + d_off + C.sizeof(Denoise)),
@@ -1037,9 +1291,9 @@ class Scene:
                 raise RtError(ERR_DEVICE, "hipMemcpyAsync(preview) failed: %d" % rc)
             self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, **kw), d_preview, hs)
             if denoise is not None:
-                yield done, preview, acc, denoised
+                yield (done, preview, acc, denoised) + more
             else:
-                yield (done, preview, acc) if squares else (done, preview)
+                yield ((done, preview, acc) if squares else (done, preview)) + more
             if budget_s is not None:
                 if hip.hipStreamSynchronize(hs) != 0:
                     raise RtError(ERR_DEVICE, "hipStreamSynchronize failed")

@@ -10,6 +10,10 @@
 // Every float operation is a single rounded f32 operation (the build has -ffp-contract=off and the correctly rounded divide),
 // in the order denoise.py states; zero-weight neighbours are skipped (every accumulator starts at +0 and never becomes -0, so
 // adding their +-0 products changes nothing).  All stores are plain stores.
+// With RTG_FLAG_FEATURES the filter is GUIDED (denoise.py nlm_guided): a fourth kernel, guide, packs the frame's albedo, normal
+// and depth planes into a second 32-byte record per pixel, and the filter's guided instantiations cap every colour weight by
+// the feature weight of the pair -- reading the neighbour's record through the caches (GUIDED = 1) or from an LDS copy of the
+// tile plus a halo of R (GUIDED = 2).  A pair whose colour weight is +0 skips the feature weight: min(wf, +0) is +0 for every wf.
 #pragma once
 #include "rt_pool.h"
 
@@ -37,10 +41,18 @@ struct DenoiseBufs {
   uint32_t* blk_u32;       // per prepare block: filtered, passed
 };
 
-// bytes of dynamic LDS the filter kernel needs
-static inline size_t denoise_lds_bytes(uint32_t radius, uint32_t patch) {
+// The guided filter's own arguments: the feature records ((a0, a1, a2, z) (n0, n1, n2, all seven finite ? word 1 : 0) per pixel)
+// and the three sigmas of the rtg_features block
+struct DenoiseGuide {
+  const float4* frec;
+  float sigma_normal, sigma_albedo, sigma_depth;
+};
+
+// bytes of dynamic LDS the filter kernel needs; guide_lds: the guided filter's LDS copy of the feature records (GUIDED = 2)
+static inline size_t denoise_lds_bytes(uint32_t radius, uint32_t patch, bool guide_lds = false) {
   const size_t h = radius + patch;
-  return (DN_TW + 2 * h) * (DN_TH + 2 * h) * 32u + (DN_TW + 2 * patch) * (DN_TH + 2 * patch) * 8u + DN_TW * (DN_TH + 2 * patch) * 8u;
+  const size_t guide = guide_lds ? (DN_TW + 2 * radius) * (DN_TH + 2 * radius) * 32u : 0u;
+  return (DN_TW + 2 * h) * (DN_TH + 2 * h) * 32u + (DN_TW + 2 * patch) * (DN_TH + 2 * patch) * 8u + DN_TW * (DN_TH + 2 * patch) * 8u + guide;
 }
 
 RT_DEV bool dn_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
@@ -89,7 +101,38 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(uint32_t n_pix, De
   }
 }
 
-__global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32_t ny, DenoiseArgs a, DenoiseBufs b) {
+// RTG_FLAG_DENOISE | RTG_FLAG_FEATURES: the feature records of the guided filter from the frame's three feature planes
+__global__ __launch_bounds__(256) void denoise_guide_kernel(uint32_t n_pix, const float* albedo, const float* normal, const float* depth, float4* frec) {
+  const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_pix) return;
+  const float* al = albedo + 3ull * p;
+  const float* nn = normal + 3ull * p;
+  const float z = depth[p];
+  const bool fin = dn_finite(al[0]) && dn_finite(al[1]) && dn_finite(al[2]) && dn_finite(nn[0]) && dn_finite(nn[1]) && dn_finite(nn[2]) && dn_finite(z);
+  frec[2ull * p] = make_float4(al[0], al[1], al[2], z);
+  frec[2ull * p + 1u] = make_float4(nn[0], nn[1], nn[2], __uint_as_float(fin ? 1u : 0u));
+}
+
+// the feature weight of a pair (denoise.py nlm_guided): pA / pB and qA / qB are the two pixels' feature records
+RT_DEV float dn_feature_weight(float4 pA, float4 pB, float4 qA, float4 qB, float sn2, float sa2, float sz2) {
+  if (__float_as_uint(pB.w) == 0u || __float_as_uint(qB.w) == 0u) return 1.f;
+  const float dn0 = pB.x - qB.x, dn1 = pB.y - qB.y, dn2 = pB.z - qB.z;
+  const float da0 = pA.x - qA.x, da1 = pA.y - qA.y, da2 = pA.z - qA.z;
+  const float xn = ((dn0 * dn0 + dn1 * dn1) + dn2 * dn2) / sn2;
+  const float xa = ((da0 * da0 + da1 * da1) + da2 * da2) / sa2;
+  const float dz = pA.w - qA.w, s = pA.w + qA.w;
+  const float xz = ((dz * dz) / (s * s + 1e-20f)) / sz2;
+  float x = xn;
+  x = xa > x ? xa : x;
+  x = xz > x ? xz : x;
+  float u = 1.f - x * 0.25f;
+  u = u > 0.f ? u : 0.f;
+  return (u * u) * (u * u);
+}
+
+// GUIDED: 0 = the colour-only filter; 1 / 2 = the guided filter, the neighbours' feature records read through the caches / from LDS
+template <int GUIDED>
+__global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32_t ny, DenoiseArgs a, DenoiseBufs b, DenoiseGuide gd) {
   extern __shared__ float4 dn_lds[];
   const int R = (int)a.radius, F = (int)a.patch, H = R + F;
   const int WR = (int)DN_TW + 2 * H, HR = (int)DN_TH + 2 * H;  // the staged records: tile + halo of R + F
@@ -111,6 +154,21 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
     }
     recA[i] = A, recB[i] = B;
   }
+  // GUIDED = 2: the feature records of the tile plus a halo of R, behind the row folds
+  const int WG = (int)DN_TW + 2 * R, HG = (int)DN_TH + 2 * R;
+  float4* fA = reinterpret_cast<float4*>(rr + (int)DN_TW * HA);
+  float4* fB = fA + WG * HG;
+  if (GUIDED == 2) {
+    for (int i = tid; i < WG * HG; i += (int)DN_THREADS) {
+      const long long gx = tx0 + (i % WG) - R, gy = ty0 + (i / WG) - R;
+      float4 A = zero, B = zero;
+      if (gx >= 0 && gx < (long long)nx && gy >= 0 && gy < (long long)ny) {
+        const size_t p = (size_t)gy * nx + (size_t)gx;
+        A = gd.frec[2ull * p], B = gd.frec[2ull * p + 1u];
+      }
+      fA[i] = A, fB[i] = B;
+    }
+  }
   // this thread's pd elements (index into the records, -1: none) and row folds
   int pd_at[DN_PD_ITER];
   for (uint32_t j = 0; j < DN_PD_ITER; j++) {
@@ -126,6 +184,22 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
   for (int j = 0; j < 2; j++) {
     at[j] = (y0 + 8 * j + H) * WR + x + H;
     ok[j] = __float_as_uint(recA[at[j]].w) != 0u;  // valid (pixels outside the image are not)
+  }
+  // guided: this thread's two feature records, where the neighbours' are (GUIDED = 1: in the frame; 2: in LDS), the sigmas squared
+  long long gat[2] = {0, 0};
+  float4 pfA[2] = {zero, zero}, pfB[2] = {zero, zero};
+  const float sn2 = gd.sigma_normal * gd.sigma_normal, sa2 = gd.sigma_albedo * gd.sigma_albedo, sz2 = gd.sigma_depth * gd.sigma_depth;
+  if (GUIDED != 0) {
+    for (int j = 0; j < 2; j++) {
+      if (!ok[j]) continue;  // (valid: inside the image)
+      if (GUIDED == 1) {
+        gat[j] = (ty0 + y0 + 8 * j) * (long long)nx + (tx0 + x);
+        pfA[j] = gd.frec[2ull * (size_t)gat[j]], pfB[j] = gd.frec[2ull * (size_t)gat[j] + 1u];
+      } else {
+        gat[j] = (y0 + 8 * j + R) * WG + x + R;
+        pfA[j] = fA[gat[j]], pfB[j] = fB[gat[j]];
+      }
+    }
   }
   const float k2 = a.k * a.k, eps = 1e-10f;
   for (int dy = -R; dy <= R; dy++)
@@ -181,7 +255,18 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
         float u = 1.f - xx * 0.25f;
         u = u > 0.f ? u : 0.f;
         const float u2 = u * u;
-        const float w = u2 * u2;
+        float w = u2 * u2;
+        if (GUIDED != 0 && w > 0.f) {  // (q is valid: inside the image)
+          float4 qfA, qfB;
+          if (GUIDED == 1) {
+            const size_t q = (size_t)(gat[j] + (long long)dy * (long long)nx + dx);
+            qfA = gd.frec[2ull * q], qfB = gd.frec[2ull * q + 1u];
+          } else {
+            qfA = fA[gat[j] + dy * WG + dx], qfB = fB[gat[j] + dy * WG + dx];
+          }
+          const float wf = dn_feature_weight(pfA[j], pfB[j], qfA, qfB, sn2, sa2, sz2);
+          w = wf < w ? wf : w;
+        }
         acc[j][0] = acc[j][0] + w * qA.x;
         acc[j][1] = acc[j][1] + w * qA.y;
         acc[j][2] = acc[j][2] + w * qA.z;

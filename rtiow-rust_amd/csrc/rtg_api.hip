@@ -22,6 +22,7 @@
 #include "rt_pool.h"
 #include "rt_retire.h"
 #include "rt_denoise.h"
+#include "rt_features.h"
 #include "rt_pool_full.h"
 #include "rt_sync_full.h"
 #include "rt_pool2.h"
@@ -90,6 +91,9 @@ struct LaunchCtx {
   void* d_denoise = nullptr;    // RTG_FLAG_DENOISE: the per-pixel (m, v, valid) records and the prepare kernel's per-block counts (rt_denoise.h)
   size_t denoise_bytes = 0;
   rtg_denoise denoise_in{};     // ... the block's in-fields of a call without a count plane, read back before its first kernel
+  uint32_t* d_features = nullptr;  // RTG_FLAG_FEATURES: the feature kernel's per-block counts (rt_features.h)
+  size_t features_bytes = 0;
+  rtg_features features_in{};   // ... the block's in-fields of a call without a count plane, read back before its first kernel
 };
 
 struct rtg_scene {
@@ -147,6 +151,7 @@ struct rtg_scene {
   DevScene dev2{};                          // lo / hi = the second program (buffers[9], [10]); materials, textures, Perlin tables shared
   const P2Table* d_p2 = nullptr;            // buffers[11]
   Pool2Tuning pool2_tune{24, 48, 40, 4, 8, 24, 2};  // refill_min, box_leave, park_max, t_sphere, t_prism, t_list, t_push
+  int guide_lds = 0;                       // guided filter (rt_denoise.h GUIDED): 1 = the neighbours' feature records from an LDS copy, 0 = through the caches
   int small_frames = 1;                    // rtg_launch.inc pool_geometry: frames smaller than the chip get small workgroups and reservations
   LaunchCtx ctx[RTG_MAX_FRAMES];           // frames in flight
   int n_ctx = 1, next_ctx = 0;
@@ -166,11 +171,13 @@ static void ctx_free_buffers(LaunchCtx* c) {
   if (c->d_compact) (void)hipFree(c->d_compact);
   if (c->d_retire) (void)hipFree(c->d_retire);
   if (c->d_denoise) (void)hipFree(c->d_denoise);
+  if (c->d_features) (void)hipFree(c->d_features);
   c->d_scratch = nullptr, c->scratch_bytes = 0, c->d_slots = nullptr, c->slots_bytes = 0;
   c->d_stack = nullptr, c->stack_bytes = 0, c->d_lpt = nullptr, c->lpt_bytes = 0;
   c->d_list = nullptr, c->list_bytes = 0, c->d_compact = nullptr, c->compact_bytes = 0;
   c->d_retire = nullptr, c->retire_bytes = 0;
   c->d_denoise = nullptr, c->denoise_bytes = 0;
+  c->d_features = nullptr, c->features_bytes = 0;
 }
 
 // Take the next launch context of the ring: create its small buffers on first use, wait for the frame that used it last.
@@ -210,6 +217,8 @@ struct SampleSlice {
   ListConsts list{};       // ... and where the list, its inverse and the count plane are
   bool retire = false;  // RTG_FLAG_RETIRE: the framebuffer ends with an rtg_retire block; the retire step runs before the division
   bool denoise = false; // RTG_FLAG_DENOISE: the framebuffer ends with an rtg_denoise block and the output plane; the filter runs before the division
+  bool features = false; // RTG_FLAG_FEATURES: the framebuffer ends with an rtg_features block and the albedo / normal / depth planes
+  bool features_done = false;  // ... set by the launcher once the feature pass of the call is enqueued
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -220,6 +229,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_SAMPLE_COUNTS) sl.counts = true;
   if (p->flags & RTG_FLAG_RETIRE) sl.retire = true;
   if (p->flags & RTG_FLAG_DENOISE) sl.denoise = true;
+  if (p->flags & RTG_FLAG_FEATURES) sl.features = true;
   return sl;
 }
 
@@ -246,6 +256,25 @@ static const char* denoise_refusal(const rtg_denoise& r, uint32_t nranks) {
   if (!(r.k > 0.f) || !std::isfinite(r.k)) return "RTG_FLAG_DENOISE: k is NaN, infinite or <= 0";
   if (r.reserved_in != 0u) return "RTG_FLAG_DENOISE: reserved_in != 0";
   if (nranks > 1u) return "RTG_FLAG_DENOISE needs nranks = 1 (the neighbours live on other ranks)";
+  return nullptr;
+}
+
+// RTG_FLAG_FEATURES: the features block's word offset in the framebuffer -- the first even word behind everything the other
+// flags put there: the float planes, the count plane, the retire block or the denoise output plane -- the albedo plane 16 words
+// behind it, then the normal and the depth plane; and why the block's in-fields are refused (nullptr: accepted)
+static uint64_t features_block_word(uint32_t nx, uint32_t ny, const SampleSlice& sl) {
+  const uint64_t n = (uint64_t)nx * ny;
+  uint64_t end = (sl.squares ? 6u : 3u) * n + (sl.counts ? n : 0u);
+  if (sl.retire) end = retire_block_word(nx, ny) + 16u;
+  if (sl.denoise) end = denoise_block_word(nx, ny, sl.counts, sl.retire) + 16u + 3u * n;
+  return (end + 1u) & ~1ull;
+}
+static const char* features_refusal(const rtg_features& r, bool denoise) {
+  if (r.grid == 0u || r.grid > RTG_FEATURES_MAX_GRID) return "RTG_FLAG_FEATURES: grid is 0 or > RTG_FEATURES_MAX_GRID";
+  if (r.compute > 1u) return "RTG_FLAG_FEATURES: compute > 1";
+  if (r.reserved_in != 0u) return "RTG_FLAG_FEATURES: reserved_in != 0";
+  for (float sg : {r.sigma_normal, r.sigma_albedo, r.sigma_depth})
+    if (denoise && (!(sg > 0.f) || !std::isfinite(sg))) return "RTG_FLAG_FEATURES with RTG_FLAG_DENOISE: a sigma is NaN, infinite or <= 0";
   return nullptr;
 }
 
@@ -679,6 +708,7 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "pool2") s->pool2 = value;                      // 0: the first full-feature pool kernel also for programs the pool-2 kernel walks (A/B switch)
   else if (k == "deep_sized") s->deep_sized = value;
   else if (k == "mat_lds") s->mat_lds = value;
+  else if (k == "guide_lds") s->guide_lds = value;
   else if (k == "small_frames") s->small_frames = value;        // 0: one geometry for every frame size (measurement switch)
   else if (k == "verbose") s->verbose = value;                  // print launch geometry / schedule statistics to stderr
   else if (k == "window") s->window = value;                    // full-feature kernel: records staged in LDS, -1 = automatic
@@ -824,13 +854,19 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
       return hip_fail(e_, #expr);                       \
     }                                                   \
   } while (0)
-  if (sl.denoise && !sl.counts) {
-    // RTG_FLAG_DENOISE without a count plane: the block's in-fields come back now, before anything of the frame is enqueued
-    // and outside the timed span (a counts call reads them with its compaction result: launch_counts)
-    const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, false, false);
-    HIP_TRY(hipMemcpyAsync(&s->cx->denoise_in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream));
+  if ((sl.denoise || sl.features) && !sl.counts) {
+    // RTG_FLAG_DENOISE / RTG_FLAG_FEATURES without a count plane: the blocks' in-fields come back now, in one copy-and-wait, before
+    // anything of the frame is enqueued and outside the timed span (a counts call reads them with its compaction result: launch_counts)
+    if (sl.denoise) {
+      const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, false, false);
+      HIP_TRY(hipMemcpyAsync(&s->cx->denoise_in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream));
+    }
+    if (sl.features) HIP_TRY(read_features_block(d, d_out, stream, sl, &s->cx->features_in));
     HIP_TRY(hipStreamSynchronize(stream));
-    if (const char* why = denoise_refusal(s->cx->denoise_in, d.nranks)) return fail(RTG_ERR_INVALID, why);
+    if (sl.denoise)
+      if (const char* why = denoise_refusal(s->cx->denoise_in, d.nranks)) return fail(RTG_ERR_INVALID, why);
+    if (sl.features)
+      if (const char* why = features_refusal(s->cx->features_in, sl.denoise)) return fail(RTG_ERR_INVALID, why);
   }
   if (count) {
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), stream));
@@ -906,6 +942,14 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     memcpy(&r, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(r));
     if (const char* why = denoise_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
   }
+  // RTG_FLAG_FEATURES: likewise; the block and the three feature planes end the frame
+  const size_t fblock_bytes = sl.features ? features_block_word(params->nx, params->ny, sl) * sizeof(float) : 0;
+  const size_t fplanes_bytes = (size_t)params->nx * params->ny * 7 * sizeof(float);
+  rtg_features fin{};
+  if (sl.features) {
+    memcpy(&fin, reinterpret_cast<const char*>(out_rgb) + fblock_bytes, sizeof(fin));
+    if (const char* why = features_refusal(fin, sl.denoise)) return fail(RTG_ERR_INVALID, why);
+  }
   HIP_TRY(hipSetDevice(s->device));
   // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares; RTG_FLAG_SAMPLE_COUNTS adds the count plane, which
   // travels to the device and is copied back only under RTG_FLAG_RETIRE, together with the out-fields of the retire block)
@@ -913,7 +957,8 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
   const size_t count_bytes = sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0;
   const size_t in_bytes = sl.denoise ? dblock_bytes + sizeof(rtg_denoise) + plane_bytes : sl.retire ? block_bytes + sizeof(rtg_retire) : bytes + count_bytes;
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
-  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, in_bytes ? in_bytes : 16);
+  const size_t frame_bytes = sl.features ? fblock_bytes + sizeof(rtg_features) + fplanes_bytes : in_bytes;
+  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, frame_bytes ? frame_bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
   float* d_out = s->d_frame;
   // pixels of other ranks stay as the caller left them; a single rank overwrites every pixel -- unless it resumes a progressive
@@ -922,6 +967,13 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
   if (upload) e = hipMemcpy(d_out, out_rgb, in_bytes, hipMemcpyHostToDevice);
   else if (sl.denoise)  // (the block alone: a whole frame without counts writes every pixel of every plane)
     e = hipMemcpy(reinterpret_cast<char*>(d_out) + dblock_bytes, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(rtg_denoise), hipMemcpyHostToDevice);
+  if (e == hipSuccess && sl.features) {
+    // the block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other ranks'
+    // pixels must come back as the caller left them
+    const bool planes = params->nranks > 1 || (fin.compute == 0u && sl.denoise);
+    e = hipMemcpy(reinterpret_cast<char*>(d_out) + fblock_bytes, reinterpret_cast<const char*>(out_rgb) + fblock_bytes,
+                  sizeof(rtg_features) + (planes ? fplanes_bytes : 0), hipMemcpyHostToDevice);
+  }
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();
@@ -934,6 +986,11 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     if (e == hipSuccess && sl.denoise) {  // the out-fields (filtered .. reserved) and the output plane behind them
       const size_t lo = dblock_bytes + offsetof(rtg_denoise, filtered);
       e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + lo, reinterpret_cast<const char*>(d_out) + lo, in_bytes - lo, hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess && sl.features) {  // the out-fields (traced .. reserved) and, when this call traced them, the planes behind them
+      const size_t lo = fblock_bytes + offsetof(rtg_features, traced);
+      const size_t hi = fblock_bytes + sizeof(rtg_features) + (fin.compute ? fplanes_bytes : 0);
+      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + lo, reinterpret_cast<const char*>(d_out) + lo, hi - lo, hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) rc = hip_fail(e, "render / copy back");
   }

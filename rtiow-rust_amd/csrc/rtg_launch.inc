@@ -557,11 +557,15 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
 // records and the pass-through pixels, the filter into the output plane, the block's out-fields.  It reads the UNDIVIDED
 // running sums: the callers run it after the slice (and the retire step) and before the division.  `in`: the block's
 // in-fields, already validated.
-static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const rtg_denoise& in) {
+// `guide` (RTG_FLAG_FEATURES in the same call, else nullptr): the features block's in-fields -- the filter is the guided one, over
+// the feature planes the frame holds now (the callers run the feature pass first).
+static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const rtg_denoise& in,
+                                 const rtg_features* guide = nullptr) {
   const uint64_t n_pix = (uint64_t)d.nx * d.ny;
   const uint32_t n_blk = (uint32_t)((n_pix + 255u) / 256u);
-  // [records: 32 B x n_pix] [blk_u32: 2 x n_blk]
-  hipError_t e = grow(&s->cx->d_denoise, &s->cx->denoise_bytes, (size_t)n_pix * 32u + (size_t)n_blk * 8u);
+  // [records: 32 B x n_pix] [blk_u32: 2 x n_blk, padded to 16 B] [guided: feature records: 32 B x n_pix]
+  const size_t frec_at = (size_t)n_pix * 32u + (((size_t)n_blk * 8u + 15u) & ~(size_t)15u);
+  hipError_t e = grow(&s->cx->d_denoise, &s->cx->denoise_bytes, frec_at + (guide ? (size_t)n_pix * 32u : 0u));
   if (e != hipSuccess) return e;
   uint32_t* words = reinterpret_cast<uint32_t*>(d_out);
   DenoiseBufs b;
@@ -572,14 +576,25 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   b.block = words + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
   b.outp = reinterpret_cast<float*>(b.block + 16);
   const DenoiseArgs a{in.k, in.radius, in.patch, d.ns};
-  const size_t lds = denoise_lds_bytes(in.radius, in.patch);
+  // the guided filter reads its neighbours' feature records through the caches, or (option guide_lds) from an LDS copy
+  const int guided = !guide ? 0 : (s->guide_lds > 0 ? 2 : 1);
+  void (*filter)(uint32_t, uint32_t, DenoiseArgs, DenoiseBufs, DenoiseGuide) =
+      guided == 0 ? denoise_filter_kernel<0> : (guided == 1 ? denoise_filter_kernel<1> : denoise_filter_kernel<2>);
+  const size_t lds = denoise_lds_bytes(in.radius, in.patch, guided == 2);
   int per_cu = 0;
-  e = kernel_setup(s, (const void*)denoise_filter_kernel, (int)DN_THREADS, lds, &per_cu);  // (the raise of the dynamic-LDS limit)
+  e = kernel_setup(s, (const void*)filter, (int)DN_THREADS, lds, &per_cu);  // (the raise of the dynamic-LDS limit)
   if (e != hipSuccess) return e;
   const uint64_t tiles = (uint64_t)((d.nx + DN_TW - 1u) / DN_TW) * ((d.ny + DN_TH - 1u) / DN_TH);
   if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  DenoiseGuide gd{nullptr, 1.f, 1.f, 1.f};
+  if (guide) {
+    float4* frec = reinterpret_cast<float4*>(reinterpret_cast<char*>(s->cx->d_denoise) + frec_at);
+    const float* albedo = d_out + features_block_word(d.nx, d.ny, sl) + 16u;
+    gd = DenoiseGuide{frec, guide->sigma_normal, guide->sigma_albedo, guide->sigma_depth};
+    hipLaunchKernelGGL(denoise_guide_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, albedo, albedo + 3ull * n_pix, albedo + 6ull * n_pix, frec);
+  }
   hipLaunchKernelGGL(denoise_prepare_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
-  hipLaunchKernelGGL(denoise_filter_kernel, dim3((uint32_t)tiles), dim3(DN_THREADS), lds, stream, d.nx, d.ny, a, b);
+  hipLaunchKernelGGL(filter, dim3((uint32_t)tiles), dim3(DN_THREADS), lds, stream, d.nx, d.ny, a, b, gd);
   hipLaunchKernelGGL(denoise_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
   return hipGetLastError();
 }
@@ -589,6 +604,42 @@ static hipError_t read_denoise_block(const DevParams& d, const float* d_out, hip
   return hipMemcpyAsync(in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream);
 }
 
+// RTG_FLAG_FEATURES (include/rtiow_gpu.h): the feature pass over this rank's pixels (rt_features.h) -- the three planes behind the
+// features block and the block's out-fields.  `in`: the block's in-fields, already validated; compute = 0 writes the
+// out-fields alone.  The kernel is instantiated per scene-feature set as the probes' (rtg_probes.inc): deep graphs take the
+// general walk.
+static hipError_t launch_features(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl,
+                                  const rtg_features& in) {
+  const uint64_t n_pix = (uint64_t)d.nx * d.ny;
+  const uint64_t blocks = (uint64_t)((d.nx + 15u) / 16u) * ((d.ny + 15u) / 16u);
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  const uint32_t n_blk = in.compute ? (uint32_t)blocks : 0u;
+  hipError_t e = grow((void**)&s->cx->d_features, &s->cx->features_bytes, (size_t)std::max<uint64_t>(blocks, 1) * 8u);
+  if (e != hipSuccess) return e;
+  FeatureBufs b;
+  b.block = reinterpret_cast<uint32_t*>(d_out) + features_block_word(d.nx, d.ny, sl);
+  b.albedo = reinterpret_cast<float*>(b.block + 16);
+  b.normal = b.albedo + 3ull * n_pix;
+  b.depth = b.normal + 3ull * n_pix;
+  b.blk_u32 = s->cx->d_features;
+  if (n_blk != 0u) {
+    const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
+    if (s->features & FEAT_DEEP)
+      hipLaunchKernelGGL((features_kernel<FEAT_ALL | FEAT_DEEP>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
+    else if (geom == 0)
+      hipLaunchKernelGGL((features_kernel<0u>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
+    else
+      hipLaunchKernelGGL((features_kernel<FEAT_ALL>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
+  }
+  hipLaunchKernelGGL(features_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
+  return hipGetLastError();
+}
+// ... and the read-back of its in-fields on the launch stream, with the call's other read-backs
+static hipError_t read_features_block(const DevParams& d, const float* d_out, hipStream_t stream, const SampleSlice& sl, rtg_features* in) {
+  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + features_block_word(d.nx, d.ny, sl);
+  return hipMemcpyAsync(in, d_block, offsetof(rtg_features, traced), hipMemcpyDeviceToHost, stream);
+}
+
 // RTG_FLAG_SAMPLE_COUNTS (include/rtiow_gpu.h): compact this rank's active pixels (e_p > sl.begin) into the list the pool
 // kernels run over (rt_pool.h compact_*), read back its length and the call's sample count -- the one synchronisation of the
 // stream a counts call makes -- render the list with the kernel the features pick (the baseline kernel walks every pixel and
@@ -596,15 +647,18 @@ static hipError_t read_denoise_block(const DevParams& d, const float* d_out, hip
 // RTG_FLAG_RETIRE: the block's in-fields come back with that read-back (on their own when the call renders nothing); refused
 // ones end the call before it renders (s->cx->refusal), accepted ones run the retire step between the render and the division.
 // RTG_FLAG_DENOISE: its in-fields travel in the same read-back; the filter runs after the retire step, before the division.
+// RTG_FLAG_FEATURES: likewise its in-fields (a call that renders, retires and filters nothing syncs for them alone); the feature
+// pass runs first, before the render.
 template <bool COUNT>
 static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
                                 const SampleSlice& sl, uint32_t geom, bool pool_ok) {
   s->cx->counts_samples = 0;
   const uint64_t pix_work = rank_pix_work(d);
-  if (pix_work == 0 && !sl.retire) return hipSuccess;  // this rank owns no tile
+  if (pix_work == 0 && !sl.retire && !sl.features) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
   rtg_retire rin{};  // (RTG_FLAG_RETIRE: the in-fields, read back below)
   rtg_denoise din{};  // (RTG_FLAG_DENOISE: likewise)
+  rtg_features fin{};  // (RTG_FLAG_FEATURES: likewise)
   const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
   SampleSlice ls = sl;
   ls.list.counts = reinterpret_cast<const uint32_t*>(d_out + (sl.squares ? 6ull : 3ull) * d.nx * d.ny);
@@ -634,10 +688,13 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && sl.retire) e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
+    if (e == hipSuccess && sl.features) e = read_features_block(d, d_out, stream, sl, &fin);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
     if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
+    if (sl.features && (s->cx->refusal = features_refusal(fin, sl.denoise))) return hipSuccess;
+    if (sl.features && (e = launch_features(s, cam, d, d_out, stream, sl, fin)) != hipSuccess) return e;
     s->cx->counts_samples = h.samples;
     ls.list_work = h.padded;
     if (s->verbose)
@@ -663,20 +720,23 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
       }
       if (e != hipSuccess) return e;
     }
-  } else if (sl.retire || sl.denoise) {
+  } else if (sl.retire || sl.denoise || sl.features) {
     e = sl.retire ? hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream) : hipSuccess;
     if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
+    if (e == hipSuccess && sl.features) e = read_features_block(d, d_out, stream, sl, &fin);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
     if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
+    if (sl.features && (s->cx->refusal = features_refusal(fin, sl.denoise))) return hipSuccess;
+    if (sl.features && (e = launch_features(s, cam, d, d_out, stream, sl, fin)) != hipSuccess) return e;
   }
   if (sl.retire) {
     e = launch_retire(s, d, d_out, stream, pix_work, rin);
     if (e != hipSuccess) return e;
   }
   if (sl.denoise) {
-    e = launch_denoise(s, d, d_out, stream, sl, din);
+    e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &fin : nullptr);
     if (e != hipSuccess) return e;
   }
   if (!sl.divide || pix_work == 0) return hipSuccess;
@@ -696,6 +756,15 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
   s->cx->last_kernel = KernelKind::baseline;
   if (sl.counts) return launch_counts<COUNT>(s, cam, d, d_out, stream, sl, geom, pool_ok);
+  if (sl.features && !sl.features_done) {
+    // RTG_FLAG_FEATURES without a count plane (the block's in-fields were read back and checked by rtg_par_cast_device): the
+    // feature pass first, then the call as without the flag (the filter, if any, guided)
+    hipError_t e = launch_features(s, cam, d, d_out, stream, sl, s->cx->features_in);
+    if (e != hipSuccess) return e;
+    SampleSlice rest = sl;
+    rest.features_done = true;
+    return launch_render<COUNT>(s, cam, d, d_out, stream, rest);
+  }
   if (sl.denoise) {
     // RTG_FLAG_DENOISE without a count plane (the block's in-fields were read back and checked by rtg_par_cast_device): render
     // the slice as a PARTIAL one, whichever kernel takes it, filter the undivided sums, then divide as the resolve step does
@@ -703,7 +772,7 @@ static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevPar
     SampleSlice render = sl;
     render.denoise = false, render.divide = false;
     hipError_t e = launch_render<COUNT>(s, cam, d, d_out, stream, render);
-    if (e == hipSuccess) e = launch_denoise(s, d, d_out, stream, sl, din);
+    if (e == hipSuccess) e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &s->cx->features_in : nullptr);
     if (e != hipSuccess) return e;
     return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;
   }

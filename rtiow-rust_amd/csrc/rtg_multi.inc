@@ -380,6 +380,7 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   if (params->flags & RTG_FLAG_SAMPLE_COUNTS) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SAMPLE_COUNTS is not supported");
   if (params->flags & RTG_FLAG_RETIRE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_RETIRE is not supported");
   if (params->flags & RTG_FLAG_DENOISE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_DENOISE is not supported");
+  if (params->flags & RTG_FLAG_FEATURES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_FEATURES is not supported");
   for (int i = 0; i < n_scenes; i++) {
     if (!scenes[i]) return fail(RTG_ERR_INVALID, "null scene handle");
     // one handle = one frame, one work queue, one stream: the same handle twice would wipe its own tiles

@@ -71,6 +71,69 @@ def nlm(sum_, sq, held, radius=5, patch=2, k=0.7):
     return out.astype(f32)
 
 
+def feature_weight(albedo, normal, depth, dy, dx, sigma_normal, sigma_albedo, sigma_depth):
+    """The guided filter's weight of every pixel p with q = p + (dy, dx), float32 [ny, nx]: the n = 4 member of
+    (1 - x / n)^n at x = the largest of the three squared feature distances, each over its sigma squared; 1 where any of the
+    fourteen feature values is not finite.  (q outside the image: zeros take its place; the colour weight is 0 there.)"""
+    a, n, z = np.asarray(albedo, dtype=f32), np.asarray(normal, dtype=f32), np.asarray(depth, dtype=f32)
+    sn, sa, sz = f32(sigma_normal), f32(sigma_albedo), f32(sigma_depth)
+    fin = np.isfinite(a).all(axis=-1) & np.isfinite(n).all(axis=-1) & np.isfinite(z)
+    with np.errstate(all="ignore"):
+        dn, da = n - _shift(n, dy, dx, f32(0)), a - _shift(a, dy, dx, f32(0))
+        zq = _shift(z, dy, dx, f32(0))
+        xn = ((dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]) / (sn * sn)
+        xa = ((da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2]) / (sa * sa)
+        dz, s = z - zq, z + zq
+        xz = ((dz * dz) / (s * s + f32(1e-20))) / (sz * sz)
+        x = xn
+        x = np.where(xa > x, xa, x)
+        x = np.where(xz > x, xz, x)
+        u = f32(1) - x * f32(0.25)
+        u = np.where(u > 0, u, f32(0))
+        wf = (u * u) * (u * u)
+    return np.where(fin & _shift(fin, dy, dx, True), wf, f32(1)).astype(f32)
+
+
+def nlm_guided(sum_, sq, held, albedo, normal, depth, radius=5, patch=2, k=0.7, sigma_normal=0.1, sigma_albedo=0.1,
+               sigma_depth=0.1):
+    """nlm() guided by first-hit feature planes (RTG_FLAG_DENOISE | RTG_FLAG_FEATURES): albedo and normal float32 [ny, nx, 3],
+    depth float32 [ny, nx].  The one change: after the colour weight w of a displacement is computed and before the mask of
+    valid pairs, w = wf < w ? wf : w with wf = feature_weight() of the pair.  Sigmas of 1e18 give nlm() bit for bit."""
+    m, v, valid = mean_var(sum_, sq, held)
+    ny, nx = valid.shape
+    mz = np.where(valid[..., None], m, f32(0)).astype(f32)
+    k2, eps = f32(k) * f32(k), f32(1e-10)
+    acc, wsum = np.zeros((ny, nx, 3), f32), np.zeros((ny, nx), f32)
+    R, F = int(radius), int(patch)
+    with np.errstate(all="ignore"):
+        for dy in range(-R, R + 1):
+            for dx in range(-R, R + 1):
+                mb, vb = _shift(mz, dy, dx, f32(0)), _shift(v, dy, dx, f32(0))
+                pv = valid & _shift(valid, dy, dx, False)
+                diff = mz - mb
+                d2 = (diff * diff - (v + np.minimum(vb, v))) / (eps + k2 * (v + vb))
+                pd = np.where(pv, (d2[..., 0] + d2[..., 1]) + d2[..., 2], f32(0)).astype(f32)
+                pc = pv.astype(np.int32)
+                r, rc = np.zeros((ny, nx), f32), np.zeros((ny, nx), np.int32)
+                for ox in range(-F, F + 1):
+                    r, rc = r + _shift(pd, 0, ox, f32(0)), rc + _shift(pc, 0, ox, 0)
+                dsum, cnt = np.zeros((ny, nx), f32), np.zeros((ny, nx), np.int32)
+                for oy in range(-F, F + 1):
+                    dsum, cnt = dsum + _shift(r, oy, 0, f32(0)), cnt + _shift(rc, oy, 0, 0)
+                x = dsum / (f32(3) * cnt.astype(f32))
+                x = np.where(x > 0, x, f32(0))
+                u = f32(1) - x * f32(0.25)
+                u = np.where(u > 0, u, f32(0))
+                u2 = u * u
+                w = u2 * u2
+                wf = feature_weight(albedo, normal, depth, dy, dx, sigma_normal, sigma_albedo, sigma_depth)
+                w = np.where(wf < w, wf, w)
+                w = np.where(pv, w, f32(0)).astype(f32)
+                acc, wsum = acc + w[..., None] * mb, wsum + w
+        out = np.where(valid[..., None], acc / np.where(valid, wsum, f32(1))[..., None], m)
+    return out.astype(f32)
+
+
 def denoise(frame_or_planes, held, radius=5, patch=2, k=0.7):
     """nlm() of a frame's planes: `frame_or_planes` is a float32 [2, ny, nx, 3] array (running sums, sums of squares) or an
     object with such a `planes` view (capi.CountsFrame / capi.DenoiseFrame); `held` the samples every pixel holds, an int or a

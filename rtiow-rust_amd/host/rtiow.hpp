@@ -419,6 +419,37 @@ inline DenoisedImage par_cast_denoised(size_t nx, size_t ny, size_t ns, const Ca
   return out;
 }
 
+// Not in the reference: par_cast with RTG_FLAG_FEATURES.  `image` is exactly what par_cast returns; `albedo` and `normal` (three
+// floats per pixel) and `depth` (one) are the first-hit feature planes a denoiser or compositor takes beside the colour, from
+// grid x grid primary rays per pixel (see the header); `block` the features block with its out-fields.
+struct FeatureImages {
+  Image image, albedo, normal;
+  std::vector<float> depth;
+  rtg_features block{};
+};
+
+inline FeatureImages par_cast_features(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, uint32_t grid = 2,
+                                       const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  const size_t n = nx * ny, block_word = (3 * n + 1) & ~size_t(1);  // one plane, padding to 8 bytes, the block, the three planes
+  std::vector<float> frame(block_word + sizeof(rtg_features) / sizeof(float) + 7 * n, 0.f);
+  rtg_features f{};
+  f.grid = grid, f.compute = 1;
+  std::memcpy(frame.data() + block_word, &f, sizeof(f));
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_FEATURES;
+  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  FeatureImages out;
+  out.image.nx = out.albedo.nx = out.normal.nx = nx, out.image.ny = out.albedo.ny = out.normal.ny = ny;
+  const auto at = frame.begin() + block_word + 16;
+  out.image.rgb.assign(frame.begin(), frame.begin() + 3 * n);
+  out.albedo.rgb.assign(at, at + 3 * n);
+  out.normal.rgb.assign(at + 3 * n, at + 6 * n);
+  out.depth.assign(at + 6 * n, at + 7 * n);
+  std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_features));
+  return out;
+}
+
 // Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /
 // (n - 1)), se = sqrt(s2 / n); +inf for n = 1.  `mean` = sum / n (par_cast's image; a PARTIAL running sum divided by n).
 inline double standard_error(double mean, double sum_sq, size_t n) {

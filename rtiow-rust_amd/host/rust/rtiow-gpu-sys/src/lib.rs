@@ -36,6 +36,9 @@ pub const RTG_RETIRE_MAX_RADIUS: u32 = 8;
 pub const RTG_FLAG_DENOISE: u32 = 128;
 pub const RTG_DENOISE_MAX_RADIUS: u32 = 8;
 pub const RTG_DENOISE_MAX_PATCH: u32 = 3;
+/// The framebuffer ends with an `rtg_features` block and the first-hit albedo, normal and depth planes (see the header).
+pub const RTG_FLAG_FEATURES: u32 = 256;
+pub const RTG_FEATURES_MAX_GRID: u32 = 4;
 
 #[repr(C)]
 pub struct rtg_builder {
@@ -108,6 +111,22 @@ pub struct rtg_denoise {
     pub filtered: u32,
     pub passed: u32,
     pub reserved: [u32; 10],
+}
+
+/// 64 bytes, at the first even word behind everything the other flags put in an `RTG_FLAG_FEATURES` frame; the albedo plane
+/// (`nx * ny * 3` floats) starts 16 words behind it, then the normal plane (`nx * ny * 3`) and the depth plane (`nx * ny`).
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct rtg_features {
+    pub grid: u32,
+    pub compute: u32,
+    pub sigma_normal: c_float,
+    pub sigma_albedo: c_float,
+    pub sigma_depth: c_float,
+    pub reserved_in: u32,
+    pub traced: u32,
+    pub missed: u32,
+    pub reserved: [u32; 8],
 }
 
 /// 56 bytes.
