@@ -175,7 +175,7 @@ struct ChunkMode {
   // long-path-prone blocks first, sky last.  Order never changes results (per-event RNG streams,
   // ordered fold).
   const LptQueue* lpt;   // descriptor in device memory (a by-value copy inside the kernel arguments cost 19 more SGPR spills and
-                         // 8 % of a C2 launch); written on the LAUNCH STREAM by write_lpt_descriptor, so launches stay ordered
+                         // 8 % of a C2 launch); written on the LAUNCH STREAM by write_pass_setup, so launches stay ordered
   uint32_t lpt_samples;  // samples [0, lpt_samples) of every pixel belong to phase 1 (0 = off)
   uint32_t lpt_deep;     // a scatter event counts towards its block's cost from this bounce on
   // Sample passes (bounded scratch): a launch renders the samples [s_begin, P.ns) of every pixel -- P.ns of the LAUNCH is
@@ -313,11 +313,18 @@ RT_DEV T load_const(const T* p) {
   for (uint32_t i = 0; i < sizeof(T) / 4u; i++) dst[i] = w[i];
   return c;
 }
-// (also resets the work-queue head of the launch: one stream operation less per sample pass than a hipMemsetAsync)
-__global__ void write_launch_consts(LaunchConsts* dst, LaunchConsts v, unsigned long long* queue) { *dst = v, *queue = 0ull; }
-
-// stream-ordered update of the descriptor (a kernel argument by value: no host buffer has to outlive the call)
-__global__ void write_lpt_descriptor(LptQueue* dst, LptQueue v) { *dst = v; }
+// Everything a sample pass needs in device memory before its render kernel starts, in ONE stream operation (one block of 256
+// threads, launched in front of the render kernel on the launch stream): the launch constants, the work-queue head and --
+// `lpt_dst` != null: the pass runs the cost-ordered queue -- the queue's descriptor and its zeroed cost[] / ctl[] words
+// (`n_zero` words from q.cost on: ctl[] follows cost[]).  The structs are kernel arguments by value: no host buffer has to
+// outlive the call.
+__global__ __launch_bounds__(256) void write_pass_setup(LaunchConsts* dst, LaunchConsts v, unsigned long long* queue, LptQueue* lpt_dst,
+                                                        LptQueue q, uint32_t n_zero) {
+  if (threadIdx.x == 0) *dst = v, *queue = 0ull;
+  if (lpt_dst == nullptr) return;
+  if (threadIdx.x == 64) *lpt_dst = q;
+  for (uint32_t i = threadIdx.x; i < n_zero; i += blockDim.x) q.cost[i] = 0u;
+}
 
 // second pass of the chunk mode: ordered fold of the per-sample colours (vec3.rs:195-203, lib.rs:374).  Samples
 // [cm.s_begin, P.ns) of this pass are added IN ORDER to the running sum of the earlier passes -- (0, 0, 0) for the first
@@ -831,6 +838,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
   uint32_t my_slot = 0;
   bool have_ray = false;  // lane holds a ray (traversing or parked at a SPHERE record)
   V3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+  float dd = 0.f;  // dot(d, d), object.rs:86: formed once per ray at the refill, used by every Sphere::hit of its walk
   uint32_t pc = 0, best_pc = NO_HIT, best_flags = 0;
   float best = F32_MAX;
   // the record at pc as the box step wants it: per axis (near plane, far plane), skip pc, op/flags
@@ -880,16 +888,21 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
 #endif
 #define RT_IS_BOX() (USE_LDS ? (int32_t)c_flags < 0 : (c_flags & 0xffu) == OP_BOX)
 #define RT_BOX_STEP() \
-        if (RT_IS_BOX()) { \
+        if (in_box) { \
           if (COUNT) cnt.aabb++; \
           RT_BOX_T(tx, cx, o.x, inv.x); \
           RT_BOX_T(ty, cy, o.y, inv.y); \
           RT_BOX_T(tz, cz, o.z, inv.z); \
           float start = rs_max(t_near, rs_max(rs_max(tx.x, ty.x), tz.x)); \
           float end = rs_min(best, rs_min(rs_min(tx.y, ty.y), tz.y)); \
-          pc = (end > start) ? pc + REC_BOX : c_skip; \
+          const bool pass_ = end > start; \
+          __builtin_amdgcn_sched_barrier(0); \
+          const uint32_t next_ = pc + REC_BOX; \
+          __builtin_amdgcn_sched_barrier(0); \
+          pc = pass_ ? next_ : c_skip; \
           RT_LOAD_REC(); \
-        }
+        } \
+        in_box = RT_IS_BOX();
   // WIDE: continue at node `n_pc`: its next pending child (left to right), else up to its parent, else the program ends
   auto wide_next = [&](uint32_t n_pc) {
     for (;;) {
@@ -1247,6 +1260,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
             o = mk(RAY_F(PF_O, my_slot), RAY_F(PF_O + 1, my_slot), RAY_F(PF_O + 2, my_slot));
             d = mk(RAY_F(PF_D, my_slot), RAY_F(PF_D + 1, my_slot), RAY_F(PF_D + 2, my_slot));
             inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);  // aabb.rs:17
+            dd = vdot(d, d);
             sgn_x = inv.x < 0.f ? 32u : 8u, sgn_y = inv.y < 0.f ? 40u : 16u, sgn_z = inv.z < 0.f ? 48u : 24u;  // aabb.rs:20-23
             pc = pc0, best = F32_MAX, best_pc = NO_HIT, best_flags = 0;
             if (COUNT) tr_a0 = cnt.aabb, tr_p0 = cnt.prim;
@@ -1279,9 +1293,14 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
     if (b_box != 0 && (uint32_t)__builtin_popcountll(b_sph) < tune.sphere_min) {
       // box run: tight loop, schedule re-evaluated once `box_leave` lanes have left the BOX state
       if (COUNT) t_mark = RT_TICK();
+      // The run's bookkeeping: ONE "is this lane at a BOX" compare per step -- made behind the step's record reload, it is the
+      // next step's entry mask and, behind the last step of an iteration, the ballot of the exit test -- and an exit test
+      // that stays on the scalar unit (the saturating subtract would otherwise be formed as a vector instruction and drag
+      // the per-iteration compare with it)
       const uint32_t n0 = (uint32_t)__builtin_popcountll(b_box);
-      const uint32_t floor_lanes = n0 > tune.box_leave ? n0 - tune.box_leave : 0u;
+      const uint32_t floor_lanes = __builtin_amdgcn_readfirstlane(n0 > tune.box_leave ? n0 - tune.box_leave : 0u);
       uint32_t n_now;
+      bool in_box = RT_IS_BOX();
       do {
         if (COUNT) n_box_it++;
         if (WIDE) {
@@ -1298,7 +1317,8 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
         RT_BOX_STEP();
 #endif
         }
-        n_now = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(RT_IS_BOX()));
+        if (WIDE) in_box = RT_IS_BOX();
+        n_now = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in_box));
         if (COUNT) n_box_lanes += n_now;
       } while (n_now > floor_lanes);
       if (COUNT) t_box += RT_TICK() - t_mark;
@@ -1310,7 +1330,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
         V3 lo_o = o;
         if (c_flags & F_TRANSLATE) lo_o = vsub(o, mk(u2f(slo.x), u2f(slo.y), u2f(slo.z)));
         float t;
-        if (sphere_hit_t(lo_o, d, u2f(slo.w), t_near, best, t)) {
+        if (sphere_hit_t_a(lo_o, d, dd, u2f(slo.w), t_near, best, t)) {
           best = t;
           best_pc = pc;
           best_flags = c_flags;

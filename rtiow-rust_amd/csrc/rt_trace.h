@@ -82,9 +82,9 @@ struct Counts {
 
 RT_DEV float u2f(uint32_t u) { return __uint_as_float(u); }
 
-// object.rs:84-111 (sphere at the local origin)
-RT_DEV bool sphere_hit_t(V3 o, V3 d, float radius, float t0, float t1, float& t_out) {
-  float a = vdot(d, d);
+// object.rs:84-111 (sphere at the local origin), with a = dot(d, d) handed in: it depends on the ray alone, so a walk that
+// keeps its ray in registers forms it once per ray (rt_pool.h, the refill) instead of once per sphere
+RT_DEV bool sphere_hit_t_a(V3 o, V3 d, float a, float radius, float t0, float t1, float& t_out) {
   float b = vdot(o, d);
   float c = vdot(o, o) - radius * radius;
   float disc = b * b - a * c;
@@ -102,6 +102,9 @@ RT_DEV bool sphere_hit_t(V3 o, V3 d, float radius, float t0, float t1, float& t_
     }
   }
   return false;
+}
+RT_DEV bool sphere_hit_t(V3 o, V3 d, float radius, float t0, float t1, float& t_out) {
+  return sphere_hit_t_a(o, d, vdot(d, d), radius, t0, t1, t_out);
 }
 
 // object.rs:185-218; other axes: X->(Y,Z), Y->(X,Z), Z->(X,Y)  (object.rs:157-181)

@@ -55,7 +55,8 @@ static hipError_t grow(void** buf, size_t* have, size_t need) {
   return e;
 }
 
-static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipStream_t stream);
+static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity);
+static void launch_pass_setup(rtg_scene* s, const LaunchConsts& c, uint32_t* queue, hipStream_t stream);
 
 // hipFuncSetAttribute(max dynamic LDS) + the occupancy query of a (kernel, block, LDS) triple: the two runtime calls cost a
 // small frame more than its kernels (tools/latency_probe.py), so they are made once per process.  The attribute belongs to
@@ -151,7 +152,7 @@ static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, 
     const uint64_t total_work = (uint64_t)cm.pix_work * cm.n_chunks;
     if (total_work > 0xfffffffeull) return hipErrorInvalidValue;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(L.geo.grid, (uint64_t)s->num_cus * L.per_cu);
-    hipError_t e = setup_lpt(s, cm, (uint64_t)grid * (uint32_t)(L.bt / 64) * L.pool, stream);
+    hipError_t e = setup_lpt(s, cm, (uint64_t)grid * (uint32_t)(L.bt / 64) * L.pool);
     if (e != hipSuccess) return e;
     if (cm.lpt) cm.work_block = WORK_BLOCK;  // (its blocks are the reservations)
     e = issue(s0, dp, cm, grid, (uint32_t)total_work);
@@ -258,7 +259,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
               s0, dp.ns, d.ns, grid, bt, L.per_cu, lds, (int)use_lds, (int)ray_lds, cm.n_chunks, cm.chunk, (cm.lpt_samples - (cm.lpt_samples ? s0 : 0u)) / (cm.chunk ? cm.chunk : 1u));
     hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
     if (eg != hipSuccess) return eg;
-    hipLaunchKernelGGL(write_launch_consts, dim3(1), dim3(1), 0, stream, s->cx->d_consts, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, (unsigned long long*)queue);
+    launch_pass_setup(s, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, queue, stream);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                        s->cx->d_counters, s->pool_tune, s->cx->d_slots);
     return hipSuccess;
@@ -336,8 +337,9 @@ static bool build_wide_image(const Packet* lo, const Packet* hi, size_t n, std::
 }
 
 // Cost-ordered work queue (rt_pool.h, ChunkMode): enabled when the frame has enough chunks for a measuring
-// phase and enough blocks to order; the buffers are re-zeroed on the launch stream every call.
-static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipStream_t stream) {
+// phase and enough blocks to order.  This decides and sizes; the descriptor and the zeroed counters reach the device with the
+// pass's constants (launch_pass_setup), every pass.
+static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity) {
   cm.lpt = nullptr, cm.lpt_samples = 0, cm.lpt_deep = 0;
   const uint32_t n_blocks = cm.pix_work / LPT_BLOCK;
   if (!s->lpt || !cm.scratch || cm.n_chunks < 6 || n_blocks < 64 || n_blocks > 65536 || cm.pix_work % LPT_BLOCK) return hipSuccess;
@@ -358,17 +360,21 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity, hipS
   q.phase2_base = phase1 * cm.pix_work;
   q.span = LPT_BLOCK * (cm.n_chunks - phase1);
   q.mode = (uint32_t)s->lpt, q.shift = (uint32_t)s->lpt_shift;
-  // descriptor and zeroed counters travel on the launch stream: ordered with the render kernels before and after
-  hipLaunchKernelGGL(write_lpt_descriptor, dim3(1), dim3(1), 0, stream, reinterpret_cast<LptQueue*>(s->cx->d_lpt), q);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
   s->cx->lpt_desc = q;
-  e = hipMemsetAsync(q.cost, 0, ((size_t)n_blocks + LPT_CTL) * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
   cm.lpt = reinterpret_cast<const LptQueue*>(s->cx->d_lpt);
   cm.lpt_samples = cm.s_begin + phase1 * cm.chunk;  // samples [s_begin, lpt_samples) of every pixel: phase 1 of this pass
   cm.lpt_deep = (uint32_t)s->lpt_deep;
   return hipSuccess;
+}
+
+// The one stream operation in front of a pass's render kernel (rt_pool.h write_pass_setup): constants, queue head and, when
+// setup_lpt switched the cost-ordered queue on for this pass (c.cm.lpt), its descriptor and zeroed counters -- on the launch
+// stream, so ordered with the render kernels before and after.
+static void launch_pass_setup(rtg_scene* s, const LaunchConsts& c, uint32_t* queue, hipStream_t stream) {
+  const bool lpt = c.cm.lpt != nullptr;
+  const LptQueue q = lpt ? s->cx->lpt_desc : LptQueue{};
+  hipLaunchKernelGGL(write_pass_setup, dim3(1), dim3(256), 0, stream, s->cx->d_consts, c, (unsigned long long*)queue,
+                     lpt ? reinterpret_cast<LptQueue*>(s->cx->d_lpt) : (LptQueue*)nullptr, q, lpt ? q.n_blocks + LPT_CTL : 0u);
 }
 
 // Full-feature scenes, ray-pool kernel (rt_pool_full.h) or, for list worlds without a Bvh, the lock-step kernel
@@ -499,7 +505,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
               cm.lpt_samples - (cm.lpt_samples ? s0 : 0u));
     LaunchConsts c = consts;
     c.cam = cam, c.P = dp, c.cm = cm, c.pm = make_pixmap(dp);
-    hipLaunchKernelGGL(write_launch_consts, dim3(1), dim3(1), 0, stream, s->cx->d_consts, c, (unsigned long long*)queue);
+    launch_pass_setup(s, c, queue, stream);
     if (L.kind == KernelKind::lock_step)
       hipLaunchKernelGGL(sync_kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                          s->cx->d_counters, s->sync_tune, s->cx->d_stack, window);
