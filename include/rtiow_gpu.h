@@ -382,6 +382,37 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
  * Scene option "multi_gather" = 1 (on any handle) selects the PACKED collective instead: every scene packs the pixels it owns
  * (1 / n_scenes of the frame), grouped ncclSend / ncclRecv bring the packed tiles of the other devices to the first one, which
  * scatters them into its frame -- copies only, bit-identical by construction, 1 / n_scenes of the bytes per device. */
+/* Flagged frames over several handles: scene option "multi_planes" (default 0; it counts when set on ANY handle of the call,
+ * like "multi_gather" and "force_rccl").  Off, nothing changes: a call with RTG_FLAG_SUM_SQUARES, SAMPLE_COUNTS, RETIRE, DENOISE
+ * or FEATURES returns RTG_ERR_UNSUPPORTED and writes nothing.  On, rtg_par_cast_multi accepts these five flags in every
+ * combination rtg_par_cast accepts; PARTIAL, RESUME and COUNTERS combine with them as on one handle.
+ *   - `out` is HOST memory with exactly the layout rtg_par_cast defines for the same flags, blocks included.  Every word of it
+ *     that rtg_par_cast on ONE handle (nranks 0 / 1, same camera, params and blocks) would write ends bit-identical to that
+ *     call's; every word that call leaves alone stays as the caller left it (pixels with n_p == 0, the blocks' in-fields,
+ *     reserved2, the feature planes under compute = 0, the count plane except under RTG_FLAG_RETIRE) -- for any number of
+ *     handles, any tile size, any device placement and either RCCL route.
+ *   - Order: every scene renders its tiles as a PARTIAL slice, with SUM_SQUARES / SAMPLE_COUNTS as given, and traces the
+ *     feature pass for the pixels it owns when compute = 1; the ranks apply no retire rule, no filter and no division.  The
+ *     owned pixels of every plane the ranks wrote (the sum, the squares, the three feature planes when compute = 1) are then
+ *     gathered onto the first device's frame, and on that frame the first device runs what a one-handle call with
+ *     sample_begin == ns runs: RTG_FLAG_RETIRE with any radius up to RTG_RETIRE_MAX_RADIUS, then RTG_FLAG_DENOISE (guided
+ *     when RTG_FLAG_FEATURES is set, over the feature planes the frame now holds), then the division unless RTG_FLAG_PARTIAL --
+ *     the same kernels as on one handle.
+ *   - Refusals: those of rtg_par_cast with nranks = 1 (the window and the filter see the whole frame, so the "nranks > 1"
+ *     clauses above do not apply), checked on the host copy of the blocks before anything is uploaded or enqueued; nothing is
+ *     written.  params->rank / nranks must stay 0 / 0-or-1.
+ *   - Blocks: the out-fields of every block equal the one-handle call's.  rtg_features.traced / missed are the sums over the
+ *     ranks; rtg_retire.sum_se2 comes from the first device's run over the whole frame (tiles of the caller's params, 0 =
+ *     16x16), so its bits are the one-handle call's.
+ *   - Collective: a call with any of the five flags always takes the packed route (copies only: bit-identical by
+ *     construction).  ONE ncclSend / ncclRecv pair per handle that travels carries all its planes, plane-major (word k of work
+ *     item w at k * pix_work + w; 3 .. 13 words per pixel), so rtg_multi_reset counts the same transfers as for a plain packed
+ *     frame; handles on the first device are unpacked from their own buffer.  The count plane is the caller's input and never
+ *     travels back.  A call WITHOUT any of the five flags is unchanged whatever the option says.
+ *   - rtg_stats: samples and the counters are the sums over the ranks, equal to the one-handle call's; kernel_ms is the slowest
+ *     shard's render span plus the first device's span for retire / filter / division.
+ *   - Uploads: the first device's frame is uploaded as rtg_par_cast uploads it (untouched pixels and an untouched output plane
+ *     survive); every other rank gets the float planes when the call resumes or has a count plane, and the count plane. */
 int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera,
                        const rtg_params* params, float* out_rgb, rtg_stats* stats_or_null);
 

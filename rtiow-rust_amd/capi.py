@@ -382,6 +382,70 @@ def _host_frame(out, nx, ny, kw):
     return out
 
 
+def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw):
+    """The host-frame loop of Scene.adaptive and Backend.adaptive_multi: `cast(ns, **keywords)` is the par_cast of either
+    (camera and frame size bound); denoise / features: a checked Denoise / Features, or None."""
+    if features is not None:
+        f = FeaturesFrame(nx, ny, squares=True, counts=True, denoise=denoise) if out is None else out
+        if (not isinstance(f, FeaturesFrame) or f.counts is None or f.retire is not None or not f.squares
+                or (f.denoise is None) != (denoise is None)):
+            raise ValueError("features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)")
+        C.memmove(C.addressof(f.features), C.addressof(features), Features.OUT_OFFSET)
+        if denoise is not None:
+            C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+    elif denoise is not None:
+        f = DenoiseFrame(nx, ny, counts=True) if out is None else out
+        if not isinstance(f, DenoiseFrame) or f.counts is None or f.retire is not None:
+            raise ValueError("denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)")
+        C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+    else:
+        f = CountsFrame(nx, ny, squares=True) if out is None else out
+        if not isinstance(f, CountsFrame):
+            raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
+    more = () if features is None else (f,)
+    if f.planes.shape != (2, ny, nx, 3):
+        raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
+    f.counts[...] = ns
+    active = np.ones((ny, nx), dtype=bool)
+    t0 = time.perf_counter()
+    done = 0
+    while done < ns:
+        end = min(ns, done + step)
+        if features is not None:
+            _, st = cast(end, seed=seed, out=f, denoise=True if denoise is not None else None, features=True, sample_begin=done,
+                         resume=True, partial=True, squares=True, stats=True, counters=False, **kw)
+            f.features.compute = 0   # (the planes are traced once)
+        elif denoise is not None:
+            _, st = cast(end, seed=seed, out=f, denoise=True, sample_begin=done, resume=True, partial=True, squares=True,
+                         stats=True, counters=False, **kw)
+        else:
+            _, st = cast(end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True, partial=True, squares=True,
+                         stats=True, counters=False, **kw)
+        if stats is not None:
+            stats.append(st)
+        done = end
+        held = np.minimum(f.counts, done).astype(np.uint32)
+        se = noise.standard_error_counts(f.planes[0], f.planes[1], held)
+        if radius:
+            retire = noise.retire(active, done, se, min_samples, target_se, radius=radius, present=f.counts > 0)
+        else:
+            retire = noise.retire(active, done, se, min_samples, target_se)
+        f.counts[retire] = done
+        active &= ~retire
+        pv = CountsFrame(nx, ny)   # resolve a copy: the running sums go on
+        pv.planes[...] = f.planes[0]
+        pv.counts[...] = held
+        cast(done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
+        if denoise is not None:
+            yield (held, pv.planes, se, f.denoised.copy()) + more
+        else:
+            yield (held, pv.planes, se) + more
+        if not active.any():
+            return
+        if budget_s is not None and time.perf_counter() - t0 >= budget_s:
+            return
+
+
 # error codes of include/rtiow_gpu.h
 ERR_INVALID, ERR_EMPTY_BVH, ERR_NAN, ERR_RANGE, ERR_UNSUPPORTED, ERR_DEVICE = -1, -2, -3, -4, -5, -6
 
@@ -509,18 +573,130 @@ class Backend:
                                      focus_dist, exposure[0], exposure[1], C.byref(cam)))
         return cam
 
-    def par_cast_multi(self, scenes, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, **kw):
+    def par_cast_multi(self, scenes, camera, nx, ny, ns, seed=0xDEADBEEF, stats=False, out=None, counters=None, **kw):
         """rtg_par_cast_multi: one scene handle per device (the same world flattened on each), tiles sharded over
         them, ONE RCCL reduce(sum) of the float3 framebuffer inside the library.  Returns the assembled frame.
-        resume=True, sample_begin=k: `out` holds the running sum of samples [0, k) (as a partial=True call left it)."""
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats else 0, **kw)
+        resume=True, sample_begin=k: `out` holds the running sum of samples [0, k) (as a partial=True call left it).
+        With scene option "multi_planes" on a handle the call also takes the flagged frames of Scene.par_cast: out= a
+        CountsFrame, DenoiseFrame or FeaturesFrame is rendered in place and returned, its flags those of the parts it has
+        (denoise= / features= other than True replace the blocks' in-fields first, retire= a Retire those of its block); a
+        [2, ny, nx, 3] array with squares=True as before; and counts= an array, retire= a Retire, denoise= / features= a
+        block or a dict beside an array `out` go through a staging frame as in Scene.par_cast (a denoise / features call
+        returns that frame).  Plain flags beside a plain array (counts=True, ...) are forwarded to the library as they are.
+        stats=True returns (frame, rtg_stats as a dict), with the instrumented counters unless counters=False."""
+        counts, retire, denoise, features = kw.get("counts"), kw.get("retire"), kw.get("denoise"), kw.get("features")
+        if (isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame)) or isinstance(counts, np.ndarray) or isinstance(retire, Retire)
+                or isinstance(denoise, (dict, Denoise)) or isinstance(features, (dict, Features))):
+            return self._par_cast_multi_planes(scenes, camera, nx, ny, ns, seed, stats, out, counters, kw)
+        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters is not False else 0, **kw)
         out = _host_frame(out, nx, ny, kw)
+        st = self._par_cast_multi_call(scenes, camera, p, out)
+        return (out, st.as_dict()) if stats else out
+
+    def _par_cast_multi_call(self, scenes, camera, p, buf):
         st = Stats()
         st.struct_size = C.sizeof(Stats)
         arr = (C.c_void_p * len(scenes))(*[s.h for s in scenes])
-        self.check(self._par_cast_multi(arr, len(scenes), C.byref(camera), C.byref(p), out.ctypes.data_as(c_f32p),
-                                        C.byref(st)))
-        return (out, st.as_dict()) if stats else out
+        self.check(self._par_cast_multi(arr, len(scenes), C.byref(camera), C.byref(p), buf.ctypes.data_as(c_f32p), C.byref(st)))
+        return st
+
+    def _par_cast_multi_planes(self, scenes, camera, nx, ny, ns, seed, stats, out, counters, kw):
+        """par_cast_multi on a frame object (in place) or through a staging frame: every check is made before the library call."""
+        kw = dict(kw)
+        counts, retire, denoise, features = (kw.pop(k, None) for k in ("counts", "retire", "denoise", "features"))
+        squares = kw.pop("squares", None)
+        has_dn = denoise is not None and denoise is not False
+        has_ft = features is not None and features is not False
+        in_place = isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame))
+        if in_place:
+            f = out
+            if f.planes.shape[-3:] != (ny, nx, 3):
+                raise ValueError("out= is a %s of another size" % type(f).__name__)
+            if isinstance(counts, np.ndarray):
+                raise ValueError("out= a %s brings its own counts view" % type(f).__name__)
+            f_dn, f_ft = getattr(f, "denoise", None), getattr(f, "features", None)
+            if squares is not None and bool(squares) != (f.planes.ndim == 4):
+                raise ValueError("out= a %s: squares= must say what the frame holds" % type(f).__name__)
+            if (has_dn and f_dn is None) or (has_ft and f_ft is None) or (retire is not None and retire is not False and f.retire is None):
+                raise ValueError("out= a %s has no such block" % type(f).__name__)
+            if isinstance(retire, Retire):
+                C.memmove(C.addressof(f.retire), C.addressof(retire), Retire.active.offset)
+            if has_dn and denoise is not True:
+                block = make_denoise(denoise)
+                C.memmove(C.addressof(f_dn), C.addressof(block), Denoise.OUT_OFFSET)
+            if has_ft and features is not True:
+                block = make_features(features)
+                C.memmove(C.addressof(f_ft), C.addressof(block), Features.OUT_OFFSET)
+            flags = {"squares": f.planes.ndim == 4, "counts": f.counts is not None, "retire": f.retire is not None,
+                     "denoise": f_dn is not None, "features": f_ft is not None}
+        else:
+            if counts is not None and not isinstance(counts, np.ndarray):
+                raise ValueError("counts= must be a uint32 array beside retire= / denoise= / features= blocks (or pass a frame as out=)")
+            if retire is not None and (not isinstance(retire, Retire) or counts is None or not squares):
+                raise ValueError("retire= needs a Retire, squares=True and counts= a uint32 array (the call writes it)")
+            if has_dn and not squares:
+                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
+            if counts is not None and np.asarray(counts).shape != (ny, nx):
+                raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+            sq = {"squares": True} if squares else {}
+            if out is None and _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
+            if has_ft:
+                f = FeaturesFrame(nx, ny, squares, counts is not None, retire is not None, denoise if has_dn else None,
+                                  None if features is True else features)
+            elif has_dn:
+                f = DenoiseFrame(nx, ny, counts is not None, retire is not None, None if denoise is True else denoise)
+            else:
+                f = None
+            if f is None:   # counts (and retire) alone: in place when `out` and `counts` are one CountsFrame's views
+                out = _host_frame(out, nx, ny, sq)
+                dst, f = _counts_call(out, counts, nx, ny, squares, retire)
+                buf = dst if f is None else f.buf
+            else:
+                if out is not None:
+                    f.planes[...] = _host_frame(out, nx, ny, sq)
+                if counts is not None:
+                    f.counts[...] = counts
+                if retire is not None:
+                    C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
+                buf = f.buf
+            flags = {"squares": bool(squares), "counts": counts is not None, "retire": retire is not None, "denoise": has_dn,
+                     "features": has_ft}
+        if in_place:
+            buf = f.buf
+        for part, check in ((flags["squares"], _squares_supported), (flags["counts"], _counts_supported),
+                            (flags["retire"], _retire_supported), (flags["denoise"], _denoise_supported),
+                            (flags["features"], _features_supported)):
+            if part:
+                check(self)
+        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters is not False else 0, **flags, **kw)
+        st = self._par_cast_multi_call(scenes, camera, p, buf)
+        if in_place:
+            ret = f
+        else:
+            if f is not None and out is not None:
+                out[...] = f.planes
+            if f is not None and retire is not None:   # (the library wrote the count plane and the block's out-fields)
+                counts[...] = f.counts
+                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
+            ret = f if (has_dn or has_ft) else out
+        return (ret, st.as_dict()) if stats else ret
+
+    def adaptive_multi(self, scenes, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
+                       stats=None, radius=0, denoise=None, features=None, **kw):
+        """Scene.adaptive's host-frame loop over several handles (scene option "multi_planes" on one of them): every slice is
+        one par_cast_multi call, the retire rule is noise.retire on the host, and the loop yields the same tuples --
+        (counts, preview, stderr), then the filtered frame with denoise=, then the FeaturesFrame with features=."""
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        if not 0 <= radius <= RETIRE_MAX_RADIUS:
+            raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
+        _squares_supported(self)
+        _counts_supported(self)
+        features = make_features(None if features is True else features) if features is not None and features is not False else None
+        denoise = make_denoise(None if denoise is True else denoise) if denoise is not None and denoise is not False else None
+        yield from _adaptive_host(lambda n, **k: self.par_cast_multi(scenes, camera, nx, ny, n, **k), nx, ny, ns, step,
+                                  target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw)
 
     def multi_reset(self, rccl_library=None):
         """rtg_multi_reset: drop the cached RCCL communicators, unload librccl, choose the library to load next (None =
@@ -697,7 +873,7 @@ class Scene:
     # measurement / test hook: RTG_<OPTION>=<int> in the environment of the PYTHON process becomes
     # rtg_scene_set_option(scene, "<option>", <int>) -- the library itself reads no environment variable
     ENV_OPTIONS = ("kernel", "chunks", "lpt", "lpt_phase1", "lpt_deep", "lpt_shift", "ray_lds", "sync", "block", "wg_per_cu", "window",
-                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "force_rccl", "multi_gather", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push")
+                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push")
 
     def set_option(self, name, value):
         self.be.check(self.be._scene_set_option(self.h, name.encode(), int(value)))
@@ -1045,66 +1221,8 @@ class Scene:
             yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
                                              radius, preview, stream, kw, denoise, denoised, features)
             return
-        if features is not None:
-            f = FeaturesFrame(nx, ny, squares=True, counts=True, denoise=denoise) if out is None else out
-            if (not isinstance(f, FeaturesFrame) or f.counts is None or f.retire is not None or not f.squares
-                    or (f.denoise is None) != (denoise is None)):
-                raise ValueError("features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)")
-            C.memmove(C.addressof(f.features), C.addressof(features), Features.OUT_OFFSET)
-            if denoise is not None:
-                C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
-        elif denoise is not None:
-            f = DenoiseFrame(nx, ny, counts=True) if out is None else out
-            if not isinstance(f, DenoiseFrame) or f.counts is None or f.retire is not None:
-                raise ValueError("denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)")
-            C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
-        else:
-            f = CountsFrame(nx, ny, squares=True) if out is None else out
-            if not isinstance(f, CountsFrame):
-                raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
-        more = () if features is None else (f,)
-        if f.planes.shape != (2, ny, nx, 3):
-            raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
-        f.counts[...] = ns
-        active = np.ones((ny, nx), dtype=bool)
-        t0 = time.perf_counter()
-        done = 0
-        while done < ns:
-            end = min(ns, done + step)
-            if features is not None:
-                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f, denoise=True if denoise is not None else None,
-                                      features=True, sample_begin=done, resume=True, partial=True, squares=True, stats=True,
-                                      counters=False, **kw)
-                f.features.compute = 0   # (the planes are traced once)
-            elif denoise is not None:
-                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f, denoise=True, sample_begin=done, resume=True,
-                                      partial=True, squares=True, stats=True, counters=False, **kw)
-            else:
-                _, st = self.par_cast(camera, nx, ny, end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True,
-                                      partial=True, squares=True, stats=True, counters=False, **kw)
-            if stats is not None:
-                stats.append(st)
-            done = end
-            held = np.minimum(f.counts, done).astype(np.uint32)
-            se = noise.standard_error_counts(f.planes[0], f.planes[1], held)
-            if radius:
-                retire = noise.retire(active, done, se, min_samples, target_se, radius=radius, present=f.counts > 0)
-            else:
-                retire = noise.retire(active, done, se, min_samples, target_se)
-            f.counts[retire] = done
-            active &= ~retire
-            pv = CountsFrame(nx, ny)   # resolve a copy: the running sums go on
-            pv.planes[...] = f.planes[0]
-            pv.counts[...] = held
-            self.par_cast(camera, nx, ny, done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
-            if denoise is not None:
-                yield (held, pv.planes, se, f.denoised.copy()) + more
-            else:
-                yield (held, pv.planes, se) + more
-            if not active.any():
-                return
-            if budget_s is not None and time.perf_counter() - t0 >= budget_s:
-                return
+        yield from _adaptive_host(lambda n, **k: self.par_cast(camera, nx, ny, n, **k), nx, ny, ns, step, target_se,
+                                  min_samples, budget_s, out, seed, stats, radius, denoise, features, kw)
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
                          stream, kw, denoise=None, denoised=None, features=None):

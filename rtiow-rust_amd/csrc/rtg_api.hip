@@ -23,6 +23,7 @@
 #include "rt_retire.h"
 #include "rt_denoise.h"
 #include "rt_features.h"
+#include "rt_multi_planes.h"
 #include "rt_pool_full.h"
 #include "rt_sync_full.h"
 #include "rt_pool2.h"
@@ -120,6 +121,9 @@ struct rtg_scene {
   size_t pack_bytes = 0;
   float* d_recv = nullptr;     // ... and where they arrive on the first device
   size_t recv_bytes = 0;
+  int multi_planes = 0;        // rtg_par_cast_multi: 1 = accept the flagged frames (SUM_SQUARES .. FEATURES): every plane gathered on the first device, which retires, filters and divides (rtg_multi.inc par_cast_multi_planes_body)
+  hipEvent_t post0 = nullptr, post1 = nullptr;  // ... the first device's span for that step (rtg_stats.kernel_ms), created on first use
+  hipEvent_t pack0 = nullptr, pack1 = nullptr, unpack0 = nullptr;  // ... option verbose: this scene's pack kernel, and where the first device's unpack kernels begin (they end at post0)
   int bvh4 = 0;                // 1: traverse the 4-wide collapse of the Bvh (same image, other counters; needs wide_bytes)
   uint32_t wide_bytes = 0;     // size of the 4-wide image in buffers[7], 0 = the scene has none
   int box_chains = 1;          // production launches of the lean pool kernel stage the image without box-chain followers (rt_pool.h); 0 = off
@@ -233,9 +237,8 @@ static SampleSlice slice_of(const rtg_params* p) {
   return sl;
 }
 
-// RTG_FLAG_RETIRE: the retire block's word offset in the framebuffer (7 nx ny words of planes and counts, rounded up to an even
-// word: 8-byte aligned), and why its in-fields are refused (nullptr: accepted)
-static uint64_t retire_block_word(uint32_t nx, uint32_t ny) { return ((uint64_t)7 * nx * ny + 1u) & ~1ull; }
+// The frame layout (retire_block_word, denoise_block_word, features_block_word) is rt_multi_planes.h's host part.
+// RTG_FLAG_RETIRE: why the block's in-fields are refused (nullptr: accepted)
 static const char* retire_refusal(const rtg_retire& r, uint32_t nranks) {
   if (r.radius > RTG_RETIRE_MAX_RADIUS) return "RTG_FLAG_RETIRE: radius > RTG_RETIRE_MAX_RADIUS";
   if (!(r.target_se >= 0.0)) return "RTG_FLAG_RETIRE: target_se is NaN or negative";
@@ -243,13 +246,7 @@ static const char* retire_refusal(const rtg_retire& r, uint32_t nranks) {
   return nullptr;
 }
 
-// RTG_FLAG_DENOISE: the denoise block's word offset in the framebuffer -- the first even word behind the planes (6 nx ny words),
-// the count plane (7 nx ny) or the retire block (its word + 16) -- the output plane 16 words behind it, and why the block's
-// in-fields are refused (nullptr: accepted)
-static uint64_t denoise_block_word(uint32_t nx, uint32_t ny, bool counts, bool retire) {
-  if (retire) return retire_block_word(nx, ny) + 16u;
-  return ((uint64_t)(counts ? 7 : 6) * nx * ny + 1u) & ~1ull;
-}
+// RTG_FLAG_DENOISE: why the block's in-fields are refused (nullptr: accepted)
 static const char* denoise_refusal(const rtg_denoise& r, uint32_t nranks) {
   if (r.radius > RTG_DENOISE_MAX_RADIUS) return "RTG_FLAG_DENOISE: radius > RTG_DENOISE_MAX_RADIUS";
   if (r.patch > RTG_DENOISE_MAX_PATCH) return "RTG_FLAG_DENOISE: patch > RTG_DENOISE_MAX_PATCH";
@@ -259,16 +256,7 @@ static const char* denoise_refusal(const rtg_denoise& r, uint32_t nranks) {
   return nullptr;
 }
 
-// RTG_FLAG_FEATURES: the features block's word offset in the framebuffer -- the first even word behind everything the other
-// flags put there: the float planes, the count plane, the retire block or the denoise output plane -- the albedo plane 16 words
-// behind it, then the normal and the depth plane; and why the block's in-fields are refused (nullptr: accepted)
-static uint64_t features_block_word(uint32_t nx, uint32_t ny, const SampleSlice& sl) {
-  const uint64_t n = (uint64_t)nx * ny;
-  uint64_t end = (sl.squares ? 6u : 3u) * n + (sl.counts ? n : 0u);
-  if (sl.retire) end = retire_block_word(nx, ny) + 16u;
-  if (sl.denoise) end = denoise_block_word(nx, ny, sl.counts, sl.retire) + 16u + 3u * n;
-  return (end + 1u) & ~1ull;
-}
+// RTG_FLAG_FEATURES: why the block's in-fields are refused (nullptr: accepted)
 static const char* features_refusal(const rtg_features& r, bool denoise) {
   if (r.grid == 0u || r.grid > RTG_FEATURES_MAX_GRID) return "RTG_FLAG_FEATURES: grid is 0 or > RTG_FEATURES_MAX_GRID";
   if (r.compute > 1u) return "RTG_FLAG_FEATURES: compute > 1";
@@ -554,6 +542,10 @@ void rtg_scene_destroy(rtg_scene* s) {
   if (s->d_frame) (void)hipFree(s->d_frame);
   if (s->d_pack) (void)hipFree(s->d_pack);
   if (s->d_recv) (void)hipFree(s->d_recv);
+  if (s->post0) (void)hipEventDestroy(s->post0);
+  if (s->post1) (void)hipEventDestroy(s->post1);
+  for (hipEvent_t ev : {s->pack0, s->pack1, s->unpack0})
+    if (ev) (void)hipEventDestroy(ev);
   if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
   delete s;
 }
@@ -697,6 +689,7 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   }
   else if (k == "force_rccl") s->force_rccl = value;
   else if (k == "multi_gather") s->multi_gather = value;        // rtg_par_cast_multi: the packed collective (1 / n of the bytes per scene) instead of the reduce
+  else if (k == "multi_planes") s->multi_planes = value;        // rtg_par_cast_multi: accept the flagged frames (include/rtiow_gpu.h, at rtg_par_cast_multi)
   else if (k == "sync") s->sync_full = value;
   else if (k == "block") {
     if (value < 64 || value > 1024 || value % 64) return fail(RTG_ERR_INVALID, "block: a multiple of 64 in [64, 1024]");
@@ -919,6 +912,86 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   return RTG_OK;
 }
 
+// ---- what rtg_par_cast does around rtg_par_cast_device, shared with rtg_par_cast_multi's flagged frames (rtg_multi.inc) ------
+// The host copies of a flagged frame's blocks, checked: the refusals of include/rtiow_gpu.h for a call of `nranks` ranks, made
+// before anything is uploaded or enqueued.
+struct FrameBlocks {
+  rtg_retire retire{};
+  rtg_denoise denoise{};
+  rtg_features features{};
+};
+// Byte offsets and sizes of the parts of a host frame (rt_multi_planes.h: the layout)
+struct FrameLayout {
+  size_t bytes = 0;        // the float planes: one, or two under RTG_FLAG_SUM_SQUARES
+  size_t count_bytes = 0;  // the count plane behind them (RTG_FLAG_SAMPLE_COUNTS)
+  size_t block_bytes = 0, dblock_bytes = 0, fblock_bytes = 0;  // where the retire / denoise / features block starts (0: no such block)
+  size_t plane_bytes = 0, fplanes_bytes = 0;                   // the denoise output plane; the three feature planes
+  size_t in_bytes = 0;     // everything in front of the features block
+  size_t frame_bytes = 0;  // the whole frame
+};
+static FrameLayout frame_layout(uint32_t nx, uint32_t ny, const SampleSlice& sl) {
+  FrameLayout L;
+  const size_t n = (size_t)nx * ny;
+  L.bytes = n * 3 * sizeof(float) * (sl.squares ? 2 : 1);
+  L.count_bytes = sl.counts ? n * sizeof(uint32_t) : 0;
+  L.block_bytes = sl.retire ? retire_block_word(nx, ny) * sizeof(float) : 0;
+  L.dblock_bytes = sl.denoise ? denoise_block_word(nx, ny, sl.counts, sl.retire) * sizeof(float) : 0;
+  L.fblock_bytes = sl.features ? features_block_word(nx, ny, sl) * sizeof(float) : 0;
+  L.plane_bytes = n * 3 * sizeof(float), L.fplanes_bytes = n * 7 * sizeof(float);
+  L.in_bytes = sl.denoise ? L.dblock_bytes + sizeof(rtg_denoise) + L.plane_bytes : sl.retire ? L.block_bytes + sizeof(rtg_retire) : L.bytes + L.count_bytes;
+  L.frame_bytes = sl.features ? L.fblock_bytes + sizeof(rtg_features) + L.fplanes_bytes : L.in_bytes;
+  return L;
+}
+static int check_blocks(const FrameLayout& L, const SampleSlice& sl, const float* out_rgb, uint32_t nranks, FrameBlocks* fb) {
+  const char* base = reinterpret_cast<const char*>(out_rgb);
+  if (sl.retire) {
+    memcpy(&fb->retire, base + L.block_bytes, sizeof(rtg_retire));
+    if (const char* why = retire_refusal(fb->retire, nranks)) return fail(RTG_ERR_INVALID, why);
+  }
+  if (sl.denoise) {
+    memcpy(&fb->denoise, base + L.dblock_bytes, sizeof(rtg_denoise));
+    if (const char* why = denoise_refusal(fb->denoise, nranks)) return fail(RTG_ERR_INVALID, why);
+  }
+  if (sl.features) {
+    memcpy(&fb->features, base + L.fblock_bytes, sizeof(rtg_features));
+    if (const char* why = features_refusal(fb->features, sl.denoise)) return fail(RTG_ERR_INVALID, why);
+  }
+  return RTG_OK;
+}
+// Byte ranges [lo, hi) of a frame, at most four
+struct Extents {
+  struct { size_t lo, hi; } e[4];
+  int n = 0;
+  void add(size_t lo, size_t hi) {
+    if (hi > lo) e[n].lo = lo, e[n].hi = hi, n++;
+  }
+};
+// What travels to the device before the call.  `other_ranks` (nranks > 1): pixels of other ranks must come back as the caller
+// left them.  A single rank overwrites every pixel -- unless it resumes a progressive frame, whose running sums are in the
+// frame, or renders per-pixel counts (pixels with n_p = 0 stay as they are).  Under RTG_FLAG_SAMPLE_COUNTS the count plane
+// travels with the float planes, under RTG_FLAG_RETIRE / RTG_FLAG_DENOISE their blocks (and the output plane: pixels with
+// e_p = 0 keep what it held).
+static Extents upload_extents(const FrameLayout& L, const SampleSlice& sl, bool other_ranks, uint32_t features_compute) {
+  Extents x;
+  if (other_ranks || sl.begin != 0u || sl.counts) x.add(0, L.in_bytes);
+  else if (sl.denoise) x.add(L.dblock_bytes, L.dblock_bytes + sizeof(rtg_denoise));  // (the block alone: a whole frame without counts writes every pixel of every plane)
+  // the features block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other
+  // ranks' pixels must come back as the caller left them
+  if (sl.features) x.add(L.fblock_bytes, L.fblock_bytes + sizeof(rtg_features) + (other_ranks || (features_compute == 0u && sl.denoise) ? L.fplanes_bytes : 0));
+  return x;
+}
+// ... and back afterwards: the float planes; under RTG_FLAG_RETIRE the count plane and the block's out-fields (active ..
+// samples_held); under RTG_FLAG_DENOISE the out-fields (filtered .. reserved) and the output plane behind them; under
+// RTG_FLAG_FEATURES the out-fields (traced .. reserved) and, when this call traced them, the planes behind them
+static Extents copy_back_extents(const FrameLayout& L, const SampleSlice& sl, uint32_t features_compute) {
+  Extents x;
+  x.add(0, sl.retire ? L.bytes + L.count_bytes : L.bytes);
+  if (sl.retire) x.add(L.block_bytes + offsetof(rtg_retire, active), L.block_bytes + offsetof(rtg_retire, reserved2));
+  if (sl.denoise) x.add(L.dblock_bytes + offsetof(rtg_denoise, filtered), L.in_bytes);
+  if (sl.features) x.add(L.fblock_bytes + offsetof(rtg_features, traced), L.fblock_bytes + sizeof(rtg_features) + (features_compute ? L.fplanes_bytes : 0));
+  return x;
+}
+
 int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* params, float* out_rgb, rtg_stats* stats) {
   if (!s || !params || !out_rgb) return fail(RTG_ERR_INVALID, "null argument");
   {
@@ -927,71 +1000,24 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     if (rc0) return rc0;
   }
   const SampleSlice sl = slice_of(params);
-  // RTG_FLAG_RETIRE: the block's in-fields are checked here, before anything is uploaded
-  const size_t block_bytes = sl.retire ? retire_block_word(params->nx, params->ny) * sizeof(float) : 0;
-  if (sl.retire) {
-    rtg_retire r;
-    memcpy(&r, reinterpret_cast<const char*>(out_rgb) + block_bytes, sizeof(r));
-    if (const char* why = retire_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
-  }
-  // RTG_FLAG_DENOISE: likewise; the block and the output plane end the frame
-  const size_t dblock_bytes = sl.denoise ? denoise_block_word(params->nx, params->ny, sl.counts, sl.retire) * sizeof(float) : 0;
-  const size_t plane_bytes = (size_t)params->nx * params->ny * 3 * sizeof(float);
-  if (sl.denoise) {
-    rtg_denoise r;
-    memcpy(&r, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(r));
-    if (const char* why = denoise_refusal(r, params->nranks ? params->nranks : 1u)) return fail(RTG_ERR_INVALID, why);
-  }
-  // RTG_FLAG_FEATURES: likewise; the block and the three feature planes end the frame
-  const size_t fblock_bytes = sl.features ? features_block_word(params->nx, params->ny, sl) * sizeof(float) : 0;
-  const size_t fplanes_bytes = (size_t)params->nx * params->ny * 7 * sizeof(float);
-  rtg_features fin{};
-  if (sl.features) {
-    memcpy(&fin, reinterpret_cast<const char*>(out_rgb) + fblock_bytes, sizeof(fin));
-    if (const char* why = features_refusal(fin, sl.denoise)) return fail(RTG_ERR_INVALID, why);
-  }
+  const FrameLayout L = frame_layout(params->nx, params->ny, sl);
+  // the blocks' in-fields are checked here, before anything is uploaded
+  FrameBlocks fb;
+  if (int rc0 = check_blocks(L, sl, out_rgb, params->nranks ? params->nranks : 1u, &fb)) return rc0;
   HIP_TRY(hipSetDevice(s->device));
-  // (two planes under RTG_FLAG_SUM_SQUARES: the sum and the sum of squares; RTG_FLAG_SAMPLE_COUNTS adds the count plane, which
-  // travels to the device and is copied back only under RTG_FLAG_RETIRE, together with the out-fields of the retire block)
-  size_t bytes = (size_t)params->nx * params->ny * 3 * sizeof(float) * (sl.squares ? 2 : 1);
-  const size_t count_bytes = sl.counts ? (size_t)params->nx * params->ny * sizeof(uint32_t) : 0;
-  const size_t in_bytes = sl.denoise ? dblock_bytes + sizeof(rtg_denoise) + plane_bytes : sl.retire ? block_bytes + sizeof(rtg_retire) : bytes + count_bytes;
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
-  const size_t frame_bytes = sl.features ? fblock_bytes + sizeof(rtg_features) + fplanes_bytes : in_bytes;
-  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, frame_bytes ? frame_bytes : 16);
+  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.frame_bytes ? L.frame_bytes : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
   float* d_out = s->d_frame;
-  // pixels of other ranks stay as the caller left them; a single rank overwrites every pixel -- unless it resumes a progressive
-  // frame, whose running sums are in out_rgb, or renders per-pixel counts (pixels with n_p = 0 stay as they are)
-  const bool upload = params->nranks > 1 || sl.begin != 0u || sl.counts;
-  if (upload) e = hipMemcpy(d_out, out_rgb, in_bytes, hipMemcpyHostToDevice);
-  else if (sl.denoise)  // (the block alone: a whole frame without counts writes every pixel of every plane)
-    e = hipMemcpy(reinterpret_cast<char*>(d_out) + dblock_bytes, reinterpret_cast<const char*>(out_rgb) + dblock_bytes, sizeof(rtg_denoise), hipMemcpyHostToDevice);
-  if (e == hipSuccess && sl.features) {
-    // the block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other ranks'
-    // pixels must come back as the caller left them
-    const bool planes = params->nranks > 1 || (fin.compute == 0u && sl.denoise);
-    e = hipMemcpy(reinterpret_cast<char*>(d_out) + fblock_bytes, reinterpret_cast<const char*>(out_rgb) + fblock_bytes,
-                  sizeof(rtg_features) + (planes ? fplanes_bytes : 0), hipMemcpyHostToDevice);
-  }
+  char* dev = reinterpret_cast<char*>(d_out);
+  char* host = reinterpret_cast<char*>(out_rgb);
+  const Extents up = upload_extents(L, sl, params->nranks > 1, fb.features.compute);
+  for (int i = 0; i < up.n && e == hipSuccess; i++) e = hipMemcpy(dev + up.e[i].lo, host + up.e[i].lo, up.e[i].hi - up.e[i].lo, hipMemcpyHostToDevice);
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sl.retire ? bytes + count_bytes : bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && sl.retire) {  // the out-fields only: active .. samples_held
-      const size_t lo = offsetof(rtg_retire, active), hi = offsetof(rtg_retire, reserved2);
-      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + block_bytes + lo, reinterpret_cast<const char*>(d_out) + block_bytes + lo, hi - lo,
-                    hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess && sl.denoise) {  // the out-fields (filtered .. reserved) and the output plane behind them
-      const size_t lo = dblock_bytes + offsetof(rtg_denoise, filtered);
-      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + lo, reinterpret_cast<const char*>(d_out) + lo, in_bytes - lo, hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess && sl.features) {  // the out-fields (traced .. reserved) and, when this call traced them, the planes behind them
-      const size_t lo = fblock_bytes + offsetof(rtg_features, traced);
-      const size_t hi = fblock_bytes + sizeof(rtg_features) + (fin.compute ? fplanes_bytes : 0);
-      e = hipMemcpy(reinterpret_cast<char*>(out_rgb) + lo, reinterpret_cast<const char*>(d_out) + lo, hi - lo, hipMemcpyDeviceToHost);
-    }
+    const Extents back = copy_back_extents(L, sl, fb.features.compute);
+    for (int i = 0; i < back.n && e == hipSuccess; i++) e = hipMemcpy(host + back.e[i].lo, dev + back.e[i].lo, back.e[i].hi - back.e[i].lo, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = hip_fail(e, "render / copy back");
   }
   return rc;

@@ -531,6 +531,15 @@ static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t s
   return hipGetLastError();
 }
 
+// ... and of a counts frame: every owned pixel with e_p > 0 divided by e_p = min(n_p, ns)
+static hipError_t launch_resolve_counts(const DevParams& d, float* d_out, hipStream_t stream, const uint32_t* counts) {
+  const uint64_t pix_work = rank_pix_work(d);
+  if (pix_work == 0) return hipSuccess;
+  if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(resolve_counts_kernel, dim3((uint32_t)(pix_work / 256u)), dim3(256), 0, stream, d, make_pixmap(d), (uint32_t)pix_work, d_out, counts);
+  return hipGetLastError();
+}
+
 // RTG_FLAG_RETIRE (include/rtiow_gpu.h): the retire step of a counts call over this rank's work items (rt_retire.h) -- mark the
 // OK bits and the estimate's partials, retire the candidates whose window is OK, sum the partials into the caller's block.
 // `r`: the block's in-fields, already validated.  A rank without work items (pix_work = 0) only writes the block's zeros.
@@ -745,9 +754,7 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &fin : nullptr);
     if (e != hipSuccess) return e;
   }
-  if (!sl.divide || pix_work == 0) return hipSuccess;
-  hipLaunchKernelGGL(resolve_counts_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, d_out, ls.list.counts);
-  return hipGetLastError();
+  return sl.divide ? launch_resolve_counts(d, d_out, stream, ls.list.counts) : hipSuccess;
 }
 
 // `sl` (rtg_api.hip SampleSlice): the samples of a progressive frame this call renders; the default is the whole frame.

@@ -124,6 +124,14 @@ int rccl_gather_tiles(const std::vector<int>& devs, const std::vector<rtg_scene*
   std::lock_guard<std::mutex> lock(g_rccl.mu);
   if (int rc = rccl_load()) return rc;
   if (!g_rccl.Send || !g_rccl.Recv) return fail(RTG_ERR_DEVICE, "librccl lacks ncclSend / ncclRecv (the packed collective needs them)");
+  // every move is checked before the group opens: an argument error must not leave a half-issued group behind
+  if (devs.empty() || heads.size() != devs.size() || !heads[0] || !heads[0]->own_stream) return fail(RTG_ERR_INVALID, "packed collective: no first device");
+  for (const PackedMove& m : moves) {
+    if (!m.src || !m.dst) return fail(RTG_ERR_INVALID, "packed collective: a move without a buffer");
+    if (m.n_floats == 0) return fail(RTG_ERR_INVALID, "packed collective: an empty move");
+    if (m.from < 0 || (size_t)m.from >= devs.size()) return fail(RTG_ERR_INVALID, "packed collective: a move from a device outside the clique");
+    if (!m.src_stream) return fail(RTG_ERR_INVALID, "packed collective: a move without a stream");
+  }
   return rccl_group(devs, [&](const std::vector<ncclComm_t>& comms, std::string& err) {
     for (size_t k = 0; k < moves.size() && err.empty(); k++) {
       const PackedMove& m = moves[k];
@@ -367,6 +375,189 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
   HIP_TRY(hipMemcpy(out_rgb, heads[0]->d_frame, bytes, hipMemcpyDeviceToHost));
   return multi_stats(scenes, n_scenes, camera, params, stats, count);
 }
+
+// The flagged frames (scene option multi_planes; include/rtiow_gpu.h at rtg_par_cast_multi): RTG_FLAG_SUM_SQUARES, SAMPLE_COUNTS,
+// RETIRE, DENOISE and FEATURES over several handles.
+// (0) the refusals of rtg_par_cast with nranks = 1, on the host copy of the blocks;
+// (1) every scene renders ITS tiles as a PARTIAL slice (squares / counts as given) into its own frame of the full layout, and
+//     traces the feature pass for the pixels it owns -- no retire rule, no filter, no division.  A rank's launch holds at most
+//     one host wait (a counts call's compaction), so launching the ranks in turn keeps the devices busy;
+// (2) the packed collective over EVERY plane the ranks wrote (rt_multi_planes.h PlaneSet: one pack kernel, one ncclSend /
+//     ncclRecv pair and one unpack kernel per handle that travels; handles on the first device are unpacked from their own
+//     buffer) assembles the frame on the first device.  Copies only;
+// (3) the first device runs what a one-handle call with sample_begin == ns runs on that frame: launch_retire (any radius: the
+//     window sees the whole frame), launch_denoise (guided over the gathered feature planes), the division;
+// (4) copy back what rtg_par_cast copies back; traced / missed of the features block are the sums over the ranks.
+int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params, float* out_rgb,
+                               rtg_stats* stats) {
+  const SampleSlice sl = slice_of(params);
+  DevParams d1;  // the one-handle call's parameters (nranks = 1, the caller's tiles): the first device's step runs over them
+  if (int rc = check_params(scenes[0], camera, params, &d1)) return rc;
+  const FrameLayout L = frame_layout(params->nx, params->ny, sl);
+  FrameBlocks fb;
+  if (int rc = check_blocks(L, sl, out_rgb, 1u, &fb)) return rc;
+  const uint32_t compute = sl.features ? fb.features.compute : 0u;
+  const PlaneSet ps = make_plane_set(params->nx, params->ny, sl, compute != 0u);
+  rtg_params rp = *params;  // what the ranks render: the slice, never resolved
+  rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_FEATURES)) | RTG_FLAG_PARTIAL;
+  const SampleSlice rsl = slice_of(&rp);
+  const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
+  const DevCamera cam = to_dev(camera);
+  char* host = reinterpret_cast<char*>(out_rgb);
+  std::vector<DevParams> dps(n_scenes);
+  for (int i = 0; i < n_scenes; i++) {
+    if (int rc = rank_params(scenes[i], camera, &rp, i, n_scenes, &dps[i])) return rc;
+    // (the pack / unpack kernels index a rank's work items with 32 bits, as launch_resolve and launch_counts do)
+    if (rank_pix_work(dps[i]) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: a rank's work items overflow the 32-bit work index");
+  }
+  if (rank_pix_work(d1) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: the frame's work items overflow the 32-bit work index");
+  uint64_t samples = 0;
+  // (1) the first scene's frame is the call's frame: uploaded as rtg_par_cast uploads it (untouched pixels and an untouched
+  // output plane survive); the others get what their slice reads -- the float planes when it resumes or renders counts (pixels
+  // with n_p = 0 must travel back as they came), and the count plane.  The feature pass takes its in-fields from the host copy.
+  Extents rank_up;
+  if (sl.begin != 0u || sl.counts) rank_up.add(0, L.bytes + L.count_bytes);
+  for (int i = 0; i < n_scenes; i++) {
+    rtg_scene* s = scenes[i];
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+    hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.frame_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
+    char* dev = reinterpret_cast<char*>(s->d_frame);
+    const Extents up = i == 0 ? upload_extents(L, sl, false, compute) : rank_up;
+    for (int k = 0; k < up.n; k++) HIP_TRY(hipMemcpyAsync(dev + up.e[k].lo, host + up.e[k].lo, up.e[k].hi - up.e[k].lo, hipMemcpyHostToDevice, s->own_stream));
+    {
+      const int rc_ctx = ctx_acquire(s);
+      if (rc_ctx) return rc_ctx;
+    }
+    if (count) {
+      HIP_TRY(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), s->own_stream));
+      HIP_TRY(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), s->own_stream));
+    }
+    HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
+    HIP_TRY(count ? launch_render<true>(s, cam, dps[i], s->d_frame, s->own_stream, rsl) : launch_render<false>(s, cam, dps[i], s->d_frame, s->own_stream, rsl));
+    // the feature pass BEHIND the render (the planes do not depend on each other): a counts call's compaction wait, the rank's
+    // one host wait, then covers no feature kernel, and the next rank is launched while this one traces (`sl`: the frame's layout)
+    if (sl.features) HIP_TRY(launch_features(s, cam, dps[i], s->d_frame, s->own_stream, sl, fb.features));
+    HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
+    samples += rsl.counts ? s->cx->counts_samples : owned_pixels(dps[i]) * (dps[i].ns - rsl.begin);
+    {
+      const int rc_ctx = ctx_release(s, s->own_stream);
+      if (rc_ctx) return rc_ctx;
+    }
+  }
+  bool force_rccl = false, verbose = false;
+  for (int i = 0; i < n_scenes; i++) force_rccl = force_rccl || scenes[i]->force_rccl != 0, verbose = verbose || scenes[i]->verbose != 0;
+  const DeviceGroups g = group_by_device(scenes, n_scenes);
+  rtg_scene* head = g.heads[0];  // (= scenes[0])
+  // (2) pack, travel, unpack
+  std::vector<PackedMove> moves;
+  std::vector<const uint32_t*> at_head(n_scenes, nullptr);  // where scene i's packed planes stand on the first device
+  for (int i = 0; i < n_scenes; i++) {
+    rtg_scene* s = scenes[i];
+    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
+    // (a clique of one under force_rccl: the first scene's planes take the send / recv path too, to itself)
+    const bool travels = g.of[i] != 0 || (force_rccl && g.devs.size() == 1 && i == 0);
+    if (pw == 0 || (s == head && !travels)) continue;  // (the first scene's own pixels already stand in the frame)
+    const size_t words = (size_t)pw * ps.words_per_pixel;
+    HIP_TRY(hipSetDevice(s->device));
+    hipError_t e = grow((void**)&s->d_pack, &s->pack_bytes, words * sizeof(uint32_t));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(packed planes)");
+    if (verbose) {
+      if (!s->pack0) HIP_TRY(hipEventCreate(&s->pack0));
+      if (!s->pack1) HIP_TRY(hipEventCreate(&s->pack1));
+      HIP_TRY(hipEventRecord(s->pack0, s->own_stream));
+    }
+    hipLaunchKernelGGL(pack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, s->own_stream, dps[i], make_pixmap(dps[i]), pw, ps,
+                       reinterpret_cast<const uint32_t*>(s->d_frame), reinterpret_cast<uint32_t*>(s->d_pack));
+    HIP_TRY(hipGetLastError());
+    if (verbose) HIP_TRY(hipEventRecord(s->pack1, s->own_stream));
+    if (travels) {
+      HIP_TRY(hipSetDevice(g.devs[0]));
+      e = grow((void**)&s->d_recv, &s->recv_bytes, words * sizeof(uint32_t));
+      if (e != hipSuccess) return hip_fail(e, "hipMalloc(received planes)");
+      moves.push_back(PackedMove{s->d_pack, s->d_recv, words, g.of[i], s->own_stream});
+      at_head[i] = reinterpret_cast<const uint32_t*>(s->d_recv);
+    } else {
+      at_head[i] = reinterpret_cast<const uint32_t*>(s->d_pack);
+      HIP_TRY(hipStreamSynchronize(s->own_stream));  // (another handle on the first device: its own stream)
+    }
+  }
+  if (!moves.empty()) {
+    int rc = rccl_gather_tiles(g.devs, g.heads, moves);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipSetDevice(head->device));
+  const hipStream_t hs = head->own_stream;
+  if (verbose) {
+    if (!head->unpack0) HIP_TRY(hipEventCreate(&head->unpack0));
+    HIP_TRY(hipEventRecord(head->unpack0, hs));
+  }
+  for (int i = 0; i < n_scenes; i++) {
+    if (!at_head[i]) continue;
+    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
+    hipLaunchKernelGGL(unpack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, hs, dps[i], make_pixmap(dps[i]), pw, ps,
+                       reinterpret_cast<uint32_t*>(head->d_frame), at_head[i]);
+    HIP_TRY(hipGetLastError());
+  }
+  // (3) the first device's step over the assembled frame, through the launch functions of the one-handle call
+  if (!head->post0) HIP_TRY(hipEventCreate(&head->post0));
+  if (!head->post1) HIP_TRY(hipEventCreate(&head->post1));
+  HIP_TRY(hipEventRecord(head->post0, hs));
+  if (sl.retire) HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire));
+  if (sl.denoise) HIP_TRY(launch_denoise(head, d1, head->d_frame, hs, sl, fb.denoise, sl.features ? &fb.features : nullptr));
+  if (sl.divide)
+    HIP_TRY(sl.counts ? launch_resolve_counts(d1, head->d_frame, hs, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(head->d_frame) + L.bytes))
+                      : launch_resolve(d1, head->d_frame, hs));
+  HIP_TRY(hipEventRecord(head->post1, hs));
+  // (4) wait, copy out
+  HIP_TRY(hipStreamSynchronize(hs));
+  for (int i = 0; i < n_scenes; i++) {
+    HIP_TRY(hipSetDevice(scenes[i]->device));
+    HIP_TRY(hipStreamSynchronize(scenes[i]->own_stream));
+  }
+  if (sl.features) {  // traced / missed: the sums over the ranks' blocks, into the first scene's before it is copied out
+    uint32_t sum[2] = {0u, 0u};
+    const size_t at = L.fblock_bytes + offsetof(rtg_features, traced);
+    for (int i = 0; i < n_scenes; i++) {
+      uint32_t tm[2] = {0u, 0u};
+      HIP_TRY(hipSetDevice(scenes[i]->device));
+      HIP_TRY(hipMemcpy(tm, reinterpret_cast<const char*>(scenes[i]->d_frame) + at, sizeof(tm), hipMemcpyDeviceToHost));
+      sum[0] += tm[0], sum[1] += tm[1];
+    }
+    HIP_TRY(hipSetDevice(head->device));
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(head->d_frame) + at, sum, sizeof(sum), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipSetDevice(head->device));
+  const Extents back = copy_back_extents(L, sl, compute);
+  for (int k = 0; k < back.n; k++)
+    HIP_TRY(hipMemcpy(host + back.e[k].lo, reinterpret_cast<const char*>(head->d_frame) + back.e[k].lo, back.e[k].hi - back.e[k].lo, hipMemcpyDeviceToHost));
+  if (verbose) {  // the pack kernels (summed over the handles) and the first device's unpack kernels, by their events
+    float pack_ms = 0.f, unpack_ms = 0.f;
+    uint64_t items = 0;
+    for (int i = 0; i < n_scenes; i++) {
+      if (!at_head[i]) continue;
+      float ms = 0.f;
+      HIP_TRY(hipSetDevice(scenes[i]->device));
+      HIP_TRY(hipEventElapsedTime(&ms, scenes[i]->pack0, scenes[i]->pack1));
+      pack_ms += ms, items += rank_pix_work(dps[i]);
+    }
+    HIP_TRY(hipSetDevice(head->device));
+    HIP_TRY(hipEventElapsedTime(&unpack_ms, head->unpack0, head->post0));
+    // (tools/multi_planes_cost.py parses this line -- VERBOSE_LINE there: change both together)
+    fprintf(stderr, "[rtg] multi planes: %d handle(s) on %zu device(s), %u words per pixel, %llu work items packed (%llu bytes), %zu through RCCL; pack %.4f ms, unpack %.4f ms\n",
+            n_scenes, g.devs.size(), ps.words_per_pixel, (unsigned long long)items, (unsigned long long)(items * ps.words_per_pixel * 4u), moves.size(), pack_ms, unpack_ms);
+  }
+  if (int rc = multi_stats(scenes, n_scenes, camera, &rp, stats, count)) return rc;
+  if (stats) {  // the slowest shard's render span + the first device's span for retire / filter / division
+    float ms = 0.f;
+    HIP_TRY(hipSetDevice(head->device));
+    HIP_TRY(hipEventElapsedTime(&ms, head->post0, head->post1));
+    stats->kernel_ms += ms;
+    stats->samples = samples;
+  }
+  return RTG_OK;
+}
 }  // namespace
 
 int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params,
@@ -376,18 +567,26 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   if (params->nranks > 1u) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi shards by itself: params.rank / nranks must be 0 / 0|1");
   if (stats && stats->struct_size != sizeof(rtg_stats)) return fail(RTG_ERR_INVALID, "rtg_stats.struct_size mismatch");
   if ((params->flags & RTG_FLAG_RESUME) && params->sample_begin > params->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
-  if (params->flags & RTG_FLAG_SUM_SQUARES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SUM_SQUARES is not supported");
-  if (params->flags & RTG_FLAG_SAMPLE_COUNTS) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SAMPLE_COUNTS is not supported");
-  if (params->flags & RTG_FLAG_RETIRE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_RETIRE is not supported");
-  if (params->flags & RTG_FLAG_DENOISE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_DENOISE is not supported");
-  if (params->flags & RTG_FLAG_FEATURES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_FEATURES is not supported");
+  // the flagged frames need scene option multi_planes on a handle (include/rtiow_gpu.h, at rtg_par_cast_multi)
+  bool planes = false;
+  for (int i = 0; i < n_scenes; i++) planes = planes || (scenes[i] && scenes[i]->multi_planes != 0);
+  if (!planes) {
+    if (params->flags & RTG_FLAG_SUM_SQUARES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SUM_SQUARES is not supported without scene option multi_planes");
+    if (params->flags & RTG_FLAG_SAMPLE_COUNTS) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SAMPLE_COUNTS is not supported without scene option multi_planes");
+    if (params->flags & RTG_FLAG_RETIRE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_RETIRE is not supported without scene option multi_planes");
+    if (params->flags & RTG_FLAG_DENOISE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_DENOISE is not supported without scene option multi_planes");
+    if (params->flags & RTG_FLAG_FEATURES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_FEATURES is not supported without scene option multi_planes");
+  }
   for (int i = 0; i < n_scenes; i++) {
     if (!scenes[i]) return fail(RTG_ERR_INVALID, "null scene handle");
     // one handle = one frame, one work queue, one stream: the same handle twice would wipe its own tiles
     for (int k = 0; k < i; k++)
       if (scenes[k] == scenes[i]) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi: the same scene handle appears twice (one handle per shard)");
   }
-  const int rc = par_cast_multi_body(scenes, n_scenes, camera, params, out_rgb, stats);
+  // a call without any of the five flags is the plain frame whatever the option says
+  const uint32_t plane_flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_FEATURES;
+  const int rc = (params->flags & plane_flags) ? par_cast_multi_planes_body(scenes, n_scenes, camera, params, out_rgb, stats)
+                                               : par_cast_multi_body(scenes, n_scenes, camera, params, out_rgb, stats);
   if (rc != RTG_OK) {
     // whatever was queued before the failure must not outlive the call (the caller may free out_rgb, destroy the handles
     // or call again): drain every stream that may hold work, keeping the first error message

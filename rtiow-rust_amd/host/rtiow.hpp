@@ -400,9 +400,9 @@ struct DenoisedImage {
   rtg_denoise block{};
 };
 
-inline DenoisedImage par_cast_denoised(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, float k = 0.7f,
-                                       uint32_t radius = 5, uint32_t patch = 2, const CastOptions& opt = CastOptions()) {
-  SceneHandle s = make_scene(world, opt);
+// (`cast(params, frame)`: rtg_par_cast on one handle, or rtg_par_cast_multi on several)
+template <typename Cast>
+inline DenoisedImage denoised_frame(size_t nx, size_t ny, size_t ns, float k, uint32_t radius, uint32_t patch, const CastOptions& opt, Cast&& cast) {
   const size_t n = nx * ny, block_word = (6 * n + 1) & ~size_t(1);  // two planes, padding to 8 bytes, the block, the output plane
   std::vector<float> frame(block_word + sizeof(rtg_denoise) / sizeof(float) + 3 * n, 0.f);
   rtg_denoise d{};
@@ -410,13 +410,19 @@ inline DenoisedImage par_cast_denoised(size_t nx, size_t ny, size_t ns, const Ca
   std::memcpy(frame.data() + block_word, &d, sizeof(d));
   rtg_params p = cast_params(nx, ny, ns, opt);
   p.flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE;
-  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  cast(p, frame.data());
   DenoisedImage out;
   out.image.nx = out.denoised.nx = nx, out.image.ny = out.denoised.ny = ny;
   out.image.rgb.assign(frame.begin(), frame.begin() + 3 * n);
   out.denoised.rgb.assign(frame.begin() + block_word + 16, frame.end());
   std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_denoise));
   return out;
+}
+
+inline DenoisedImage par_cast_denoised(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, float k = 0.7f,
+                                       uint32_t radius = 5, uint32_t patch = 2, const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  return denoised_frame(nx, ny, ns, k, radius, patch, opt, [&](const rtg_params& p, float* frame) { check(rtg_par_cast(s.get(), &camera.c, &p, frame, nullptr)); });
 }
 
 // Not in the reference: par_cast with RTG_FLAG_FEATURES.  `image` is exactly what par_cast returns; `albedo` and `normal` (three
@@ -428,9 +434,8 @@ struct FeatureImages {
   rtg_features block{};
 };
 
-inline FeatureImages par_cast_features(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, uint32_t grid = 2,
-                                       const CastOptions& opt = CastOptions()) {
-  SceneHandle s = make_scene(world, opt);
+template <typename Cast>
+inline FeatureImages features_frame(size_t nx, size_t ny, size_t ns, uint32_t grid, const CastOptions& opt, Cast&& cast) {
   const size_t n = nx * ny, block_word = (3 * n + 1) & ~size_t(1);  // one plane, padding to 8 bytes, the block, the three planes
   std::vector<float> frame(block_word + sizeof(rtg_features) / sizeof(float) + 7 * n, 0.f);
   rtg_features f{};
@@ -438,7 +443,7 @@ inline FeatureImages par_cast_features(size_t nx, size_t ny, size_t ns, const Ca
   std::memcpy(frame.data() + block_word, &f, sizeof(f));
   rtg_params p = cast_params(nx, ny, ns, opt);
   p.flags = RTG_FLAG_FEATURES;
-  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  cast(p, frame.data());
   FeatureImages out;
   out.image.nx = out.albedo.nx = out.normal.nx = nx, out.image.ny = out.albedo.ny = out.normal.ny = ny;
   const auto at = frame.begin() + block_word + 16;
@@ -448,6 +453,76 @@ inline FeatureImages par_cast_features(size_t nx, size_t ny, size_t ns, const Ca
   out.depth.assign(at + 6 * n, at + 7 * n);
   std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_features));
   return out;
+}
+
+inline FeatureImages par_cast_features(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, uint32_t grid = 2,
+                                       const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  return features_frame(nx, ny, ns, grid, opt, [&](const rtg_params& p, float* frame) { check(rtg_par_cast(s.get(), &camera.c, &p, frame, nullptr)); });
+}
+
+// Not in the reference: the frame sharded over `n_devices` GPUs of this process (rtg_par_cast_multi): `world` is flattened once
+// per device (opt.device is not used), the tiles are sharded inside the library and the frame is assembled on the first device --
+// bit-identical to par_cast.  The flagged frames (par_cast_multi_squares / _denoised / _features) set scene option multi_planes:
+// every plane is gathered on the first device, which filters and divides; they equal their one-device namesakes word for word.
+struct MultiScenes {
+  std::vector<SceneHandle> handles;
+  std::vector<rtg_scene*> raw;
+};
+inline MultiScenes make_scenes(const Scene& world, int n_devices, const CastOptions& opt, bool planes) {
+  int have = 0;
+  check(rtg_device_count(&have));
+  if (n_devices < 1 || n_devices > have) throw Error(RTG_ERR_INVALID, "par_cast_multi: n_devices must be 1 .. the devices the host has");
+  MultiScenes m;
+  for (int d = 0; d < n_devices; d++) {
+    CastOptions o = opt;
+    o.device = d;
+    m.handles.push_back(make_scene(world, o));
+    m.raw.push_back(m.handles.back().get());
+  }
+  if (planes) check(rtg_scene_set_option(m.raw[0], "multi_planes", 1));
+  return m;
+}
+
+inline Image par_cast_multi(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, int n_devices,
+                            const CastOptions& opt = CastOptions()) {
+  MultiScenes m = make_scenes(world, n_devices, opt, false);
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  Image img;
+  img.nx = nx, img.ny = ny;
+  img.rgb.assign(nx * ny * 3, 0.f);
+  check(rtg_par_cast_multi(m.raw.data(), (int)m.raw.size(), &camera.c, &p, img.rgb.data(), nullptr));
+  return img;
+}
+
+inline SquaresImage par_cast_multi_squares(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, int n_devices,
+                                           const CastOptions& opt = CastOptions()) {
+  MultiScenes m = make_scenes(world, n_devices, opt, true);
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_SUM_SQUARES;
+  std::vector<float> planes(2 * nx * ny * 3, 0.f);
+  check(rtg_par_cast_multi(m.raw.data(), (int)m.raw.size(), &camera.c, &p, planes.data(), nullptr));
+  SquaresImage r;
+  r.image.nx = nx, r.image.ny = ny, r.ns = ns;
+  r.image.rgb.assign(planes.begin(), planes.begin() + nx * ny * 3);
+  r.sum_sq.assign(planes.begin() + nx * ny * 3, planes.end());
+  return r;
+}
+
+inline DenoisedImage par_cast_multi_denoised(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, int n_devices,
+                                             float k = 0.7f, uint32_t radius = 5, uint32_t patch = 2, const CastOptions& opt = CastOptions()) {
+  MultiScenes m = make_scenes(world, n_devices, opt, true);
+  return denoised_frame(nx, ny, ns, k, radius, patch, opt, [&](const rtg_params& p, float* frame) {
+    check(rtg_par_cast_multi(m.raw.data(), (int)m.raw.size(), &camera.c, &p, frame, nullptr));
+  });
+}
+
+inline FeatureImages par_cast_multi_features(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, int n_devices,
+                                             uint32_t grid = 2, const CastOptions& opt = CastOptions()) {
+  MultiScenes m = make_scenes(world, n_devices, opt, true);
+  return features_frame(nx, ny, ns, grid, opt, [&](const rtg_params& p, float* frame) {
+    check(rtg_par_cast_multi(m.raw.data(), (int)m.raw.size(), &camera.c, &p, frame, nullptr));
+  });
 }
 
 // Standard error of a pixel channel's mean over n samples (rtiow-rust_amd/noise.py, in double): s2 = max(0, (sum_sq - n m^2) /

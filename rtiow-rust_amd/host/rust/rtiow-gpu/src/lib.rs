@@ -409,6 +409,38 @@ pub fn gpu_cast_multi<W: FlattenWorld + ?Sized>(nx: usize, ny: usize, ns: usize,
     Ok(Image { nx, ny, rgb })
 }
 
+/// The flagged frames over every GPU of the node (scene option `multi_planes` on the first handle; see the header at
+/// `rtg_par_cast_multi`): `flags` are `RTG_FLAG_*` bits and `frame` the host frame of exactly the layout `rtg_par_cast` defines
+/// for them, blocks' in-fields set by the caller.  Every plane is gathered on the first device, which retires, filters and
+/// divides: the frame ends word for word as `rtg_par_cast` on one device leaves it.  (Uncompiled, like the rest of this crate.)
+pub fn gpu_cast_multi_frame<W: FlattenWorld + ?Sized>(nx: usize, ny: usize, ns: usize, camera: &Camera, world: &W, n_devices: i32,
+                                                      flags: u32, sample_begin: u32, frame: &mut [f32]) -> Result<()> {
+    let mut b = GpuBuilder::new()?;
+    let ids = world.flatten_world(&mut b)?;
+    let mut scenes: Vec<GpuScene> = (0..n_devices).map(|d| b.scene(&ids, d)).collect::<Result<_>>()?;
+    scenes[0].set_option("multi_planes", 1)?;
+    let raws: Vec<*mut sys::rtg_scene> = scenes.iter().map(|s| s.raw).collect();
+    let mut p = params(nx, ny, ns, &CastOptions::default());
+    p.flags = flags;
+    p.sample_begin = sample_begin;
+    check(unsafe { sys::rtg_par_cast_multi(raws.as_ptr(), raws.len() as i32, &camera.0, &p, frame.as_mut_ptr(), ptr::null_mut()) })
+}
+
+/// `GpuScene::par_cast_denoised` over every GPU of the node: (image, filtered image, block), equal to the one-device call's.
+pub fn gpu_cast_multi_denoised<W: FlattenWorld + ?Sized>(nx: usize, ny: usize, ns: usize, k: f32, radius: u32, patch: u32, camera: &Camera,
+                                                         world: &W, n_devices: i32) -> Result<(Image, Image, sys::rtg_denoise)> {
+    let n = nx * ny;
+    let block_word = (6 * n + 1) & !1; // two planes, padding to 8 bytes, the block, then the output plane
+    let mut frame = vec![0f32; block_word + 16 + 3 * n];
+    let block = sys::rtg_denoise { k, radius, patch, ..Default::default() };
+    unsafe { ptr::write_unaligned(frame.as_mut_ptr().add(block_word) as *mut sys::rtg_denoise, block) };
+    gpu_cast_multi_frame(nx, ny, ns, camera, world, n_devices, sys::RTG_FLAG_SUM_SQUARES | sys::RTG_FLAG_DENOISE, 0, &mut frame)?;
+    let block = unsafe { ptr::read_unaligned(frame.as_ptr().add(block_word) as *const sys::rtg_denoise) };
+    let denoised = frame[block_word + 16..].to_vec();
+    frame.truncate(3 * n);
+    Ok((Image { nx, ny, rgb: frame }, Image { nx, ny, rgb: denoised }, block))
+}
+
 /// Forget the library's multi-GPU state: destroy the cached RCCL communicators, unload librccl (the next `gpu_cast_multi`
 /// loads it again).  Returns the number of `ncclReduce` calls issued since the last reset.
 pub fn multi_reset() -> Result<u64> {
