@@ -6,6 +6,7 @@ parameter so that a test harness can drive another library exporting the same en
 same calls.
 """
 import ctypes as C
+import math
 import os
 import time
 
@@ -55,23 +56,13 @@ class Retire(C.Structure):
                 ("active", C.c_uint32), ("retired", C.c_uint32), ("estimated", C.c_uint32), ("reserved", C.c_uint32),
                 ("sum_se2", C.c_double), ("samples_held", C.c_uint64), ("reserved2", C.c_uint64 * 2)]
     OUT_FIELDS = ("active", "retired", "estimated", "reserved", "sum_se2", "samples_held")
+    OUT_OFFSET = 16   # bytes: the in-fields end here
 
     def as_dict(self):
         """The out-fields, plus est_rmse = sqrt(sum_se2 / (3 estimated)) (inf when no pixel has an estimate)."""
         d = {k: getattr(self, k) for k in self.OUT_FIELDS}
         d["est_rmse"] = float(np.sqrt(self.sum_se2 / (3 * self.estimated))) if self.estimated else float("inf")
         return d
-
-
-def retire_block_offset(nx, ny):
-    """Byte offset of the Retire block in an RTG_FLAG_RETIRE frame: word 7 * nx * ny (two float planes and the count plane),
-    rounded up to an even word."""
-    return ((7 * nx * ny + 1) & ~1) * 4
-
-
-def retire_frame_bytes(nx, ny):
-    """Bytes of an RTG_FLAG_RETIRE frame: two float planes, the count plane, padding to 8 bytes, the 64-byte Retire block."""
-    return retire_block_offset(nx, ny) + C.sizeof(Retire)
 
 
 class Denoise(C.Structure):
@@ -101,19 +92,6 @@ def make_denoise(denoise=None, k=0.7, radius=5, patch=2):
         k, radius, patch = denoise.get("k", k), denoise.get("radius", radius), denoise.get("patch", patch)
     d.k, d.radius, d.patch = float(k), int(radius), int(patch)
     return d
-
-
-def denoise_block_offset(nx, ny, counts=False, retire=False):
-    """Byte offset of the Denoise block in an RTG_FLAG_DENOISE frame: the first even word behind the two float planes, the
-    count plane (counts=True) or the Retire block (retire=True, which implies the count plane)."""
-    if retire:
-        return retire_block_offset(nx, ny) + C.sizeof(Retire)
-    return (((7 if counts else 6) * nx * ny + 1) & ~1) * 4
-
-
-def denoise_frame_bytes(nx, ny, counts=False, retire=False):
-    """Bytes of an RTG_FLAG_DENOISE frame: everything the other flags put in it, the 64-byte Denoise block, the output plane."""
-    return denoise_block_offset(nx, ny, counts, retire) + C.sizeof(Denoise) + nx * ny * 3 * 4
 
 
 class Features(C.Structure):
@@ -152,30 +130,81 @@ def make_features(features=None, **fields):
     return f
 
 
+def _given(x):
+    """An optional part of a call or of a frame was asked for: anything but None and False."""
+    return x is not None and x is not False
+
+
+class FrameLayout:
+    """Where every part of a framebuffer starts, in 4-byte words: the one rule of include/rtiow_gpu.h, as frame_layout
+    (csrc/rtg_api.hip) and the *_block_word functions (csrc/rt_multi_planes.h) state it.  The float planes (one, or two with
+    squares) start at word 0; behind them, each only with its flag: the count plane (`counts`, n = nx * ny words), the Retire
+    block (`retire`), the Denoise block (`denoise`) and its output plane (`denoised`, 3n), the Features block (`features`) and
+    the `albedo` (3n), `normal` (3n) and `depth` (n) planes.  A block is 16 words and starts on an even word.  retire implies
+    counts and squares, denoise implies squares (the library refuses a call without them).  The offset of a part the frame
+    does not have is None; `words` is the frame's length.  Plain Python integers: exact for frames beyond 2^31 bytes."""
+
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=False, features=False):
+        n = self.n = nx * ny
+        self.nx, self.ny, self.squares = nx, ny, bool(squares or retire or denoise)
+        self.counts = self.retire = self.denoise = self.denoised = self.features = self.albedo = self.normal = self.depth = None
+        w = (6 if self.squares else 3) * n
+        if counts or retire:
+            self.counts, w = w, w + n
+        if retire:
+            self.retire = (w + 1) & ~1
+            w = self.retire + 16
+        if denoise:
+            self.denoise = (w + 1) & ~1
+            self.denoised = self.denoise + 16
+            w = self.denoised + 3 * n
+        if features:
+            self.features = (w + 1) & ~1
+            self.albedo = self.features + 16
+            self.normal, self.depth = self.albedo + 3 * n, self.albedo + 6 * n
+            w = self.depth + n
+        self.words = w
+
+
+def retire_block_offset(nx, ny):
+    """Byte offset of the Retire block in an RTG_FLAG_RETIRE frame (two float planes and the count plane in front of it)."""
+    return FrameLayout(nx, ny, retire=True).retire * 4
+
+
+def retire_frame_bytes(nx, ny):
+    """Bytes of an RTG_FLAG_RETIRE frame: it ends with the 64-byte Retire block."""
+    return FrameLayout(nx, ny, retire=True).words * 4
+
+
+def denoise_block_offset(nx, ny, counts=False, retire=False):
+    """Byte offset of the Denoise block in an RTG_FLAG_DENOISE frame, behind what counts / retire put in it."""
+    return FrameLayout(nx, ny, True, counts, retire, True).denoise * 4
+
+
+def denoise_frame_bytes(nx, ny, counts=False, retire=False):
+    """Bytes of an RTG_FLAG_DENOISE frame: it ends with the 64-byte Denoise block and the output plane."""
+    return FrameLayout(nx, ny, True, counts, retire, True).words * 4
+
+
 def features_block_offset(nx, ny, squares=False, counts=False, retire=False, denoise=False):
-    """Byte offset of the Features block in an RTG_FLAG_FEATURES frame: the first even word behind everything the call's other
-    flags put in the frame -- the float planes (one, or two with squares), the count plane, the Retire block (implies counts
-    and squares) or the Denoise block and its output plane (implies squares)."""
-    n = nx * ny
-    if denoise:
-        end = denoise_block_offset(nx, ny, counts or retire, retire) // 4 + 16 + 3 * n
-    elif retire:
-        end = retire_block_offset(nx, ny) // 4 + 16
-    else:
-        end = ((6 if squares else 3) + (1 if counts else 0)) * n
-    return ((end + 1) & ~1) * 4
+    """Byte offset of the Features block in an RTG_FLAG_FEATURES frame, behind everything the call's other flags put in it."""
+    return FrameLayout(nx, ny, squares, counts, retire, denoise, True).features * 4
 
 
 def features_frame_bytes(nx, ny, squares=False, counts=False, retire=False, denoise=False):
-    """Bytes of an RTG_FLAG_FEATURES frame: everything the other flags put in it, the 64-byte Features block, the albedo,
-    normal and depth planes (7 floats per pixel)."""
-    return features_block_offset(nx, ny, squares, counts, retire, denoise) + C.sizeof(Features) + nx * ny * 7 * 4
+    """Bytes of an RTG_FLAG_FEATURES frame: it ends with the 64-byte Features block and the albedo, normal and depth planes."""
+    return FrameLayout(nx, ny, squares, counts, retire, denoise, True).words * 4
 
 
 class Stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kernel_ms", C.c_float), ("samples", C.c_uint64),
                 ("aabb_tests", C.c_uint64), ("prim_tests", C.c_uint64), ("shaded_hits", C.c_uint64),
                 ("rays", C.c_uint64), ("draws", C.c_uint64)]
+
+    @classmethod
+    def new(cls):
+        """A zeroed Stats that states its size, as every call expects it."""
+        return cls(struct_size=C.sizeof(cls))
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
@@ -221,118 +250,115 @@ def _hip_runtime():
     return _hip
 
 
+def _stream(stream):
+    """The hipStream_t of `stream`: an int, an object with .cuda_stream, or None (the default stream)."""
+    return C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+
+
+def _hip_ok(rc, what):
+    if rc != 0:
+        raise RtError(ERR_DEVICE, "%s failed: %d" % (what, rc))
+
+
 def _resumes(kw):
     return bool(kw.get("resume")) and kw.get("sample_begin", 0) > 0
 
 
-def _squares_supported(be):
-    """RTG_FLAG_SUM_SQUARES is the HIP library's (prefix rtg_): a library that exports the same entry points under another
-    prefix ignores flags it does not know and would write one plane where the caller expects two."""
+_FLAG_OF = {"squares": ("squares=True", "SUM_SQUARES"), "counts": ("counts=", "SAMPLE_COUNTS"), "retire": ("retire=", "RETIRE"),
+            "denoise": ("denoise=", "DENOISE"), "features": ("features=", "FEATURES")}
+
+
+def _supported(be, part):
+    """The flag of `part` (a make_params keyword) is the HIP library's (prefix rtg_): a library that exports the same entry
+    points under another prefix ignores flags it does not know -- it would write one plane where the caller expects two,
+    render every pixel to ns, write no block and no plane."""
     if be.prefix != "rtg_":
-        raise ValueError("squares=True: %s (prefix %s) does not implement RTG_FLAG_SUM_SQUARES" % (be.path, be.prefix))
+        raise ValueError("%s: %s (prefix %s) does not implement RTG_FLAG_%s" % (_FLAG_OF[part][0], be.path, be.prefix, _FLAG_OF[part][1]))
 
 
-def _retire_supported(be):
-    """RTG_FLAG_RETIRE is the HIP library's (prefix rtg_), like the flags it builds on."""
-    if be.prefix != "rtg_":
-        raise ValueError("retire=: %s (prefix %s) does not implement RTG_FLAG_RETIRE" % (be.path, be.prefix))
-
-
-def _denoise_supported(be):
-    """RTG_FLAG_DENOISE is the HIP library's (prefix rtg_), like the flags it builds on."""
-    if be.prefix != "rtg_":
-        raise ValueError("denoise=: %s (prefix %s) does not implement RTG_FLAG_DENOISE" % (be.path, be.prefix))
-
-
-def _features_supported(be):
-    """RTG_FLAG_FEATURES is the HIP library's (prefix rtg_): another library would ignore the flag and write no plane."""
-    if be.prefix != "rtg_":
-        raise ValueError("features=: %s (prefix %s) does not implement RTG_FLAG_FEATURES" % (be.path, be.prefix))
-
-
-def _counts_supported(be):
-    """RTG_FLAG_SAMPLE_COUNTS is the HIP library's (prefix rtg_), like RTG_FLAG_SUM_SQUARES: another library would ignore the
-    count plane and render every pixel to ns."""
-    if be.prefix != "rtg_":
-        raise ValueError("counts=: %s (prefix %s) does not implement RTG_FLAG_SAMPLE_COUNTS" % (be.path, be.prefix))
-
-
-class CountsFrame:
-    """One contiguous host framebuffer for RTG_FLAG_SAMPLE_COUNTS: the float planes ([ny, nx, 3], or [2, ny, nx, 3] with
-    squares) followed by the count plane (uint32 [ny, nx]), as include/rtiow_gpu.h lays them out.  `planes` and `counts` are
-    views of `buf`; passing them as par_cast(out=frame.planes, counts=frame.counts) renders in place, without copies.
-    retire=True (needs squares): `buf` also holds the RTG_FLAG_RETIRE block, and `retire` is a Retire view of it
-    (par_cast(..., retire=frame.retire) renders in place too)."""
-
-    def __init__(self, nx, ny, squares=False, retire=False):
-        if retire and not squares:
-            raise ValueError("a retire frame has two float planes: squares=True")
-        n_f = (2 if squares else 1) * ny * nx * 3
-        self.buf = np.zeros(retire_frame_bytes(nx, ny) // 4 if retire else n_f + ny * nx, dtype=np.float32)
-        self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
-        self.counts = self.buf[n_f:n_f + ny * nx].view(np.uint32).reshape(ny, nx)
-        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
-
-
-class DenoiseFrame:
-    """A sibling of CountsFrame (always two float planes; the count plane is optional).  One contiguous host framebuffer for RTG_FLAG_DENOISE, as include/rtiow_gpu.h lays it out: the two float planes
-    (`planes`, [2, ny, nx, 3]), with counts=True the count plane (`counts`, uint32 [ny, nx], else None), with retire=True
-    (implies counts) the Retire block (`retire`, else None), then the Denoise block (`denoise`) and the output plane
-    (`denoised`, float32 [ny, nx, 3]).  All are views of `buf`; par_cast(out=frame, denoise=...) renders in place."""
-
-    def __init__(self, nx, ny, counts=False, retire=False, denoise=None):
-        counts = bool(counts or retire)
-        n = nx * ny
-        off = denoise_block_offset(nx, ny, counts, retire)
-        self.nx, self.ny = nx, ny
-        self.buf = np.zeros(denoise_frame_bytes(nx, ny, counts, retire) // 4, dtype=np.float32)
-        self.planes = self.buf[:6 * n].reshape(2, ny, nx, 3)
-        self.counts = self.buf[6 * n:7 * n].view(np.uint32).reshape(ny, nx) if counts else None
-        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
-        self.denoise = Denoise.from_buffer(self.buf, off)
-        self.denoised = self.buf[off // 4 + 16:off // 4 + 16 + 3 * n].reshape(ny, nx, 3)
-        block = make_denoise(denoise)
-        C.memmove(C.addressof(self.denoise), C.addressof(block), Denoise.OUT_OFFSET)
-
-
-class FeaturesFrame:
-    """One contiguous host framebuffer for RTG_FLAG_FEATURES, as include/rtiow_gpu.h lays it out, with the views of its
-    siblings: `planes` ([ny, nx, 3], or [2, ny, nx, 3] with squares), `counts` (uint32 [ny, nx]) with counts=True, `retire`
-    with retire=True (implies counts and squares), `denoise` / `denoised` with denoise= (a Denoise, a dict or True; implies
-    squares) -- each None when the frame has no such part -- then `features` (the Features block) and the planes `albedo`,
-    `normal` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]).  All are views of `buf`;
-    par_cast(out=frame, features=True) renders in place."""
+class Frame:
+    """One contiguous, zeroed host framebuffer `buf`, laid out by FrameLayout (`layout`), and a view of every part: `planes`
+    ([ny, nx, 3], or [2, ny, nx, 3] with squares), `counts` (uint32 [ny, nx]), `retire`, `denoise`, `features` (the blocks),
+    `denoised`, `albedo`, `normal` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]) -- None when the frame has no such
+    part.  denoise / features: a block, a dict or True (make_denoise / make_features), whose in-fields the block gets."""
 
     def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
-        has_dn = denoise is not None and denoise is not False
-        counts, squares = bool(counts or retire), bool(squares or retire or has_dn)
-        n = nx * ny
-        self.nx, self.ny, self.squares = nx, ny, squares
-        off = features_block_offset(nx, ny, squares, counts, retire, has_dn)
-        self.buf = np.zeros(features_frame_bytes(nx, ny, squares, counts, retire, has_dn) // 4, dtype=np.float32)
-        n_f = (6 if squares else 3) * n
-        self.planes = self.buf[:n_f].reshape((2, ny, nx, 3) if squares else (ny, nx, 3))
-        self.counts = self.buf[n_f:n_f + n].view(np.uint32).reshape(ny, nx) if counts else None
-        self.retire = Retire.from_buffer(self.buf, retire_block_offset(nx, ny)) if retire else None
-        self.denoise = self.denoised = None
-        if has_dn:
-            d_off = denoise_block_offset(nx, ny, counts, retire)
-            self.denoise = Denoise.from_buffer(self.buf, d_off)
-            self.denoised = self.buf[d_off // 4 + 16:d_off // 4 + 16 + 3 * n].reshape(ny, nx, 3)
-            block = make_denoise(None if denoise is True else denoise)
-            C.memmove(C.addressof(self.denoise), C.addressof(block), Denoise.OUT_OFFSET)
-        self.features = Features.from_buffer(self.buf, off)
-        w = off // 4 + 16
-        self.albedo = self.buf[w:w + 3 * n].reshape(ny, nx, 3)
-        self.normal = self.buf[w + 3 * n:w + 6 * n].reshape(ny, nx, 3)
-        self.depth = self.buf[w + 6 * n:w + 7 * n].reshape(ny, nx)
-        block = make_features(None if features is True else features)
-        C.memmove(C.addressof(self.features), C.addressof(block), Features.OUT_OFFSET)
+        lay = self.layout = FrameLayout(nx, ny, squares, counts, retire, _given(denoise), _given(features))
+        self.nx, self.ny, self.squares = nx, ny, lay.squares
+        self.buf = np.zeros(lay.words, dtype=np.float32)
+
+        def plane(at, *shape):
+            return None if at is None else self.buf[at:at + math.prod(shape)].reshape(shape)
+
+        def block(cls, at):
+            return None if at is None else cls.from_buffer(self.buf, at * 4)
+        self.planes = plane(0, *((2, ny, nx, 3) if lay.squares else (ny, nx, 3)))
+        self.counts = None if lay.counts is None else plane(lay.counts, ny, nx).view(np.uint32)
+        self.denoised, self.albedo, self.normal = (plane(at, ny, nx, 3) for at in (lay.denoised, lay.albedo, lay.normal))
+        self.depth = plane(lay.depth, ny, nx)
+        self.retire, self.denoise, self.features = block(Retire, lay.retire), block(Denoise, lay.denoise), block(Features, lay.features)
+        if self.denoise is not None:
+            self.set_in(make_denoise(denoise))
+        if self.features is not None:
+            self.set_in(make_features(features))
 
     def flags(self):
         """make_params keywords of the parts the frame has."""
         return {"squares": self.squares, "counts": self.counts is not None, "retire": self.retire is not None,
-                "denoise": self.denoise is not None, "features": True}
+                "denoise": self.denoise is not None, "features": self.features is not None}
+
+    def set_in(self, block):
+        """Write the in-fields of `block` (a Retire, Denoise or Features) to the frame's block of that class; the out-fields,
+        which only the library writes, stay."""
+        C.memmove(C.addressof(getattr(self, type(block).__name__.lower())), C.addressof(block), block.OUT_OFFSET)
+
+    def copy_in(self, out=None, counts=None, retire=None):
+        """The caller's float planes, count plane and Retire (all of it) into the frame."""
+        if out is not None:
+            self.planes[...] = out
+        if counts is not None:
+            self.counts[...] = counts
+        if retire is not None:
+            C.memmove(C.addressof(self.retire), C.addressof(retire), C.sizeof(Retire))
+
+    def copy_back(self, out=None, counts=None, retire=None):
+        """The frame's float planes, count plane and Retire block back to the caller's."""
+        if out is not None:
+            out[...] = self.planes
+        if counts is not None:
+            counts[...] = self.counts
+        if retire is not None:
+            C.memmove(C.addressof(retire), C.addressof(self.retire), C.sizeof(Retire))
+
+
+class CountsFrame(Frame):
+    """The frame of RTG_FLAG_SAMPLE_COUNTS: the float planes and the count plane; retire=True (needs squares): and the
+    RTG_FLAG_RETIRE block.  par_cast(out=frame.planes, counts=frame.counts[, retire=frame.retire]) renders in place, without
+    copies, as par_cast(out=frame) does."""
+
+    def __init__(self, nx, ny, squares=False, retire=False):
+        if retire and not squares:
+            raise ValueError("a retire frame has two float planes: squares=True")
+        super().__init__(nx, ny, squares, True, retire)
+
+
+class DenoiseFrame(Frame):
+    """The frame of RTG_FLAG_DENOISE, a sibling of CountsFrame: always two float planes, the count plane with counts=True, the
+    Retire block with retire=True (implies counts), then the Denoise block and the output plane.  par_cast(out=frame,
+    denoise=...) renders in place."""
+
+    def __init__(self, nx, ny, counts=False, retire=False, denoise=None):
+        super().__init__(nx, ny, True, counts, retire, denoise if _given(denoise) else True)
+
+
+class FeaturesFrame(Frame):
+    """The frame of RTG_FLAG_FEATURES: what its siblings hold -- the count plane with counts=True, the Retire block with
+    retire=True (implies counts and squares), the Denoise block and its output plane with denoise= (a Denoise, a dict or
+    True; implies squares) -- then the Features block and the albedo, normal and depth planes.  par_cast(out=frame,
+    features=True) renders in place."""
+
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
+        super().__init__(nx, ny, squares, counts, retire, denoise, features if _given(features) else True)
 
 
 def features_frame(nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
@@ -361,66 +387,122 @@ def _counts_call(out, counts, nx, ny, squares, retire=None):
             and (retire is None or C.addressof(retire) == out.ctypes.data + retire_block_offset(nx, ny))):
         return out, None
     f = CountsFrame(nx, ny, squares, retire is not None)
-    f.planes[...] = out
-    f.counts[...] = counts
-    if retire is not None:
-        C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
+    f.copy_in(out, counts, retire)
     return f.planes, f
 
 
-def _host_frame(out, nx, ny, kw):
+def _host_frame(out, nx, ny, squares, kw):
     """The host framebuffer of a par_cast call: `out`, checked, or a new zeroed one -- [ny, nx, 3] float32, or [2, ny, nx, 3]
-    with squares=True (the library writes both planes: a smaller array would be overrun)."""
-    shape = (2, ny, nx, 3) if kw.get("squares") else (ny, nx, 3)
+    with squares (the library writes both planes: a smaller array would be overrun)."""
+    shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
     if out is None:
         if _resumes(kw):
             raise ValueError("resume=True needs out= (the running sum to continue)")
         return np.zeros(shape, dtype=np.float32)
-    if kw.get("squares") and not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == np.float32
-                                  and out.flags.c_contiguous):
+    if squares and not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == np.float32 and out.flags.c_contiguous):
         raise ValueError("squares=True needs out= a C-contiguous float32 array of shape %s" % (shape,))
     return out
+
+
+def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, retire, denoise, features, kw, exact, forward=False):
+    """The one path of Scene.par_cast and Backend.par_cast_multi into the library: `supported(part)` is _supported on the
+    backend of either, `call(params, buffer)` makes the library call and returns its Stats; `counters`: whether a stats=True call asks for the instrumented counters.  The frame is
+    `out` itself (a Frame: rendered in place, its flags those of the parts it has), a staging frame that carries copies of
+    the caller's out / counts / retire and gives them back, or a plain array.  Every check is made before anything of the
+    caller's is written.
+    exact (Scene.par_cast): beside a Frame, squares= / denoise= / features= must say what the frame holds, and it brings its
+    own counts and retire.  Otherwise (par_cast_multi) they may say less, and retire= a Retire sets the block's in-fields.
+    forward (par_cast_multi): plain flags beside a plain array (counts=True, ...) go to the library as they are."""
+    kw = dict(kw)
+    squares = kw.pop("squares", None)
+    has_rt, has_dn, has_ft = _given(retire), _given(denoise), _given(features)
+    in_place = isinstance(out, Frame)
+    f = None
+    plain = forward and not (in_place or isinstance(counts, np.ndarray) or isinstance(retire, Retire)
+                             or isinstance(denoise, (dict, Denoise)) or isinstance(features, (dict, Features)))
+    if plain:   # (the library's to answer)
+        flags, parts = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features}, ()
+    else:
+        if has_dn and not squares and (exact or not in_place):
+            raise ValueError("denoise= needs squares=True (the filter reads both planes)")
+        blocks = [make(x) for x, make in ((denoise, make_denoise), (features, make_features)) if _given(x) and x is not True]
+        if in_place:
+            f, name = out, type(out).__name__
+            if (f.nx, f.ny) != (nx, ny):
+                raise ValueError("out= is a %s of another size" % name)
+            if isinstance(counts, np.ndarray) or (exact and (counts is not None or retire is not None)):
+                raise ValueError("out= a %s brings its own counts / retire views" % name)
+            if has_ft and f.features is None:
+                raise ValueError("features=: out= must be a FeaturesFrame or an array")
+            if (has_dn and f.denoise is None) or (has_rt and f.retire is None):
+                raise ValueError("out= a %s has no such block" % name)
+            if ((squares is not None or exact) and bool(squares) != f.squares) or (
+                    exact and (has_dn != (f.denoise is not None) or has_ft != (f.features is not None))):
+                raise ValueError("out= a %s: squares= / denoise= / features= must say what the frame holds" % name)
+            if isinstance(retire, Retire):
+                blocks.append(retire)
+            flags = f.flags()
+        else:
+            if has_rt and not (isinstance(retire, Retire) and isinstance(counts, np.ndarray) and squares):
+                raise ValueError("retire= needs a Retire, squares=True and counts= a uint32 array (the call writes it)")
+            if counts is not None and np.asarray(counts).shape != (ny, nx):
+                raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
+            if out is None and _resumes(kw):
+                raise ValueError("resume=True needs out= (the running sum to continue)")
+            flags = {"squares": bool(squares), "counts": counts is not None, "retire": has_rt, "denoise": has_dn, "features": has_ft}
+        parts = [part for part, on in flags.items() if on]
+    for part in parts:
+        supported(part)
+    if in_place:
+        for block in blocks:
+            f.set_in(block)
+        ret, buf = f, f.buf
+    elif (has_dn or has_ft) and not plain:
+        f = (FeaturesFrame(nx, ny, squares, counts is not None, has_rt, denoise if has_dn else None, features) if has_ft else
+             DenoiseFrame(nx, ny, counts is not None, has_rt, denoise))
+        f.copy_in(None if out is None else _host_frame(out, nx, ny, squares, kw), counts, retire if has_rt else None)
+        ret, buf = f, f.buf
+    else:
+        ret = out = buf = _host_frame(out, nx, ny, squares, kw)
+        if counts is not None and not plain:   # in place when `out` and `counts` are one CountsFrame's views
+            buf, f = _counts_call(out, counts, nx, ny, squares, retire if has_rt else None)
+    p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, **flags, **kw)
+    st = call(p, buf)
+    if f is not None and not in_place:   # (with retire the library wrote the count plane and the block's out-fields)
+        f.copy_back(out, counts if has_rt else None, retire if has_rt else None)
+    return (ret, st.as_dict()) if stats else ret
 
 
 def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw):
     """The host-frame loop of Scene.adaptive and Backend.adaptive_multi: `cast(ns, **keywords)` is the par_cast of either
     (camera and frame size bound); denoise / features: a checked Denoise / Features, or None."""
     if features is not None:
-        f = FeaturesFrame(nx, ny, squares=True, counts=True, denoise=denoise) if out is None else out
-        if (not isinstance(f, FeaturesFrame) or f.counts is None or f.retire is not None or not f.squares
-                or (f.denoise is None) != (denoise is None)):
-            raise ValueError("features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)")
-        C.memmove(C.addressof(f.features), C.addressof(features), Features.OUT_OFFSET)
-        if denoise is not None:
-            C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+        f = FeaturesFrame(nx, ny, True, True, False, denoise) if out is None else out
+        what = "features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)"
     elif denoise is not None:
-        f = DenoiseFrame(nx, ny, counts=True) if out is None else out
-        if not isinstance(f, DenoiseFrame) or f.counts is None or f.retire is not None:
-            raise ValueError("denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)")
-        C.memmove(C.addressof(f.denoise), C.addressof(denoise), Denoise.OUT_OFFSET)
+        f = DenoiseFrame(nx, ny, True) if out is None else out
+        what = "denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)"
     else:
-        f = CountsFrame(nx, ny, squares=True) if out is None else out
-        if not isinstance(f, CountsFrame):
-            raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
+        f = CountsFrame(nx, ny, True) if out is None else out
+        what = "out= must be a CountsFrame(nx, ny, squares=True)"
+    on = {"denoise": True if denoise is not None else None, "features": True if features is not None else None}
+    if not isinstance(f, Frame) or (f.nx, f.ny) != (nx, ny) or f.flags() != {
+            "squares": True, "counts": True, "retire": False, "denoise": denoise is not None, "features": features is not None}:
+        raise ValueError(what)
+    for block in (features, denoise):
+        if block is not None:
+            f.set_in(block)
     more = () if features is None else (f,)
-    if f.planes.shape != (2, ny, nx, 3):
-        raise ValueError("out= must be a CountsFrame(nx, ny, squares=True)")
     f.counts[...] = ns
     active = np.ones((ny, nx), dtype=bool)
     t0 = time.perf_counter()
     done = 0
     while done < ns:
         end = min(ns, done + step)
+        _, st = cast(end, seed=seed, out=f, sample_begin=done, resume=True, partial=True, squares=True, stats=True, counters=False,
+                     **on, **kw)
         if features is not None:
-            _, st = cast(end, seed=seed, out=f, denoise=True if denoise is not None else None, features=True, sample_begin=done,
-                         resume=True, partial=True, squares=True, stats=True, counters=False, **kw)
             f.features.compute = 0   # (the planes are traced once)
-        elif denoise is not None:
-            _, st = cast(end, seed=seed, out=f, denoise=True, sample_begin=done, resume=True, partial=True, squares=True,
-                         stats=True, counters=False, **kw)
-        else:
-            _, st = cast(end, seed=seed, out=f.planes, counts=f.counts, sample_begin=done, resume=True, partial=True, squares=True,
-                         stats=True, counters=False, **kw)
         if stats is not None:
             stats.append(st)
         done = end
@@ -433,9 +515,8 @@ def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out
         f.counts[retire] = done
         active &= ~retire
         pv = CountsFrame(nx, ny)   # resolve a copy: the running sums go on
-        pv.planes[...] = f.planes[0]
-        pv.counts[...] = held
-        cast(done, seed=seed, out=pv.planes, counts=pv.counts, sample_begin=done, resume=True, **kw)
+        pv.copy_in(f.planes[0], held)
+        cast(done, seed=seed, out=pv, sample_begin=done, resume=True, **kw)
         if denoise is not None:
             yield (held, pv.planes, se, f.denoised.copy()) + more
         else:
@@ -584,103 +665,18 @@ class Backend:
         block or a dict beside an array `out` go through a staging frame as in Scene.par_cast (a denoise / features call
         returns that frame).  Plain flags beside a plain array (counts=True, ...) are forwarded to the library as they are.
         stats=True returns (frame, rtg_stats as a dict), with the instrumented counters unless counters=False."""
-        counts, retire, denoise, features = kw.get("counts"), kw.get("retire"), kw.get("denoise"), kw.get("features")
-        if (isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame)) or isinstance(counts, np.ndarray) or isinstance(retire, Retire)
-                or isinstance(denoise, (dict, Denoise)) or isinstance(features, (dict, Features))):
-            return self._par_cast_multi_planes(scenes, camera, nx, ny, ns, seed, stats, out, counters, kw)
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters is not False else 0, **kw)
-        out = _host_frame(out, nx, ny, kw)
-        st = self._par_cast_multi_call(scenes, camera, p, out)
-        return (out, st.as_dict()) if stats else out
+        kw = dict(kw)
+        counts, retire, denoise, features = (kw.pop(k, None) for k in ("counts", "retire", "denoise", "features"))
+        return _render(lambda part: _supported(self, part), lambda p, buf: self._par_cast_multi_call(scenes, camera, p, buf),
+                       nx, ny, ns, seed, stats, out, True if counters is None else counters, counts, retire, denoise, features, kw,
+                       exact=False, forward=True)
 
     def _par_cast_multi_call(self, scenes, camera, p, buf):
-        st = Stats()
-        st.struct_size = C.sizeof(Stats)
+        """The library call alone, on any params and buffer."""
+        st = Stats.new()
         arr = (C.c_void_p * len(scenes))(*[s.h for s in scenes])
         self.check(self._par_cast_multi(arr, len(scenes), C.byref(camera), C.byref(p), buf.ctypes.data_as(c_f32p), C.byref(st)))
         return st
-
-    def _par_cast_multi_planes(self, scenes, camera, nx, ny, ns, seed, stats, out, counters, kw):
-        """par_cast_multi on a frame object (in place) or through a staging frame: every check is made before the library call."""
-        kw = dict(kw)
-        counts, retire, denoise, features = (kw.pop(k, None) for k in ("counts", "retire", "denoise", "features"))
-        squares = kw.pop("squares", None)
-        has_dn = denoise is not None and denoise is not False
-        has_ft = features is not None and features is not False
-        in_place = isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame))
-        if in_place:
-            f = out
-            if f.planes.shape[-3:] != (ny, nx, 3):
-                raise ValueError("out= is a %s of another size" % type(f).__name__)
-            if isinstance(counts, np.ndarray):
-                raise ValueError("out= a %s brings its own counts view" % type(f).__name__)
-            f_dn, f_ft = getattr(f, "denoise", None), getattr(f, "features", None)
-            if squares is not None and bool(squares) != (f.planes.ndim == 4):
-                raise ValueError("out= a %s: squares= must say what the frame holds" % type(f).__name__)
-            if (has_dn and f_dn is None) or (has_ft and f_ft is None) or (retire is not None and retire is not False and f.retire is None):
-                raise ValueError("out= a %s has no such block" % type(f).__name__)
-            if isinstance(retire, Retire):
-                C.memmove(C.addressof(f.retire), C.addressof(retire), Retire.active.offset)
-            if has_dn and denoise is not True:
-                block = make_denoise(denoise)
-                C.memmove(C.addressof(f_dn), C.addressof(block), Denoise.OUT_OFFSET)
-            if has_ft and features is not True:
-                block = make_features(features)
-                C.memmove(C.addressof(f_ft), C.addressof(block), Features.OUT_OFFSET)
-            flags = {"squares": f.planes.ndim == 4, "counts": f.counts is not None, "retire": f.retire is not None,
-                     "denoise": f_dn is not None, "features": f_ft is not None}
-        else:
-            if counts is not None and not isinstance(counts, np.ndarray):
-                raise ValueError("counts= must be a uint32 array beside retire= / denoise= / features= blocks (or pass a frame as out=)")
-            if retire is not None and (not isinstance(retire, Retire) or counts is None or not squares):
-                raise ValueError("retire= needs a Retire, squares=True and counts= a uint32 array (the call writes it)")
-            if has_dn and not squares:
-                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
-            if counts is not None and np.asarray(counts).shape != (ny, nx):
-                raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
-            sq = {"squares": True} if squares else {}
-            if out is None and _resumes(kw):
-                raise ValueError("resume=True needs out= (the running sum to continue)")
-            if has_ft:
-                f = FeaturesFrame(nx, ny, squares, counts is not None, retire is not None, denoise if has_dn else None,
-                                  None if features is True else features)
-            elif has_dn:
-                f = DenoiseFrame(nx, ny, counts is not None, retire is not None, None if denoise is True else denoise)
-            else:
-                f = None
-            if f is None:   # counts (and retire) alone: in place when `out` and `counts` are one CountsFrame's views
-                out = _host_frame(out, nx, ny, sq)
-                dst, f = _counts_call(out, counts, nx, ny, squares, retire)
-                buf = dst if f is None else f.buf
-            else:
-                if out is not None:
-                    f.planes[...] = _host_frame(out, nx, ny, sq)
-                if counts is not None:
-                    f.counts[...] = counts
-                if retire is not None:
-                    C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
-                buf = f.buf
-            flags = {"squares": bool(squares), "counts": counts is not None, "retire": retire is not None, "denoise": has_dn,
-                     "features": has_ft}
-        if in_place:
-            buf = f.buf
-        for part, check in ((flags["squares"], _squares_supported), (flags["counts"], _counts_supported),
-                            (flags["retire"], _retire_supported), (flags["denoise"], _denoise_supported),
-                            (flags["features"], _features_supported)):
-            if part:
-                check(self)
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters is not False else 0, **flags, **kw)
-        st = self._par_cast_multi_call(scenes, camera, p, buf)
-        if in_place:
-            ret = f
-        else:
-            if f is not None and out is not None:
-                out[...] = f.planes
-            if f is not None and retire is not None:   # (the library wrote the count plane and the block's out-fields)
-                counts[...] = f.counts
-                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
-            ret = f if (has_dn or has_ft) else out
-        return (ret, st.as_dict()) if stats else ret
 
     def adaptive_multi(self, scenes, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
                        stats=None, radius=0, denoise=None, features=None, **kw):
@@ -691,10 +687,10 @@ class Backend:
             raise ValueError("step must be >= 1")
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
-        _squares_supported(self)
-        _counts_supported(self)
-        features = make_features(None if features is True else features) if features is not None and features is not False else None
-        denoise = make_denoise(None if denoise is True else denoise) if denoise is not None and denoise is not False else None
+        _supported(self, "squares")
+        _supported(self, "counts")
+        features = make_features(features) if _given(features) else None
+        denoise = make_denoise(denoise) if _given(denoise) else None
         yield from _adaptive_host(lambda n, **k: self.par_cast_multi(scenes, camera, nx, ny, n, **k), nx, ny, ns, step,
                                   target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw)
 
@@ -902,8 +898,8 @@ class Scene:
         squares=True (RTG_FLAG_SUM_SQUARES): float32 [2, ny, nx, 3] instead -- [0] as without the flag, [1] the running sum
         of the squared sample colours; `out`, when given, must have that shape.
         counts= (RTG_FLAG_SAMPLE_COUNTS): uint32 [ny, nx], every pixel's own sample count n_p -- the call renders samples
-        [sample_begin, min(n_p, ns)) of each pixel; pixels with n_p = 0 are left as `out` holds them.  `out` and `counts` of
-        one CountsFrame are rendered in place; anything else goes through a staging copy.
+        [sample_begin, min(n_p, ns)) of each pixel; pixels with n_p = 0 are left as `out` holds them.  out= a CountsFrame, or
+        `out` and `counts` that are one CountsFrame's views, are rendered in place; anything else goes through a staging copy.
         retire= (RTG_FLAG_RETIRE; needs counts= and squares=True): a Retire whose target_se / min_samples / radius the call
         applies after its slice -- retiring pixels get n_p = ns in `counts` -- and whose out-fields it fills.  counts= must then
         be a uint32 array the call can write (a CountsFrame(retire=True)'s counts and retire render in place).
@@ -919,144 +915,13 @@ class Scene:
         rendered in place and returned (features=True / denoise=True: its blocks as they stand); anything else is copied into
         a new frame and written back as without features=.
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
-        if features is not None and features is not False:
-            if denoise is not None and denoise is not False and not kw.get("squares"):
-                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
-            _features_supported(self.be)
-            return self._par_cast_features(camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise,
-                                           features, kw)
-        if denoise is not None and denoise is not False:
-            if not kw.get("squares"):
-                raise ValueError("denoise= needs squares=True (the filter reads both planes)")
-            _denoise_supported(self.be)
-            return self._par_cast_denoise(camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, kw)
-        if kw.get("squares"):
-            _squares_supported(self.be)
-        if counts is not None:
-            _counts_supported(self.be)
-        if retire is not None:
-            _retire_supported(self.be)
-            if counts is None or not kw.get("squares") or not isinstance(counts, np.ndarray):
-                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
-        if counters is None:
-            counters = stats
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, counts=counts is not None,
-                        retire=retire is not None, **kw)
-        out = _host_frame(out, nx, ny, kw)
-        dst, staging = (out, None) if counts is None else _counts_call(out, counts, nx, ny, kw.get("squares"), retire)
-        st = Stats()
-        st.struct_size = C.sizeof(Stats)
-        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), dst.ctypes.data_as(c_f32p), C.byref(st)],
-                                   threads)
-        self.be.check(self.be._par_cast(*args))
-        if staging is not None:
-            out[...] = staging.planes
-            if retire is not None:   # (the library wrote the count plane and the block's out-fields)
-                counts[...] = staging.counts
-                C.memmove(C.addressof(retire), C.addressof(staging.retire), C.sizeof(Retire))
-        return (out, st.as_dict()) if stats else out
-
-    def _par_cast_denoise(self, camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, kw):
-        _squares_supported(self.be)
-        in_place = isinstance(out, DenoiseFrame)
-        if in_place:
-            f = out
-            if (f.nx, f.ny) != (nx, ny):
-                raise ValueError("out= is a DenoiseFrame of another size")
-            if counts is not None or retire is not None:
-                raise ValueError("out= a DenoiseFrame brings its own counts / retire views")
-            if denoise is not True:
-                block = make_denoise(denoise)
-                C.memmove(C.addressof(f.denoise), C.addressof(block), Denoise.OUT_OFFSET)
-        else:
-            if retire is not None and (counts is None or not isinstance(counts, np.ndarray)):
-                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
-            f = DenoiseFrame(nx, ny, counts is not None, retire is not None, None if denoise is True else denoise)
-            if out is not None:
-                f.planes[...] = _host_frame(out, nx, ny, kw)
-            elif _resumes(kw):
-                raise ValueError("resume=True needs out= (the running sum to continue)")
-            if counts is not None:
-                counts = np.asarray(counts)
-                if counts.shape != (ny, nx):
-                    raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
-                f.counts[...] = counts
-            if retire is not None:
-                C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
-        if f.counts is not None:
-            _counts_supported(self.be)
-        if f.retire is not None:
-            _retire_supported(self.be)
-        if counters is None:
-            counters = stats
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, counts=f.counts is not None,
-                        retire=f.retire is not None, denoise=True, **kw)
-        st = Stats()
-        st.struct_size = C.sizeof(Stats)
-        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), f.buf.ctypes.data_as(c_f32p), C.byref(st)], threads)
-        self.be.check(self.be._par_cast(*args))
-        if not in_place:
-            if out is not None:
-                out[...] = f.planes
-            if retire is not None:
-                counts[...] = f.counts
-                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
-        return (f, st.as_dict()) if stats else f
-
-    def _par_cast_features(self, camera, nx, ny, ns, seed, stats, out, threads, counts, counters, retire, denoise, features, kw):
-        has_dn = denoise is not None and denoise is not False
-        in_place = isinstance(out, FeaturesFrame)
-        if in_place:
-            f = out
-            if (f.nx, f.ny) != (nx, ny):
-                raise ValueError("out= is a FeaturesFrame of another size")
-            if counts is not None or retire is not None:
-                raise ValueError("out= a FeaturesFrame brings its own counts / retire views")
-            if has_dn != (f.denoise is not None) or bool(kw.get("squares")) != f.squares:
-                raise ValueError("out= a FeaturesFrame: squares= / denoise= must say what the frame holds")
-            if has_dn and denoise is not True:
-                block = make_denoise(denoise)
-                C.memmove(C.addressof(f.denoise), C.addressof(block), Denoise.OUT_OFFSET)
-            if features is not True:
-                block = make_features(features)
-                C.memmove(C.addressof(f.features), C.addressof(block), Features.OUT_OFFSET)
-        else:
-            if retire is not None and (counts is None or not kw.get("squares") or not isinstance(counts, np.ndarray)):
-                raise ValueError("retire= needs squares=True and counts= a uint32 array (the call writes it)")
-            if isinstance(out, (DenoiseFrame, CountsFrame)):
-                raise ValueError("features=: out= must be a FeaturesFrame or an array")
-            f = FeaturesFrame(nx, ny, kw.get("squares"), counts is not None, retire is not None, denoise if has_dn else None,
-                              None if features is True else features)
-            if out is not None:
-                f.planes[...] = _host_frame(out, nx, ny, kw)
-            elif _resumes(kw):
-                raise ValueError("resume=True needs out= (the running sum to continue)")
-            if counts is not None:
-                counts = np.asarray(counts)
-                if counts.shape != (ny, nx):
-                    raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
-                f.counts[...] = counts
-            if retire is not None:
-                C.memmove(C.addressof(f.retire), C.addressof(retire), C.sizeof(Retire))
-        for part, check in ((f.squares, _squares_supported), (f.counts is not None, _counts_supported),
-                            (f.retire is not None, _retire_supported), (f.denoise is not None, _denoise_supported)):
-            if part:
-                check(self.be)
-        if counters is None:
-            counters = stats
-        kw = {k: v for k, v in kw.items() if k != "squares"}
-        p = make_params(nx, ny, ns, seed=seed, flags=FLAG_COUNTERS if stats and counters else 0, **f.flags(), **kw)
-        st = Stats()
-        st.struct_size = C.sizeof(Stats)
-        args = self._par_cast_args([self.h, C.byref(camera), C.byref(p), f.buf.ctypes.data_as(c_f32p), C.byref(st)], threads)
-        self.be.check(self.be._par_cast(*args))
-        if not in_place:
-            if out is not None:
-                out[...] = f.planes
-            if retire is not None:
-                counts[...] = f.counts
-                C.memmove(C.addressof(retire), C.addressof(f.retire), C.sizeof(Retire))
-        return (f, st.as_dict()) if stats else f
+        def call(p, buf):
+            st = Stats.new()
+            self.be.check(self.be._par_cast(*self._par_cast_args(
+                [self.h, C.byref(camera), C.byref(p), buf.ctypes.data_as(c_f32p), C.byref(st)], threads)))
+            return st
+        return _render(lambda part: _supported(self.be, part), call, nx, ny, ns, seed, stats, out,
+                       stats if counters is None else counters, counts, retire, denoise, features, kw, exact=True)
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
                         resume=None, squares=None, counts=None, retire=None, denoise=None, features=None):
@@ -1074,98 +939,72 @@ class Scene:
         features= (RTG_FLAG_FEATURES): True, the flag alone (the caller has written the block's in-fields on the device); a
         Features, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
         `d_out_ptr` then holds features_frame_bytes(nx, ny, squares, counts, retire, denoise) for the flags the call ends up with."""
-        dblock = fblock = None   # (every refusal first: a refused call has written nothing to the caller's frame)
-        if features is not None and features is not False:
-            _features_supported(self.be)
-        if denoise is not None and denoise is not False:
-            _denoise_supported(self.be)
-        if squares or (squares is None and params.flags & FLAG_SUM_SQUARES):
-            _squares_supported(self.be)
-        if counts is not None and counts is not False:
-            _counts_supported(self.be)
-        if retire is not None and retire is not False:
-            _retire_supported(self.be)
-        if denoise is not None and denoise is not False:
-            has = [bool(params.flags & bit) if on is None else on is not False
-                   for on, bit in ((counts, FLAG_SAMPLE_COUNTS), (retire, FLAG_RETIRE))]
-            d_off = denoise_block_offset(params.nx, params.ny, has[0], has[1])
-            if denoise is not True:
-                dblock = denoise
-                self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
-                denoise = True
-        if features is not None and features is not False:
-            has = [bool(params.flags & bit) if on is None else on is not False
-                   for on, bit in ((squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS), (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE))]
-            f_off = features_block_offset(params.nx, params.ny, *has)
-            if features is not True:
-                fblock = features
-                self._block_copy(params.nx, params.ny, d_out_ptr, fblock, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
-                features = True
-        block = None
-        if retire is not None and retire is not False:
-            if retire is not True:
-                block = retire
-                self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=True)
-                retire = True
-        if counts is not None and counts is not True and counts is not False:
-            sq = squares if squares is not None else bool(params.flags & FLAG_SUM_SQUARES)
-            self._upload_counts(params.nx, params.ny, sq, counts, d_out_ptr, stream)
-            counts = True
-        if (sample_begin is not None or partial is not None or resume is not None or squares is not None or counts is not None
-                or retire is not None or denoise is not None or features is not None):
+        over = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features}
+        bits = {"squares": FLAG_SUM_SQUARES, "counts": FLAG_SAMPLE_COUNTS, "retire": FLAG_RETIRE, "denoise": FLAG_DENOISE,
+                "features": FLAG_FEATURES}
+        # the parts the call ends up with: those of `params` unless overridden (an array or a block turns its part on).
+        # Every refusal first: a refused call has written nothing to the caller's frame
+        has = {part: bool(params.flags & bits[part] if on is None else on if isinstance(on, (bool, int)) else True)
+               for part, on in over.items()}
+        for part in ("features", "denoise", "squares", "counts", "retire"):
+            if has[part] if part == "squares" else _given(over[part]):
+                _supported(self.be, part)
+        lay = FrameLayout(params.nx, params.ny, **has)
+        # blocks of the caller's: (block, byte offset, bytes written before the call); all of a block is read back after it
+        blocks = [(over[part], 4 * at, n) for part, at, n in (("retire", lay.retire, C.sizeof(Retire)),
+                                                             ("denoise", lay.denoise, Denoise.OUT_OFFSET),
+                                                             ("features", lay.features, Features.OUT_OFFSET))
+                  if isinstance(over[part], C.Structure)]
+        for block, at, n in blocks:
+            self._block_copy(d_out_ptr, block, stream, True, at, n)
+        if _given(counts) and counts is not True:
+            self._upload_counts(lay, counts, d_out_ptr, stream)
+        if sample_begin is not None or partial is not None or resume is not None or any(on is not None for on in over.values()):
             q = Params()
             C.pointer(q)[0] = params
             if sample_begin is not None:
                 q.sample_begin = sample_begin
-            for on, bit in ((partial, FLAG_PARTIAL), (resume, FLAG_RESUME), (squares, FLAG_SUM_SQUARES), (counts, FLAG_SAMPLE_COUNTS),
-                            (retire, FLAG_RETIRE), (denoise, FLAG_DENOISE), (features, FLAG_FEATURES)):
+            for on, bit in [(partial, FLAG_PARTIAL), (resume, FLAG_RESUME)] + [(on if on is None else has[part], bits[part])
+                                                                             for part, on in over.items()]:
                 if on is not None:
                     q.flags = (q.flags | bit) if on else (q.flags & ~bit)
             params = q
-        st = Stats()
-        st.struct_size = C.sizeof(Stats)
+        st = Stats.new()
         self.be.check(self.be._par_cast_device(self.h, C.byref(camera), C.byref(params), d_out_ptr, stream,
                                                C.byref(st) if want_stats else None))
-        if block is not None:
-            self._block_copy(params.nx, params.ny, d_out_ptr, block, stream, to_device=False)
-        if dblock is not None:
-            self._block_copy(params.nx, params.ny, d_out_ptr, dblock, stream, to_device=False, offset=d_off, nbytes=C.sizeof(Denoise))
-        if fblock is not None:
-            self._block_copy(params.nx, params.ny, d_out_ptr, fblock, stream, to_device=False, offset=f_off, nbytes=C.sizeof(Features))
+        for block, at, _ in blocks:
+            self._block_copy(d_out_ptr, block, stream, False, at, C.sizeof(block))
         return st.as_dict() if want_stats else None
 
-    def _block_copy(self, nx, ny, d_out_ptr, block, stream, to_device, offset=None, nbytes=None):
-        """Copy a Retire to (or from) the retire block of a device frame on `stream`, and wait for it (`block` is host memory);
-        offset / nbytes: another block of the frame (a Denoise) and how much of it."""
-        hip = _hip_runtime()
-        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
-        dev = C.c_void_p(_device_ptr(d_out_ptr) + (retire_block_offset(nx, ny) if offset is None else offset))
-        host = C.c_void_p(C.addressof(block))
-        n = C.sizeof(Retire) if nbytes is None else nbytes
-        rc = hip.hipMemcpyAsync(*((dev, host, n, 1) if to_device else (host, dev, n, 2)), hs)
-        if rc == 0:
-            rc = hip.hipStreamSynchronize(hs)
-        if rc != 0:
-            raise RtError(ERR_DEVICE, "hipMemcpyAsync(%s block) failed: %d" % (type(block).__name__.lower(), rc))
+    def _block_copy(self, d_out_ptr, block, stream, to_device, offset, nbytes):
+        """Copy `nbytes` of a block (host memory) to, or from, byte `offset` of a device frame on `stream`, and wait for it."""
+        hip, hs = _hip_runtime(), _stream(stream)
+        dev, host = C.c_void_p(_device_ptr(d_out_ptr) + offset), C.c_void_p(C.addressof(block))
+        what = "hipMemcpyAsync(%s block)" % type(block).__name__.lower()
+        _hip_ok(hip.hipMemcpyAsync(*((dev, host, nbytes, 1) if to_device else (host, dev, nbytes, 2)), hs), what)
+        _hip_ok(hip.hipStreamSynchronize(hs), what)
 
-    def _upload_counts(self, nx, ny, squares, counts, d_out_ptr, stream):
-        """Copy a uint32 [ny, nx] count array into the count plane of a device frame, on `stream`."""
-        hip = _hip_runtime()
-        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
-        dst = C.c_void_p(_device_ptr(d_out_ptr) + (2 if squares else 1) * nx * ny * 3 * 4)
+    def _upload_counts(self, lay, counts, d_out_ptr, stream):
+        """Copy a uint32 [ny, nx] count array into the count plane of a device frame (layout `lay`), on `stream`."""
+        hip, hs = _hip_runtime(), _stream(stream)
+        dst = C.c_void_p(_device_ptr(d_out_ptr) + 4 * lay.counts)
         if hasattr(counts, "data_ptr") and getattr(counts, "is_cuda", False):
-            if tuple(counts.shape) != (ny, nx) or counts.element_size() != 4 or not counts.is_contiguous():
+            if tuple(counts.shape) != (lay.ny, lay.nx) or counts.element_size() != 4 or not counts.is_contiguous():
                 raise ValueError("counts= must be a contiguous 4-byte [ny, nx] tensor")
-            rc = hip.hipMemcpyAsync(dst, C.c_void_p(counts.data_ptr()), nx * ny * 4, 3, hs)   # 3 = hipMemcpyDeviceToDevice
+            _hip_ok(hip.hipMemcpyAsync(dst, C.c_void_p(counts.data_ptr()), 4 * lay.n, 3, hs), "hipMemcpyAsync(count plane)")   # 3: device to device
         else:
             host = np.ascontiguousarray(counts, dtype=np.uint32)
-            if host.shape != (ny, nx):
-                raise ValueError("counts= must have shape (ny, nx) = %s" % ((ny, nx),))
-            rc = hip.hipMemcpyAsync(dst, C.c_void_p(host.ctypes.data), nx * ny * 4, 1, hs)   # 1 = hipMemcpyHostToDevice
-            if rc == 0:
-                rc = hip.hipStreamSynchronize(hs)   # (the host array may go away when this call returns)
-        if rc != 0:
-            raise RtError(ERR_DEVICE, "hipMemcpyAsync(count plane) failed: %d" % rc)
+            if host.shape != (lay.ny, lay.nx):
+                raise ValueError("counts= must have shape (ny, nx) = %s" % ((lay.ny, lay.nx),))
+            _hip_ok(hip.hipMemcpyAsync(dst, C.c_void_p(host.ctypes.data), 4 * lay.n, 1, hs), "hipMemcpyAsync(count plane)")   # 1: host to device
+            _hip_ok(hip.hipStreamSynchronize(hs), "hipMemcpyAsync(count plane)")   # (the host array may go away when this call returns)
+
+    def _loop_block(self, part, given, make):
+        """The block a loop writes to its frame: make(given), checked, when the loop was asked for `part`, else None."""
+        if not _given(given):
+            return None
+        _supported(self.be, part)
+        return make(given)
 
     def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
                  stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, features=None, **kw):
@@ -1198,22 +1037,13 @@ class Scene:
         (the planes start 64 bytes behind it)."""
         if step < 1:
             raise ValueError("step must be >= 1")
-        _squares_supported(self.be)
-        _counts_supported(self.be)
+        _supported(self.be, "squares")
+        _supported(self.be, "counts")
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
-        if features is not None and features is not False:
-            _features_supported(self.be)
-            features = make_features(None if features is True else features)
-        else:
-            features = None
-        if denoise is not None and denoise is not False:
-            _denoise_supported(self.be)
-            denoise = make_denoise(None if denoise is True else denoise)
-        else:
-            denoise = None
-        if out is not None and not isinstance(out, (CountsFrame, DenoiseFrame, FeaturesFrame)):
-            _retire_supported(self.be)
+        features, denoise = self._loop_block("features", features, make_features), self._loop_block("denoise", denoise, make_denoise)
+        if out is not None and not isinstance(out, Frame):
+            _supported(self.be, "retire")
             if preview is None:
                 raise ValueError("a device frame needs a device preview buffer (preview=)")
             if denoise is not None and denoised is None:
@@ -1226,28 +1056,20 @@ class Scene:
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
                          stream, kw, denoise=None, denoised=None, features=None):
-        hip = _hip_runtime()
+        hip, hs, ok = _hip_runtime(), _stream(stream), _hip_ok
         d_out, d_pv = _device_ptr(out), _device_ptr(preview)
-        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
-        plane = nx * ny
-        counts_at = d_out + 6 * plane * 4
-
-        def ok(rc, what):
-            if rc != 0:
-                raise RtError(ERR_DEVICE, "%s failed: %d" % (what, rc))
+        lay = FrameLayout(nx, ny, True, True, True, denoise is not None, features is not None)
+        plane, counts_at = lay.n, d_out + 4 * lay.counts
         # every pixel's target count is ns; the block's in-fields are written once (the library never writes them)
         ok(hip.hipMemsetD32Async(C.c_void_p(counts_at), ns - (1 << 32) if ns >= 1 << 31 else ns, plane, hs), "hipMemsetD32Async(counts)")
-        block = Retire()
-        block.target_se, block.min_samples, block.radius = float(target_se), int(min_samples), int(radius)
-        self._block_copy(nx, ny, d_out, block, stream, to_device=True)
-        if denoise is not None:   # (likewise: its in-fields once; the output plane sits 64 bytes behind the block)
-            d_off = denoise_block_offset(nx, ny, True, True)
-            self._block_copy(nx, ny, d_out, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
+        block = Retire(target_se=float(target_se), min_samples=int(min_samples), radius=int(radius))
+        self._block_copy(d_out, block, stream, True, 4 * lay.retire, C.sizeof(Retire))
+        if denoise is not None:   # (likewise: its in-fields once)
+            self._block_copy(d_out, denoise, stream, True, 4 * lay.denoise, Denoise.OUT_OFFSET)
         more = ()
         if features is not None:   # (its in-fields before the first slice, and once more, with compute = 0, behind it)
-            f_off = features_block_offset(nx, ny, True, True, True, denoise is not None)
-            self._block_copy(nx, ny, d_out, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
-            more = (f_off,)
+            self._block_copy(d_out, features, stream, True, 4 * lay.features, Features.OUT_OFFSET)
+            more = (4 * lay.features,)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
@@ -1258,10 +1080,10 @@ class Scene:
                                       want_stats=stats is not None)
             if features is not None and features.compute:
                 features.compute = 0
-                self._block_copy(nx, ny, d_out, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
+                self._block_copy(d_out, features, stream, True, 4 * lay.features, Features.OUT_OFFSET)
             if denoise is not None:
-                ok(hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_out + d_off + C.sizeof(Denoise)), plane * 3 * 4,
-                                      3, hs), "hipMemcpyAsync(denoised)")
+                ok(hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_out + 4 * lay.denoised), plane * 3 * 4, 3, hs),
+                   "hipMemcpyAsync(denoised)")
             if stats is not None:
                 stats.append(st)
             done = end
@@ -1270,7 +1092,7 @@ class Scene:
             ok(hip.hipMemcpyAsync(C.c_void_p(d_pv + plane * 3 * 4), C.c_void_p(counts_at), plane * 4, 3, hs), "hipMemcpyAsync(preview counts)")
             self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, counts=True, **kw),
                                  d_pv, hs)
-            self._block_copy(nx, ny, d_out, block, stream, to_device=False)
+            self._block_copy(d_out, block, stream, False, 4 * lay.retire, C.sizeof(Retire))
             info = block.as_dict()
             if denoise is not None:
                 yield (done, preview, info, denoised) + more
@@ -1309,20 +1131,11 @@ class Scene:
         and the item is the byte offset of the features block in it (the planes start 64 bytes behind it)."""
         if step < 1:
             raise ValueError("step must be >= 1")
-        if features is not None and features is not False:
-            _features_supported(self.be)
-            features = make_features(None if features is True else features)
-        else:
-            features = None
-        if denoise is not None and denoise is not False:
-            _squares_supported(self.be)
-            _denoise_supported(self.be)
-            denoise = make_denoise(None if denoise is True else denoise)
-        else:
-            denoise = None
-        squares = bool(squares) or target_rmse is not None or denoise is not None
+        features = self._loop_block("features", features, make_features)
+        squares = bool(squares) or target_rmse is not None or _given(denoise)
         if squares:
-            _squares_supported(self.be)
+            _supported(self.be, "squares")
+        denoise = self._loop_block("denoise", denoise, make_denoise)
         if out is not None and not isinstance(out, np.ndarray):
             if target_rmse is not None:
                 raise ValueError("target_rmse needs host frames: there is no device-side error reduction")
@@ -1335,30 +1148,26 @@ class Scene:
             return
         shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
         acc = np.zeros(shape, dtype=np.float32) if out is None else out
-        frame = None
-        if features is not None:   # the slices render into a FeaturesFrame; a caller's `out` is kept up to date beside it
+        frame = None   # with a block the slices render into a frame; a caller's `out` is kept up to date beside it
+        if features is not None:
             frame = FeaturesFrame(nx, ny, squares, denoise=denoise, features=features)
-            frame.planes[...] = acc
-        elif denoise is not None:   # ... or into a DenoiseFrame
+        elif denoise is not None:
             frame = DenoiseFrame(nx, ny, denoise=denoise)
-            frame.planes[...] = acc
+        if frame is not None:
+            frame.copy_in(acc)
+        on = {"denoise": True if denoise is not None else None, "features": True if features is not None else None}
         more = () if features is None else (frame,)
         sums = acc[0] if squares else acc
         t0 = time.perf_counter()
         done = 0
         while done < ns:
             end = min(ns, done + step)
+            self.par_cast(camera, nx, ny, end, seed=seed, out=acc if frame is None else frame, sample_begin=done, resume=True, partial=True,
+                          squares=squares, **on, **kw)
+            if frame is not None:
+                frame.copy_back(acc)
             if features is not None:
-                self.par_cast(camera, nx, ny, end, seed=seed, out=frame, denoise=True if denoise is not None else None, features=True,
-                              sample_begin=done, resume=True, partial=True, squares=squares, **kw)
                 frame.features.compute = 0   # (the planes are traced once)
-                acc[...] = frame.planes
-            elif frame is not None:
-                self.par_cast(camera, nx, ny, end, seed=seed, out=frame, denoise=True, sample_begin=done, resume=True, partial=True,
-                              squares=True, **kw)
-                acc[...] = frame.planes
-            else:
-                self.par_cast(camera, nx, ny, end, seed=seed, out=acc, sample_begin=done, resume=True, partial=True, squares=squares, **kw)
             done = end
             pv = sums.copy()   # resolve a copy: the running sum goes on
             self.par_cast(camera, nx, ny, done, seed=seed, out=pv, sample_begin=done, resume=True, **kw)
@@ -1377,17 +1186,15 @@ class Scene:
 
     def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw, denoise=None,
                             denoised=None, features=None):
-        hip = _hip_runtime()
+        hip, hs = _hip_runtime(), _stream(stream)
         d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
-        hs = C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
+        lay = FrameLayout(nx, ny, squares, False, False, denoise is not None, features is not None)
         if denoise is not None:   # the block's in-fields are written once (the library never writes them)
-            d_off = denoise_block_offset(nx, ny)
-            self._block_copy(nx, ny, acc, denoise, stream, to_device=True, offset=d_off, nbytes=Denoise.OUT_OFFSET)
+            self._block_copy(acc, denoise, stream, True, 4 * lay.denoise, Denoise.OUT_OFFSET)
         more = ()
         if features is not None:   # (its in-fields before the first slice, and once more, with compute = 0, behind it)
-            f_off = features_block_offset(nx, ny, squares, False, False, denoise is not None)
-            self._block_copy(nx, ny, acc, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
-            more = (f_off,)
+            self._block_copy(acc, features, stream, True, 4 * lay.features, Features.OUT_OFFSET)
+            more = (4 * lay.features,)
         t0 = time.perf_counter()
         done = 0
         while done < ns:
@@ -1397,24 +1204,19 @@ class Scene:
                                                      **kw), d_acc, hs)
             if features is not None and features.compute:
                 features.compute = 0
-                self._block_copy(nx, ny, acc, features, stream, to_device=True, offset=f_off, nbytes=Features.OUT_OFFSET)
+                self._block_copy(acc, features, stream, True, 4 * lay.features, Features.OUT_OFFSET)
             done = end
             if denoise is not None:
-                rc = hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_acc.value + d_off + C.sizeof(Denoise)),
-                                        nx * ny * 3 * 4, 3, hs)
-                if rc != 0:
-                    raise RtError(ERR_DEVICE, "hipMemcpyAsync(denoised) failed: %d" % rc)
-            rc = hip.hipMemcpyAsync(d_preview, d_acc, nx * ny * 3 * 4, 3, hs)   # plane 0; 3 = hipMemcpyDeviceToDevice
-            if rc != 0:
-                raise RtError(ERR_DEVICE, "hipMemcpyAsync(preview) failed: %d" % rc)
+                _hip_ok(hip.hipMemcpyAsync(C.c_void_p(_device_ptr(denoised)), C.c_void_p(d_acc.value + 4 * lay.denoised), lay.n * 3 * 4, 3, hs),
+                        "hipMemcpyAsync(denoised)")
+            _hip_ok(hip.hipMemcpyAsync(d_preview, d_acc, lay.n * 3 * 4, 3, hs), "hipMemcpyAsync(preview)")   # plane 0; 3 = hipMemcpyDeviceToDevice
             self.par_cast_device(camera, make_params(nx, ny, done, seed=seed, sample_begin=done, resume=True, **kw), d_preview, hs)
             if denoise is not None:
                 yield (done, preview, acc, denoised) + more
             else:
                 yield ((done, preview, acc) if squares else (done, preview)) + more
             if budget_s is not None:
-                if hip.hipStreamSynchronize(hs) != 0:
-                    raise RtError(ERR_DEVICE, "hipStreamSynchronize failed")
+                _hip_ok(hip.hipStreamSynchronize(hs), "hipStreamSynchronize")
                 if time.perf_counter() - t0 >= budget_s:
                     return
 
