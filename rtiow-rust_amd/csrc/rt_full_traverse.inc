@@ -1,6 +1,7 @@
 // rt_full_traverse.inc -- included INSIDE the traverse loop of the full-feature kernels: one box run or one slow pass over the
 // including kernel's per-lane traversal state (op, o, d, inv, best, pc, cur_lo / cur_hi, the hit record ...), `tune`, `stack`;
-// RT_R_PIXEL / RT_R_EVENT = the including kernel's expressions for the ray's pixel index and event number (its RNG stream).
+// RT_R_PIXEL / RT_R_EVENT = the including kernel's expressions for the ray's pixel index and event number (its RNG stream);
+// RT_FULL_SLOW_ARM = how it attaches the slow pass behind the box run: `else` or `if (!do_box)` (see there).
 // RT_CENSUS (diagnostic builds, instrumented variant only): where the 64 lanes of the wave stand at every box step [0..15] and at
 // every slow-pass iteration [16..31]: +0 BOX, +1 END (finished, waiting for a service), +2 no ray, +3 held at a gather point,
 // +4.. = op (SPHERE 6, RECT 7, PUSH 8, POP 9, MEDIUM 10, PRISM 11, BEND 12), +15 = iterations
@@ -34,7 +35,13 @@
                                          __builtin_amdgcn_ballot_w64(is_slow && !at_gather) == 0));
     const bool runnable = is_slow && (!at_gather || release);
     const uint64_t b_slow = __builtin_amdgcn_ballot_w64(runnable);
-    if (b_box != 0 && (uint32_t)__builtin_popcountll(b_slow) < tune.sphere_min) {
+    // The two arms on one wave-uniform flag.  RT_FULL_SLOW_ARM (the including kernel's) is how the slow pass is attached:
+    // `else`, or `if (!do_box)` -- the same arm in every state, but the second form leaves the compiler no join of two arms at
+    // which to keep a second copy of the walk's registers (rt_pool.h, traverse loop).  Which form a kernel takes is decided on
+    // its ISA (profiles/r15_traverse_shape/README.txt): the lock-step kernel loses 52 VALU and up to 23 VGPRs with the second,
+    // the first pool kernel's LIST / GENB instantiations gain spills with it.
+    const bool do_box = b_box != 0 && (uint32_t)__builtin_popcountll(b_slow) < tune.sphere_min;
+    if (do_box) {
 #ifdef RT_PHASE_PRIO
       __builtin_amdgcn_s_setprio(RT_FULL_BOX_PRIO);
 #endif
@@ -89,7 +96,8 @@
         if (COUNT) n_box_lanes += n_now;
       } while (n_now > floor_lanes);
       if (COUNT) t_box += RT_TICK() - t_mark;
-    } else {
+    }
+    RT_FULL_SLOW_ARM {
       // ---- slow pass: every parked lane executes one record, then runs ahead through up to
       // `run_ahead` - 1 more while enough lanes still sit on slow records (the objects of a list world
       // are visited in the same order by every ray, so these lanes mostly share their next kinds) ----

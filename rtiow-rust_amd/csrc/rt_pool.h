@@ -947,6 +947,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
           mstack = (mstack & ~(0xfu << lvl4_)) | (m_ << lvl4_); \
           wide_next(pc); \
         }
+  const int32_t box_leave_c = (int32_t)(tune.box_leave < 64u ? tune.box_leave : 64u);
   for (;;) {
     uint32_t op = have_ray ? (c_flags & 0xffu) : 0xffu;
     const uint64_t m_box = __builtin_amdgcn_ballot_w64(op == OP_BOX);
@@ -1287,20 +1288,38 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
     // the top): the big SERVICE block stays out of the cycle the wave spends its time in
     // (at least one box run or sphere pass per visit: after a service that found nothing to refill the test
     // still says "service" although there is nothing to service)
+    // The two arms are two `if`s on one wave-uniform flag, not `if ... else if`: both forms run the same arm in every state, but
+    // the compiler gave the `else if` form two register homes for the walk's state (pc, the record, best ...) and copied it
+    // between them twice per iteration (profiles/r15_traverse_shape); in this form the state lives in one place.
+    // Termination.  Each iteration is in exactly one of three states:
+    //  * do_box: the run executes at least one step, and b_box != 0 puts at least one lane into it.  A step moves every lane
+    //    at a BOX strictly forward in the finite program (pass: pc + REC_BOX; miss: the skip pointer, which the flattener only
+    //    ever points forward; WIDE: wide_next clears a pending-child bit or climbs to the parent).  `n_now > floor_lanes` needs
+    //    a lane at a BOX (floor_lanes >= 0), so every further step advances one too: the run ends.
+    //  * !do_box && b_sph != 0: the pass moves every lane at a SPHERE one record forward (WIDE: back to its node).
+    //  * neither: b_sph == 0, and b_box == 0 as well -- b_box != 0 with b_sph == 0 makes do_box true, because sphere_min >= 1
+    //    (rtg_scene_set_option keeps it there).  Then busy == 0 below and the loop is left.
+    // So an iteration either advances a lane's pc towards END -- at most 64 x (program length) times between two services --
+    // or leaves the loop; an iteration in which no arm runs still reaches the exit test, which stands behind both.
     uint64_t b_box = __builtin_amdgcn_ballot_w64(op == OP_BOX);
     uint64_t b_sph = __builtin_amdgcn_ballot_w64(op == OP_SPHERE);
     for (;;) {
-    if (b_box != 0 && (uint32_t)__builtin_popcountll(b_sph) < tune.sphere_min) {
+    const bool do_box = b_box != 0 && (uint32_t)__builtin_popcountll(b_sph) < tune.sphere_min;
+    if (do_box) {
       // box run: tight loop, schedule re-evaluated once `box_leave` lanes have left the BOX state
       if (COUNT) t_mark = RT_TICK();
       // The run's bookkeeping: ONE "is this lane at a BOX" compare per step -- made behind the step's record reload, it is the
       // next step's entry mask and, behind the last step of an iteration, the ballot of the exit test -- and an exit test
-      // that stays on the scalar unit (the saturating subtract would otherwise be formed as a vector instruction and drag
-      // the per-iteration compare with it)
-      const uint32_t n0 = (uint32_t)__builtin_popcountll(b_box);
-      const uint32_t floor_lanes = __builtin_amdgcn_readfirstlane(n0 > tune.box_leave ? n0 - tune.box_leave : 0u);
+      // that stays on the scalar unit.  Entering a run costs no vector instruction: floor_lanes = max(n0 - box_leave, 0) in
+      // SIGNED arithmetic on the lane count (s_bcnt1, s_sub, s_max; box_leave clamped to 64 once per launch -- the unsigned
+      // saturating form has no scalar instruction and was formed on the vector unit), and the first step's entry mask is
+      // b_box itself: "op == OP_BOX" and RT_IS_BOX() say the same of every lane (a lane without a ray carries c_flags = 0xff;
+      // the staged image sets LDS_BOX_BIT on BOX records / nodes and on nothing else)
+      const int32_t n0 = __builtin_popcountll(b_box);
+      const int32_t floor_i = n0 - box_leave_c;
+      const uint32_t floor_lanes = (uint32_t)(floor_i > 0 ? floor_i : 0);
       uint32_t n_now;
-      bool in_box = RT_IS_BOX();
+      bool in_box = __builtin_amdgcn_inverse_ballot_w64(b_box);
       do {
         if (COUNT) n_box_it++;
         if (WIDE) {
@@ -1322,7 +1341,8 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
         if (COUNT) n_box_lanes += n_now;
       } while (n_now > floor_lanes);
       if (COUNT) t_box += RT_TICK() - t_mark;
-    } else if (b_sph != 0) {
+    }
+    if (!do_box && b_sph != 0) {
       if (COUNT) n_sph_it++, n_sph_lanes += (uint32_t)__builtin_popcountll(b_sph), t_mark = RT_TICK();
       if (op == OP_SPHERE) {  // Sphere::hit, object.rs:84-111 (+ Translate :275)
         if (COUNT) cnt.prim++;

@@ -801,7 +801,9 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
 #define RT_R_EVENT (r_bounces + 1u)
 #define RT_PHASE_PRIO 1  // (the pool schedule sets wave priorities per phase: see RT_FULL_SLOW_PRIO)
 #define RT_CENSUS_HERE 1
+#define RT_FULL_SLOW_ARM else
 #include "rt_full_traverse.inc"
+#undef RT_FULL_SLOW_ARM
 #undef RT_CENSUS_HERE
 #undef RT_PHASE_PRIO
 #undef RT_R_PIXEL

@@ -246,7 +246,9 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
 #define RT_R_PIXEL r_pixel
 #define RT_R_EVENT r_event
 #define RT_PHASE_PRIO 1  // wave priorities per phase (rt_pool_full.h RT_FULL_SLOW_PRIO): slow passes 3, box runs 1, the SHADE / GEN phase 0
+#define RT_FULL_SLOW_ARM if (!do_box)
 #include "rt_full_traverse.inc"
+#undef RT_FULL_SLOW_ARM
 #undef RT_PHASE_PRIO
 #undef RT_R_PIXEL
 #undef RT_R_EVENT

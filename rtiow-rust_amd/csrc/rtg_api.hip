@@ -710,7 +710,7 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "gather_min") s->pool_tune.gather_min = s->full_tune.gather_min = s->sync_tune.gather_min = u;
   else if (k == "run_ahead") s->pool_tune.run_ahead = s->full_tune.run_ahead = s->sync_tune.run_ahead = u;
   else if (k == "run_ahead_min") s->pool_tune.run_ahead_min = s->full_tune.run_ahead_min = s->sync_tune.run_ahead_min = u;
-  else if (k == "sphere_min") s->pool_tune.sphere_min = s->full_tune.sphere_min = s->sync_tune.sphere_min = u;
+  else if (k == "sphere_min") s->pool_tune.sphere_min = s->full_tune.sphere_min = s->sync_tune.sphere_min = std::max(1u, u);  // (0 would let no arm run while lanes sit at a BOX; 0 and 1 choose alike otherwise)
   else if (k == "p2_refill") s->pool2_tune.refill_min = u;      // pool-2 kernel's schedule thresholds (rt_pool2.h Pool2Tuning)
   else if (k == "p2_box_leave") s->pool2_tune.box_leave = u;
   else if (k == "p2_park") s->pool2_tune.park_max = u;

@@ -108,10 +108,21 @@ def parse_kernel(lines, prefix):
     return out
 
 
-def region_cost(instrs, fname, a, b):
+def region_cost(instrs, fname, a, b, others=()):
+    """`others`: (file, first line, last line) of the kernel's other regions.  The compiler may lay a region's blocks out AROUND
+    another region's cluster (the lean kernel's sphere pass around the box run, since its two arms are two `if`s: the pass's
+    tail blocks stand in front of the run, its head behind it, and the inlined Sphere::hit behind the last instruction of the
+    region's own lines).  First-to-last would then count the nested cluster and miss the helper code.  Such a cluster is counted
+    as its pieces: the nested cluster and the instructions of the kernel file's other lines (loop control) are left out, and the
+    header-attributed instructions directly behind the last piece are taken in.  A cluster with nothing nested is counted as ever."""
     idx = [i for i, (_, (f, ln)) in enumerate(instrs) if f == fname and a <= ln <= b]
     if not idx:
         return None
+    nested_spans = []
+    for of, oa, ob in others:
+        oi = [i for i, (_, (f, ln)) in enumerate(instrs) if f == of and oa <= ln <= ob]
+        if oi:
+            nested_spans.append((oi[0], oi[-1]))
     clusters, first, last = [], idx[0], idx[0]
     for i in idx[1:]:
         if i - last > 400:
@@ -121,10 +132,19 @@ def region_cost(instrs, fname, a, b):
     clusters.append((first, last))
     best = None
     for f, l in clusters:
-        span = instrs[f:l + 1]
+        inside = [(nf, nl) for nf, nl in nested_spans if f < nf and nl < l]
+        if inside:
+            while l + 1 < len(instrs) and instrs[l + 1][1][0] != fname:
+                l += 1
+            span = [ins for i, ins in enumerate(instrs[f:l + 1], f) if not any(nf <= i <= nl for nf, nl in inside)
+                    and (ins[1][0] != fname or a <= ins[1][1] <= b)]
+        else:
+            span = instrs[f:l + 1]
         valu = sum(1 for op, _ in span if op.startswith("v_"))
         if best is None or valu > best["valu"]:
             best = {"valu": valu, "instructions": len(span), "special_rate": sum(1 for op, _ in span if re.match(r"v_(rcp|sqrt|rsq|mad_u64|mul_hi|mul_lo|div_)", op))}
+            if inside:
+                best["laid_out_around_another_region"] = True
     best["clusters"] = len(clusters)
     return best
 
@@ -167,7 +187,8 @@ def main():
         k = {"kernel": pretty, "instructions_total": len(instrs), "valu_total": sum(1 for op, _ in instrs if op.startswith("v_")), "regions": {}}
         for name, (fname, begin, _, end, div) in regions.items():
             a, b = find_lines(os.path.join(CSRC, fname), begin, end)
-            c = region_cost(instrs, fname, a, b)
+            others = [(of,) + find_lines(os.path.join(CSRC, of), ob_, oe_) for on, (of, ob_, _, oe_, _) in regions.items() if on != name]
+            c = region_cost(instrs, fname, a, b, others)
             if c is None:
                 raise SystemExit("%s: no instruction for %s:%d-%d" % (pretty, fname, a, b))
             c.update({"file": fname, "lines": [a, b], "per_operation": c["valu"] / float(div)})
