@@ -345,7 +345,11 @@ void rtg_scene_destroy(rtg_scene* s);
 /* Scheduling / measurement switches of one scene handle -- kernel generation, cost-ordered work queue, pool
  * thresholds, workgroup size (names: DESIGN.md section 4 "Knobs").  None of them changes a bit of the result.  The
  * library reads no environment variable for these.  "box_chains" = 0 stages the full LDS image of a lean
- * program (default 1: the image without box-chain followers; the same framebuffer and counters).  "bvh4" = 1 (scenes
+ * program (default 1: the image without box-chain followers; the same framebuffer and counters).  "box_prune" (default 1)
+ * leaves out of that image the interior BOX records of the pruning plan too (rtiow_gpu_debug.h rtg_debug_box_plan): the
+ * same framebuffer and counters; 0 = off; 2 = counting launches (rtg_stats) stage that image as well, so aabb_tests reports
+ * what the production walk executes (fewer than the reference's; every other counter unchanged; a measurement switch).
+ * "bvh4" = 1 (scenes
  * that are ONE Bvh of spheres; RTG_ERR_INVALID otherwise) traverses the reference's tree (bvh.rs:22-120) as 4-wide
  * nodes: the same framebuffer, other rtg_stats.aabb_tests / prim_tests than the reference's walk. */
 int rtg_scene_set_option(rtg_scene* s, const char* name, int value);

@@ -1,0 +1,24 @@
+/* rtiow_gpu_debug.h -- host-only inspection entry points of librtiow_gpu.so that have no counterpart in a CPU restatement of
+ * the renderer and are not part of the ABI of rtiow_gpu.h (bindings that mirror that header need not follow this one). */
+#ifndef RTIOW_GPU_DEBUG_H
+#define RTIOW_GPU_DEBUG_H
+#include "rtiow_gpu.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The box plan of a lean program (BOX / SPHERE / END records; csrc/rt_box_plan.h), from the function rtg_scene_create calls
+ * for the production image of the lean pool kernel: mask_out[i] = 0 record i is kept, 1 it is a box-chain follower (the rule
+ * rtg_scene_info's n_box_followers counts), 2 it is an interior BOX the plan leaves out (scene option "box_prune").  Every
+ * other program gets zeros.  (rtg_scene_create itself makes no plan for a program whose image cannot fit a CU's LDS even
+ * without its interior boxes -- such a program is never staged; this entry point plans every lean program.)
+ * The program is `world` flattened by `b`, as rtg_debug_flatten does -- or, when `words` is not NULL, the n_records x 8 words
+ * given (the layout rtg_debug_flatten writes; b and world are then ignored).
+ * Writes min(record count, capacity) bytes; returns the record count, or a negative rtg_status.  Works without a GPU. */
+int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
+                       uint8_t* mask_out, size_t capacity);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RTIOW_GPU_DEBUG_H */

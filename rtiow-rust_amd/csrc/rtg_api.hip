@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enums only: librccl is dlopen()ed by rtg_par_cast_multi, never linked
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,7 +20,9 @@
 #include <vector>
 
 #include "../../include/rtiow_gpu.h"
+#include "../../include/rtiow_gpu_debug.h"
 #include "rt_pool.h"
+#include "rt_box_plan.h"
 #include "rt_retire.h"
 #include "rt_denoise.h"
 #include "rt_features.h"
@@ -103,7 +106,7 @@ struct rtg_scene {
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   uint64_t bytes = 0;
-  void* buffers[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  void* buffers[15] = {};
   const uint32_t* d_parent = nullptr;  // buffers[8]: the wrapper around every program record (rt_pool_full.h rebuild_hit)
   hipStream_t own_stream = nullptr;  // rtg_par_cast_multi: this scene's launch stream (created on first use)
   int num_cus = 0;
@@ -130,6 +133,17 @@ struct rtg_scene {
   uint32_t n_followers = 0;    // ... records that image drops (0: it is the full image, and buffers[12] is not allocated)
   const uint32_t* d_chain_off = nullptr;  // buffers[12]: the record offsets of that image
   uint32_t chain_bytes = 0;    // ... and its size
+  // box pruning (rt_box_plan.h): 1 = production launches stage the image without the plan's interior boxes, 2 = counting launches
+  // too (their aabb_tests then report what the production walk executes), 0 = off
+  int box_prune = 1;
+  uint32_t n_pruned = 0;       // records the plan leaves out beyond the followers
+  float plan_ms = 0.f;         // host time of the plan (option verbose)
+  // buffers[13 + chains]: record offsets of the pruned image, [1] without the followers too (the default), [0] with them (option
+  // box_chains = 0: a measurement switch, so that table is made when the option is first set -- prune_table below)
+  const uint32_t* d_prune_off[2] = {nullptr, nullptr};
+  uint32_t prune_bytes[2] = {0, 0};
+  std::vector<uint32_t> plan_ops;  // ... from these: every record's flag word and its mask (BOX_KEPT / BOX_FOLLOWER / BOX_PRUNED)
+  std::vector<uint8_t> plan_mask;
   int sync_full = -1;          // full-feature scenes on the pool-free lock-step kernel (rt_sync_full.h): -1 = when the program holds no BOX record, 0 / 1 = never / always
   uint32_t n_box = 0;          // BOX records of the flat program
   int lpt = 2;                 // RTG_LPT=0: natural order throughout; 1 / 2 = LptQueue::mode
@@ -526,6 +540,21 @@ static int upload(void** dst, const void* src, size_t bytes, uint64_t* total) {
   return RTG_OK;
 }
 
+// The record offsets of the pruned image of a lean program (rt_box_plan.h): the plan's records 0 bytes, and the box-chain
+// followers too (chains = 1) or not; made once per scene and kind.
+static int prune_table(rtg_scene* s, int chains) {
+  if (s->d_prune_off[chains] || !s->n_pruned) return RTG_OK;
+  const size_t n = s->plan_mask.size();
+  std::vector<uint8_t> drop(n);
+  std::vector<uint32_t> off(n);
+  for (size_t i = 0; i < n; i++) drop[i] = s->plan_mask[i] == BOX_PRUNED || (chains && s->plan_mask[i] == BOX_FOLLOWER);
+  s->prune_bytes[chains] = lds_image_offsets(s->plan_ops.data(), n, off.data(), drop.data());
+  int rc = upload(&s->buffers[13 + chains], off.data(), n * sizeof(uint32_t), &s->bytes);
+  if (rc) return rc;
+  s->d_prune_off[chains] = (const uint32_t*)s->buffers[13 + chains];
+  return RTG_OK;
+}
+
 void rtg_scene_destroy(rtg_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
@@ -637,6 +666,21 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
       }
       s->d_chain_off = (const uint32_t*)s->buffers[12];
     }
+    // the pruned images (rt_box_plan.h): the plan's records 0 bytes, with and without the followers.  (Only staged images
+    // have pruned records: no plan for a program that cannot fit a CU's LDS even without its interior boxes.)
+    if (s->dev.lds_image_bytes - LDS_BOX_BYTES * (s->n_box / 2u) <= 160u * 1024u) {
+      s->plan_mask.resize(fs.hi.size());
+      const auto t0 = std::chrono::steady_clock::now();
+      s->n_pruned = box_plan(reinterpret_cast<const uint32_t (*)[4]>(fs.lo.data()), reinterpret_cast<const uint32_t (*)[4]>(fs.hi.data()), fs.hi.size(), follower.data(), s->plan_mask.data()).n_pruned;
+      s->plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (s->n_pruned) {
+        s->plan_ops = ops;
+        if ((rc = prune_table(s, 1))) {
+          rtg_scene_destroy(s);
+          return rc;
+        }
+      }
+    }
     std::vector<uint32_t> wide;
     if (build_wide_image(fs.lo.data(), fs.hi.data(), fs.hi.size(), wide)) {
       if ((rc = upload(&s->buffers[7], wide.data(), wide.size() * sizeof(uint32_t), &s->bytes))) {
@@ -674,7 +718,18 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "lpt_deep") s->lpt_deep = value;
   else if (k == "lpt_shift") s->lpt_shift = std::min(6, std::max(0, value));
   else if (k == "ray_lds") s->ray_lds = value;
-  else if (k == "box_chains") s->box_chains = value;            // 0: production launches stage the full image, box-chain followers included (A/B switch)
+  else if (k == "box_chains") {                                 // 0: production launches stage the image with its box-chain followers (A/B switch)
+    if (!value) {  // ... and, with box_prune on, without the pruned records only: that table is made now
+      HIP_TRY(hipSetDevice(s->device));
+      int rc = prune_table(s, 0);
+      if (rc) return rc;
+    }
+    s->box_chains = value;
+  }
+  else if (k == "box_prune") {                                  // 0: no interior box pruned; 1: production launches; 2: counting launches too (rtg_scene above)
+    if (value < 0 || value > 2) return fail(RTG_ERR_INVALID, "box_prune: 0 .. 2");
+    s->box_prune = value;
+  }
   else if (k == "bvh4") {
     if (value && !s->wide_bytes) return fail(RTG_ERR_INVALID, "bvh4: the scene is not one Bvh of spheres (no 4-wide image)");
     if (value && pool_lds_bytes(s->wide_bytes, s->n_mat, (uint32_t)(s->pool_threads > 0 ? s->pool_threads : RT_POOL_MAX_THREADS) / 64u, true, false) > 160 * 1024)

@@ -216,12 +216,15 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   const uint32_t waves = (uint32_t)bt / 64;
   const size_t lds_limit = 160 * 1024;
   const bool wide = s->bvh4 && s->wide_bytes != 0 && !sl.counts;
-  // production launches stage the image without box-chain followers (rt_pool.h box_chain_followers); counting launches keep
-  // the full image, so that their counters and traces report every test of the reference's walk
+  // production launches stage the image without box-chain followers (rt_pool.h box_chain_followers) and without the interior
+  // boxes of the pruning plan (rt_box_plan.h); counting launches keep the full image, so that their counters and traces report
+  // every test of the reference's walk (option box_prune = 2: they stage the pruned image too, and report the production walk's)
   const bool chains = !COUNT && !wide && s->box_chains && s->d_chain_off != nullptr;
+  const bool prune = !wide && s->box_prune && (!COUNT || s->box_prune == 2) && s->d_prune_off[s->box_chains ? 1 : 0] != nullptr;
   DevScene dev = s->dev;
   if (wide) dev.lds_off = (const uint32_t*)s->buffers[7], dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
   if (chains) dev.lds_off = s->d_chain_off, dev.lds_image_bytes = s->chain_bytes;
+  if (prune) dev.lds_off = s->d_prune_off[s->box_chains ? 1 : 0], dev.lds_image_bytes = s->prune_bytes[s->box_chains ? 1 : 0];
   const uint32_t image = dev.lds_image_bytes;
   bool use_lds = image != 0 && pool_lds_bytes(image, s->n_mat, waves, true, false) <= lds_limit;
   if (wide && !use_lds) return hipErrorNotSupported;  // (rtg_scene_set_option refuses bvh4 for images that do not fit)
@@ -237,9 +240,10 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   } else if (wide) kernel = ray_lds ? render_lean_pool<true, COUNT, true, true> : render_lean_pool<true, COUNT, false, true>;
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
-  if (s->verbose && chains && use_lds)
-    fprintf(stderr, "[rtg] pool: box chains: %u follower record(s) dropped from the LDS image (%u B, full image %u B)\n",
-            s->n_followers, s->chain_bytes, s->dev.lds_image_bytes);
+  if (s->verbose && (chains || prune) && use_lds)
+    fprintf(stderr, "[rtg] pool: box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
+            s->n_followers, s->box_chains ? " dropped" : " kept", s->n_pruned, prune ? " dropped" : " kept", s->plan_ms, image,
+            s->n_prog - (s->box_chains ? s->n_followers : 0u) - (prune ? s->n_pruned : 0u), s->n_prog, s->chain_bytes ? s->chain_bytes : s->dev.lds_image_bytes, s->dev.lds_image_bytes);
   PoolLaunch L{KernelKind::lean_pool, bt, 0, lds, geo, POOL};
   hipError_t e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
   if (e != hipSuccess) return e;

@@ -184,6 +184,42 @@ int rtg_debug_flatten_pool2(rtg_builder* b, const rtg_id* world, size_t n, uint3
   return RTG_OK;
 }
 
+// Host-only (include/rtiow_gpu_debug.h): the box plan of a lean program -- per record 0 kept, 1 box-chain follower, 2 pruned
+// (rt_box_plan.h) -- by the function rtg_scene_create calls (which skips it for programs too large to be staged; this does not).  `words` (8 per record, as rtg_debug_flatten writes them) replaces the
+// flattened world when given.  Returns the record count, or a negative error code.
+int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records, uint8_t* mask_out,
+                       size_t capacity) {
+  std::vector<Packet> lo, hi;
+  bool lean = true;
+  if (words) {
+    lo.resize(n_records), hi.resize(n_records);
+    for (size_t i = 0; i < n_records; i++) {
+      std::memcpy(lo[i].w, words + 8 * i, 16), std::memcpy(hi[i].w, words + 8 * i + 4, 16);
+      const uint32_t op = hi[i].w[3] & 0xffu;
+      lean = lean && (op == OP_BOX || op == OP_SPHERE || op == OP_END) && !(hi[i].w[3] & F_MOVE);
+      if (op == OP_BOX && hi[i].w[2] >= n_records) return fail(RTG_ERR_INVALID, "rtg_debug_box_plan: a skip pointer leaves the program");
+    }
+  } else {
+    if (!b || (!world && n)) return fail(RTG_ERR_INVALID, "null argument");
+    FlatScene fs;
+    try {
+      b->sb.flatten(world, n, &fs);
+    } catch (const BuildError& e) {
+      return fail(e.code, e.msg);
+    }
+    lean = (fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0;
+    lo.swap(fs.lo), hi.swap(fs.hi);
+  }
+  if (hi.size() > 0x7fffffffu) return fail(RTG_ERR_INVALID, "rtg_debug_box_plan: program too large");
+  std::vector<uint8_t> follower(hi.size(), 0), mask(hi.size(), 0);
+  if (lean && !hi.empty()) {
+    box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), follower.data());
+    box_plan(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), follower.data(), mask.data());
+  }
+  if (mask_out) std::memcpy(mask_out, mask.data(), std::min(mask.size(), capacity));
+  return (int)hi.size();
+}
+
 int rtg_debug_math(int device, int op, size_t n, const float* in, const float* in2, float* out) {
   if (!in || !out || op < 0 || op > 5 || (op == 5 && !in2)) return fail(RTG_ERR_INVALID, "bad argument");
   int ndev = 0;

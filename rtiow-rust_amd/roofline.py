@@ -39,7 +39,7 @@ def source_stamp(root):
     import hashlib
     csrc = os.path.join(root, "rtiow-rust_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".inc", ".hip", ".cpp")) or f == "Makefile")
-    files = [os.path.join("rtiow-rust_amd", "csrc", f) for f in files] + [os.path.join("include", "rtiow_gpu.h")]
+    files = [os.path.join("rtiow-rust_amd", "csrc", f) for f in files] + [os.path.join("include", f) for f in sorted(os.listdir(os.path.join(root, "include"))) if f.endswith(".h")]
     blobs = {}
     for rel in files:
         data = open(os.path.join(root, rel), "rb").read()
