@@ -18,6 +18,16 @@ extern "C" {
 int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
                        uint8_t* mask_out, size_t capacity);
 
+/* The production program of a lean program (csrc/rt_box_plan.h box_tree_rebuild; scene option "box_tree"): the program that
+ * production launches of the lean pool kernel stage -- every maximal Bvh region rebuilt over the same leaf order, everything
+ * else copied.  The program is given as for rtg_debug_box_plan.  words_out: record count x 8 words in rtg_debug_flatten's
+ * layout; origin_out[i]: the record of the given program that record i copies, 0xffffffff for a new interior BOX; mask_out:
+ * the plan over the production program (0 / 1 / 2 as above).  Another kind of program comes back unchanged, with
+ * origin_out[i] = i and zeros.  Each array may be NULL; min(record count, capacity) records are written.  Returns the record
+ * count, or a negative rtg_status.  Works without a GPU. */
+int rtg_debug_production_program(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
+                                 uint32_t* words_out, uint32_t* origin_out, uint8_t* mask_out, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -615,6 +615,7 @@ class Backend:
         f("tonemap_device", C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p])
         # include/rtiow_gpu_debug.h (not part of ABI_SYMBOLS: no CPU restatement mirrors it)
         f("debug_box_plan", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u8p, C.c_size_t])
+        f("debug_production_program", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u32p, c_u32p, c_u8p, C.c_size_t])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -854,6 +855,29 @@ class Builder:
             self.be.check(n)
         return mask
 
+    def production_program(self, world=None, words=None):
+        """Host-only (product library): the production program of a lean program (csrc/rt_box_plan.h box_tree_rebuild; scene
+        option box_tree) as (words [n, 8] uint32, origin [n] uint32, mask [n] uint8): origin[i] is the record of the given
+        program that record i copies (0xffffffff: a new interior box), mask the box plan over the production program.
+        `words` ([n, 8] uint32, as flatten returns them) replaces the world."""
+        if words is not None:
+            words = np.ascontiguousarray(words, dtype=np.uint32)
+            head = (None, None, 0, words.ctypes.data_as(c_u32p), len(words))
+            n = len(words)
+        else:
+            arr = (C.c_uint32 * max(1, len(world)))(*world)
+            head = (self.h, arr, len(world), None, 0)
+            n = self.be._debug_production_program(*head, None, None, None, 0)
+            if n < 0:
+                self.be.check(n)
+        out = np.zeros((n, 8), dtype=np.uint32)
+        origin = np.zeros(n, dtype=np.uint32)
+        mask = np.zeros(n, dtype=np.uint8)
+        n = self.be._debug_production_program(*head, out.ctypes.data_as(c_u32p), origin.ctypes.data_as(c_u32p), mask.ctypes.data_as(c_u8p), n)
+        if n < 0:
+            self.be.check(n)
+        return out, origin, mask
+
     def bvh_sah(self, objs, exposure=(0.0, 1.0)):
         """Not in the reference: SAH-built Bvh; same results up to exact-t ties, fewer box tests."""
         arr = (C.c_uint32 * max(1, len(objs)))(*objs)
@@ -889,7 +913,7 @@ class Scene:
     # measurement / test hook: RTG_<OPTION>=<int> in the environment of the PYTHON process becomes
     # rtg_scene_set_option(scene, "<option>", <int>) -- the library itself reads no environment variable
     ENV_OPTIONS = ("kernel", "chunks", "lpt", "lpt_phase1", "lpt_deep", "lpt_shift", "ray_lds", "sync", "block", "wg_per_cu", "window",
-                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push")
+                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push")
 
     def set_option(self, name, value):
         self.be.check(self.be._scene_set_option(self.h, name.encode(), int(value)))

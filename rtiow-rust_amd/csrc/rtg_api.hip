@@ -100,13 +100,36 @@ struct LaunchCtx {
   rtg_features features_in{};   // ... the block's in-fields of a call without a count plane, read back before its first kernel
 };
 
+// The LDS images of ONE lean program (rt_pool.h): the full one, the one without box-chain followers and the ones without the
+// records of the pruning plan.  A scene has two: the reference program's and the rebuilt one's (rt_box_plan.h box_tree_rebuild).
+struct LeanImages {
+  const uint4* lo = nullptr;   // the program on the device; nullptr = the scene has no such program
+  const uint4* hi = nullptr;
+  const uint32_t* d_off = nullptr;  // record offsets of the full image, and its size
+  uint32_t bytes = 0;
+  uint32_t n_followers = 0;    // records the production image drops (0: it is the full image, and no table is allocated)
+  const uint32_t* d_chain_off = nullptr;  // buffers[slot]: the record offsets of that image
+  uint32_t chain_bytes = 0;    // ... and its size
+  bool planned = false;        // the pruning plan is made (at creation for the program that production launches stage, else on demand)
+  uint32_t n_pruned = 0;       // records the plan leaves out beyond the followers
+  float plan_ms = 0.f;         // host time of the plan (option verbose)
+  // buffers[slot + 1 + chains]: record offsets of the pruned image, [1] without the followers too (the default), [0] with them
+  // (option box_chains = 0: a measurement switch, so that table is made when the option is first set -- prune_table below)
+  const uint32_t* d_prune_off[2] = {nullptr, nullptr};
+  uint32_t prune_bytes[2] = {0, 0};
+  std::vector<uint32_t> plan_ops;  // ... from these: every record's flag word and its mask (BOX_KEPT / BOX_FOLLOWER / BOX_PRUNED)
+  std::vector<uint8_t> plan_mask;
+  std::vector<uint8_t> follower;
+  int slot = 12;               // first of this program's three offset tables in rtg_scene::buffers
+};
+
 struct rtg_scene {
   int device = 0;
   DevScene dev{};
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   uint64_t bytes = 0;
-  void* buffers[15] = {};
+  void* buffers[21] = {};
   const uint32_t* d_parent = nullptr;  // buffers[8]: the wrapper around every program record (rt_pool_full.h rebuild_hit)
   hipStream_t own_stream = nullptr;  // rtg_par_cast_multi: this scene's launch stream (created on first use)
   int num_cus = 0;
@@ -130,20 +153,19 @@ struct rtg_scene {
   int bvh4 = 0;                // 1: traverse the 4-wide collapse of the Bvh (same image, other counters; needs wide_bytes)
   uint32_t wide_bytes = 0;     // size of the 4-wide image in buffers[7], 0 = the scene has none
   int box_chains = 1;          // production launches of the lean pool kernel stage the image without box-chain followers (rt_pool.h); 0 = off
-  uint32_t n_followers = 0;    // ... records that image drops (0: it is the full image, and buffers[12] is not allocated)
-  const uint32_t* d_chain_off = nullptr;  // buffers[12]: the record offsets of that image
-  uint32_t chain_bytes = 0;    // ... and its size
   // box pruning (rt_box_plan.h): 1 = production launches stage the image without the plan's interior boxes, 2 = counting launches
   // too (their aabb_tests then report what the production walk executes), 0 = off
   int box_prune = 1;
-  uint32_t n_pruned = 0;       // records the plan leaves out beyond the followers
-  float plan_ms = 0.f;         // host time of the plan (option verbose)
-  // buffers[13 + chains]: record offsets of the pruned image, [1] without the followers too (the default), [0] with them (option
-  // box_chains = 0: a measurement switch, so that table is made when the option is first set -- prune_table below)
-  const uint32_t* d_prune_off[2] = {nullptr, nullptr};
-  uint32_t prune_bytes[2] = {0, 0};
-  std::vector<uint32_t> plan_ops;  // ... from these: every record's flag word and its mask (BOX_KEPT / BOX_FOLLOWER / BOX_PRUNED)
-  std::vector<uint8_t> plan_mask;
+  // box tree (rt_box_plan.h box_tree_rebuild): 1 = production launches of the staged lean pool kernel (and, with box_prune = 2,
+  // its counting launches) walk the program whose Bvh regions are rebuilt over the same leaf order; 0 = the reference program
+  int box_tree = 1;
+  LeanImages ref;              // the reference program (dev.lo / dev.hi; offset tables in buffers[6], [12], [13], [14])
+  LeanImages tree;             // the rebuilt one (buffers[15], [16]; tables in [17] .. [20]); tree.lo = nullptr: no region was rebuilt
+  bool tree_tried = false;     // ... and whether the rebuild has run
+  float tree_ms = 0.f;         // host time of the rebuild (option verbose)
+  uint32_t n_regions = 0;      // regions rebuilt
+  bool plannable = false;      // a lean program whose image may fit a CU's LDS without its interior boxes: it gets plans
+  std::vector<Packet> h_lo, h_hi;  // ... and keeps the host copy that plans made on demand read
   int sync_full = -1;          // full-feature scenes on the pool-free lock-step kernel (rt_sync_full.h): -1 = when the program holds no BOX record, 0 / 1 = never / always
   uint32_t n_box = 0;          // BOX records of the flat program
   int lpt = 2;                 // RTG_LPT=0: natural order throughout; 1 / 2 = LptQueue::mode
@@ -541,17 +563,72 @@ static int upload(void** dst, const void* src, size_t bytes, uint64_t* total) {
 }
 
 // The record offsets of the pruned image of a lean program (rt_box_plan.h): the plan's records 0 bytes, and the box-chain
-// followers too (chains = 1) or not; made once per scene and kind.
-static int prune_table(rtg_scene* s, int chains) {
-  if (s->d_prune_off[chains] || !s->n_pruned) return RTG_OK;
-  const size_t n = s->plan_mask.size();
+// followers too (chains = 1) or not; made once per scene, program and kind.
+static int prune_table(rtg_scene* s, LeanImages* im, int chains) {
+  if (im->d_prune_off[chains] || !im->n_pruned) return RTG_OK;
+  const size_t n = im->plan_mask.size();
   std::vector<uint8_t> drop(n);
   std::vector<uint32_t> off(n);
-  for (size_t i = 0; i < n; i++) drop[i] = s->plan_mask[i] == BOX_PRUNED || (chains && s->plan_mask[i] == BOX_FOLLOWER);
-  s->prune_bytes[chains] = lds_image_offsets(s->plan_ops.data(), n, off.data(), drop.data());
-  int rc = upload(&s->buffers[13 + chains], off.data(), n * sizeof(uint32_t), &s->bytes);
+  for (size_t i = 0; i < n; i++) drop[i] = im->plan_mask[i] == BOX_PRUNED || (chains && im->plan_mask[i] == BOX_FOLLOWER);
+  im->prune_bytes[chains] = lds_image_offsets(im->plan_ops.data(), n, off.data(), drop.data());
+  int rc = upload(&s->buffers[im->slot + 1 + chains], off.data(), n * sizeof(uint32_t), &s->bytes);
   if (rc) return rc;
-  s->d_prune_off[chains] = (const uint32_t*)s->buffers[13 + chains];
+  im->d_prune_off[chains] = (const uint32_t*)s->buffers[im->slot + 1 + chains];
+  return RTG_OK;
+}
+
+// The full image's offsets (buffers[off_slot]), the followers and the image without them (buffers[im->slot]) of the program
+// (lo, hi), which is on the device already (im->lo, im->hi).
+static int lean_images(rtg_scene* s, LeanImages* im, const std::vector<Packet>& lo, const std::vector<Packet>& hi, int off_slot) {
+  std::vector<uint32_t> off(hi.size());
+  im->plan_ops.resize(hi.size());
+  for (size_t i = 0; i < hi.size(); i++) im->plan_ops[i] = hi[i].w[3];
+  im->bytes = lds_image_offsets(im->plan_ops.data(), hi.size(), off.data());
+  int rc = upload(&s->buffers[off_slot], off.data(), off.size() * sizeof(uint32_t), &s->bytes);
+  if (rc) return rc;
+  im->d_off = (const uint32_t*)s->buffers[off_slot];
+  im->follower.resize(hi.size());
+  im->n_followers = box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), im->follower.data());
+  if (im->n_followers) {  // the production image: every follower 0 bytes (the counting launches keep the full one)
+    im->chain_bytes = lds_image_offsets(im->plan_ops.data(), hi.size(), off.data(), im->follower.data());
+    if ((rc = upload(&s->buffers[im->slot], off.data(), off.size() * sizeof(uint32_t), &s->bytes))) return rc;
+    im->d_chain_off = (const uint32_t*)s->buffers[im->slot];
+  }
+  return RTG_OK;
+}
+
+// The pruning plan of one program and its default table, once.  (Only staged images have pruned records: no plan for a
+// program that cannot fit a CU's LDS even without its interior boxes -- rtg_scene::plannable.)
+static int lean_plan(rtg_scene* s, LeanImages* im, const std::vector<Packet>& lo, const std::vector<Packet>& hi, BoxPlanKind kind) {
+  if (im->planned || !s->plannable) return RTG_OK;
+  im->planned = true;
+  im->plan_mask.resize(hi.size());
+  const auto t0 = std::chrono::steady_clock::now();
+  im->n_pruned = box_plan(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), im->follower.data(), im->plan_mask.data(), nullptr, BOX_PLAN_PROBES, kind).n_pruned;
+  im->plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return prune_table(s, im, 1);
+}
+static int ref_plan(rtg_scene* s) { return lean_plan(s, &s->ref, s->h_lo, s->h_hi, BOX_PLAN_DEFAULT); }
+
+// The rebuilt program (rt_box_plan.h box_tree_rebuild), its images and its plan, once; s->tree.lo stays nullptr when the
+// program has no region to rebuild (production launches then stage the reference program whatever option box_tree says).
+static int tree_program(rtg_scene* s) {
+  if (s->tree_tried || !s->plannable) return RTG_OK;
+  s->tree_tried = true;
+  const size_t n = s->h_hi.size();
+  std::vector<Packet> lo(n), hi(n);
+  std::vector<uint32_t> origin(n);
+  const auto t0 = std::chrono::steady_clock::now();
+  s->n_regions = box_tree_rebuild(reinterpret_cast<const uint32_t (*)[4]>(s->h_lo.data()), reinterpret_cast<const uint32_t (*)[4]>(s->h_hi.data()), n,
+                                  reinterpret_cast<uint32_t (*)[4]>(lo.data()), reinterpret_cast<uint32_t (*)[4]>(hi.data()), origin.data());
+  s->tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (!s->n_regions) return RTG_OK;
+  int rc;
+  if ((rc = upload(&s->buffers[15], lo.data(), n * 16, &s->bytes)) || (rc = upload(&s->buffers[16], hi.data(), n * 16, &s->bytes))) return rc;
+  s->tree.slot = 18;
+  if ((rc = lean_images(s, &s->tree, lo, hi, 17)) || (rc = lean_plan(s, &s->tree, lo, hi, BOX_TREE_PLAN))) return rc;
+  if (!s->box_chains && (rc = prune_table(s, &s->tree, 0))) return rc;
+  s->tree.lo = (const uint4*)s->buffers[15], s->tree.hi = (const uint4*)s->buffers[16];
   return RTG_OK;
 }
 
@@ -648,37 +725,19 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
     for (const Packet& h : fs.hi2) s->n_box2 += (h.w[3] & 0xffu) == OP_BOX ? 1u : 0u;
   }
   if ((fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0) {  // lean program (BOX / SPHERE / END): layout of its LDS image (rt_pool.h)
-    std::vector<uint32_t> ops(fs.hi.size()), off(fs.hi.size());
-    for (size_t i = 0; i < fs.hi.size(); i++) ops[i] = fs.hi[i].w[3];
-    s->dev.lds_image_bytes = lds_image_offsets(ops.data(), ops.size(), off.data());
-    if ((rc = upload(&s->buffers[6], off.data(), off.size() * sizeof(uint32_t), &s->bytes))) {
+    s->ref.lo = s->dev.lo, s->ref.hi = s->dev.hi, s->ref.slot = 12;
+    if ((rc = lean_images(s, &s->ref, fs.lo, fs.hi, 6))) {
       rtg_scene_destroy(s);
       return rc;
     }
-    s->dev.lds_off = (const uint32_t*)s->buffers[6];
-    std::vector<uint8_t> follower(fs.hi.size());
-    s->n_followers = box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(fs.lo.data()), reinterpret_cast<const uint32_t (*)[4]>(fs.hi.data()), fs.hi.size(), follower.data());
-    if (s->n_followers) {  // the production image: every follower 0 bytes (the counting launches keep the full one)
-      s->chain_bytes = lds_image_offsets(ops.data(), ops.size(), off.data(), follower.data());
-      if ((rc = upload(&s->buffers[12], off.data(), off.size() * sizeof(uint32_t), &s->bytes))) {
+    s->dev.lds_off = s->ref.d_off, s->dev.lds_image_bytes = s->ref.bytes;
+    // plans and the rebuilt program: for the program production launches stage now; the other one's when option box_tree asks
+    s->plannable = s->dev.lds_image_bytes - LDS_BOX_BYTES * (s->n_box / 2u) <= 160u * 1024u;
+    if (s->plannable) {
+      s->h_lo = fs.lo, s->h_hi = fs.hi;
+      if ((s->box_tree && (rc = tree_program(s))) || (!s->tree.lo && (rc = ref_plan(s)))) {
         rtg_scene_destroy(s);
         return rc;
-      }
-      s->d_chain_off = (const uint32_t*)s->buffers[12];
-    }
-    // the pruned images (rt_box_plan.h): the plan's records 0 bytes, with and without the followers.  (Only staged images
-    // have pruned records: no plan for a program that cannot fit a CU's LDS even without its interior boxes.)
-    if (s->dev.lds_image_bytes - LDS_BOX_BYTES * (s->n_box / 2u) <= 160u * 1024u) {
-      s->plan_mask.resize(fs.hi.size());
-      const auto t0 = std::chrono::steady_clock::now();
-      s->n_pruned = box_plan(reinterpret_cast<const uint32_t (*)[4]>(fs.lo.data()), reinterpret_cast<const uint32_t (*)[4]>(fs.hi.data()), fs.hi.size(), follower.data(), s->plan_mask.data()).n_pruned;
-      s->plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      if (s->n_pruned) {
-        s->plan_ops = ops;
-        if ((rc = prune_table(s, 1))) {
-          rtg_scene_destroy(s);
-          return rc;
-        }
       }
     }
     std::vector<uint32_t> wide;
@@ -721,10 +780,19 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "box_chains") {                                 // 0: production launches stage the image with its box-chain followers (A/B switch)
     if (!value) {  // ... and, with box_prune on, without the pruned records only: that table is made now
       HIP_TRY(hipSetDevice(s->device));
-      int rc = prune_table(s, 0);
+      int rc = prune_table(s, &s->ref, 0);
+      if (!rc) rc = prune_table(s, &s->tree, 0);
       if (rc) return rc;
     }
     s->box_chains = value;
+  }
+  else if (k == "box_tree") {                                   // 0: production launches stage the reference program (A/B switch); what the other value needs is made now
+    if (value < 0 || value > 1) return fail(RTG_ERR_INVALID, "box_tree: 0 or 1");
+    HIP_TRY(hipSetDevice(s->device));
+    int rc = value ? tree_program(s) : ref_plan(s);
+    if (!rc && !s->box_chains) rc = prune_table(s, value ? &s->tree : &s->ref, 0);
+    if (rc) return rc;
+    s->box_tree = value;
   }
   else if (k == "box_prune") {                                  // 0: no interior box pruned; 1: production launches; 2: counting launches too (rtg_scene above)
     if (value < 0 || value > 2) return fail(RTG_ERR_INVALID, "box_prune: 0 .. 2");
@@ -784,7 +852,7 @@ int rtg_scene_info(const rtg_scene* s, uint32_t* n_instructions, uint32_t* n_mat
   if (n_materials) *n_materials = s->n_mat;
   if (n_textures) *n_textures = s->n_tex;
   if (hbm_bytes) *hbm_bytes = s->bytes;
-  if (n_box_followers) *n_box_followers = s->n_followers;
+  if (n_box_followers) *n_box_followers = s->ref.n_followers;
   return RTG_OK;
 }
 

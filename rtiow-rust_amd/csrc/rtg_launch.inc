@@ -219,12 +219,27 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   // production launches stage the image without box-chain followers (rt_pool.h box_chain_followers) and without the interior
   // boxes of the pruning plan (rt_box_plan.h); counting launches keep the full image, so that their counters and traces report
   // every test of the reference's walk (option box_prune = 2: they stage the pruned image too, and report the production walk's)
-  const bool chains = !COUNT && !wide && s->box_chains && s->d_chain_off != nullptr;
-  const bool prune = !wide && s->box_prune && (!COUNT || s->box_prune == 2) && s->d_prune_off[s->box_chains ? 1 : 0] != nullptr;
+  // Option box_tree: those launches walk the program whose Bvh regions are rebuilt over the same leaf order (rt_box_plan.h
+  // box_tree_rebuild) -- the same Sphere::hit calls in the same order, fewer box tests -- when the scene has one and its image
+  // can be staged; its images are chosen by the same two options.
+  const bool production = !COUNT || s->box_prune == 2;
   DevScene dev = s->dev;
+  bool chains = false, prune = false;
+  auto choose = [&](const LeanImages& im) {
+    chains = !COUNT && !wide && s->box_chains && im.d_chain_off != nullptr;
+    prune = !wide && s->box_prune && production && im.d_prune_off[s->box_chains ? 1 : 0] != nullptr;
+    dev.lo = im.lo, dev.hi = im.hi, dev.lds_off = im.d_off, dev.lds_image_bytes = im.bytes;
+    if (chains) dev.lds_off = im.d_chain_off, dev.lds_image_bytes = im.chain_bytes;
+    if (prune) dev.lds_off = im.d_prune_off[s->box_chains ? 1 : 0], dev.lds_image_bytes = im.prune_bytes[s->box_chains ? 1 : 0];
+  };
+  bool tree = s->box_tree && s->tree.lo != nullptr && production && !wide && s->ref.lo != nullptr;
+  if (tree) {
+    choose(s->tree);
+    if (pool_lds_bytes(dev.lds_image_bytes, s->n_mat, waves, true, false) > lds_limit) tree = false;  // (the global-memory walk keeps the reference program)
+  }
+  if (!tree && s->ref.lo != nullptr) choose(s->ref);
+  const LeanImages& im = tree ? s->tree : s->ref;
   if (wide) dev.lds_off = (const uint32_t*)s->buffers[7], dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
-  if (chains) dev.lds_off = s->d_chain_off, dev.lds_image_bytes = s->chain_bytes;
-  if (prune) dev.lds_off = s->d_prune_off[s->box_chains ? 1 : 0], dev.lds_image_bytes = s->prune_bytes[s->box_chains ? 1 : 0];
   const uint32_t image = dev.lds_image_bytes;
   bool use_lds = image != 0 && pool_lds_bytes(image, s->n_mat, waves, true, false) <= lds_limit;
   if (wide && !use_lds) return hipErrorNotSupported;  // (rtg_scene_set_option refuses bvh4 for images that do not fit)
@@ -241,9 +256,9 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
   if (s->verbose && (chains || prune) && use_lds)
-    fprintf(stderr, "[rtg] pool: box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
-            s->n_followers, s->box_chains ? " dropped" : " kept", s->n_pruned, prune ? " dropped" : " kept", s->plan_ms, image,
-            s->n_prog - (s->box_chains ? s->n_followers : 0u) - (prune ? s->n_pruned : 0u), s->n_prog, s->chain_bytes ? s->chain_bytes : s->dev.lds_image_bytes, s->dev.lds_image_bytes);
+    fprintf(stderr, "[rtg] pool: %s program (%u region(s) rebuilt in %.2f ms), box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
+            tree ? "rebuilt" : "reference", s->n_regions, s->tree_ms, im.n_followers, chains || (prune && s->box_chains) ? " dropped" : " kept", im.n_pruned, prune ? " dropped" : " kept", im.plan_ms, image,
+            s->n_prog - (chains || (prune && s->box_chains) ? im.n_followers : 0u) - (prune ? im.n_pruned : 0u), s->n_prog, im.chain_bytes ? im.chain_bytes : im.bytes, im.bytes);
   PoolLaunch L{KernelKind::lean_pool, bt, 0, lds, geo, POOL};
   hipError_t e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
   if (e != hipSuccess) return e;

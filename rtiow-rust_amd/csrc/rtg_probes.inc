@@ -184,20 +184,17 @@ int rtg_debug_flatten_pool2(rtg_builder* b, const rtg_id* world, size_t n, uint3
   return RTG_OK;
 }
 
-// Host-only (include/rtiow_gpu_debug.h): the box plan of a lean program -- per record 0 kept, 1 box-chain follower, 2 pruned
-// (rt_box_plan.h) -- by the function rtg_scene_create calls (which skips it for programs too large to be staged; this does not).  `words` (8 per record, as rtg_debug_flatten writes them) replaces the
-// flattened world when given.  Returns the record count, or a negative error code.
-int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records, uint8_t* mask_out,
-                       size_t capacity) {
-  std::vector<Packet> lo, hi;
-  bool lean = true;
+// The program the two entry points below inspect: `world` flattened by `b`, or the n_records x 8 `words` given.
+static int debug_lean_program(const char* who, rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
+                              std::vector<Packet>* lo, std::vector<Packet>* hi, bool* lean) {
+  *lean = true;
   if (words) {
-    lo.resize(n_records), hi.resize(n_records);
+    lo->resize(n_records), hi->resize(n_records);
     for (size_t i = 0; i < n_records; i++) {
-      std::memcpy(lo[i].w, words + 8 * i, 16), std::memcpy(hi[i].w, words + 8 * i + 4, 16);
-      const uint32_t op = hi[i].w[3] & 0xffu;
-      lean = lean && (op == OP_BOX || op == OP_SPHERE || op == OP_END) && !(hi[i].w[3] & F_MOVE);
-      if (op == OP_BOX && hi[i].w[2] >= n_records) return fail(RTG_ERR_INVALID, "rtg_debug_box_plan: a skip pointer leaves the program");
+      std::memcpy((*lo)[i].w, words + 8 * i, 16), std::memcpy((*hi)[i].w, words + 8 * i + 4, 16);
+      const uint32_t op = (*hi)[i].w[3] & 0xffu;
+      *lean = *lean && (op == OP_BOX || op == OP_SPHERE || op == OP_END) && !((*hi)[i].w[3] & F_MOVE);
+      if (op == OP_BOX && (*hi)[i].w[2] >= n_records) return fail(RTG_ERR_INVALID, std::string(who) + ": a skip pointer leaves the program");
     }
   } else {
     if (!b || (!world && n)) return fail(RTG_ERR_INVALID, "null argument");
@@ -207,10 +204,22 @@ int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint
     } catch (const BuildError& e) {
       return fail(e.code, e.msg);
     }
-    lean = (fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0;
-    lo.swap(fs.lo), hi.swap(fs.hi);
+    *lean = (fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0;
+    lo->swap(fs.lo), hi->swap(fs.hi);
   }
-  if (hi.size() > 0x7fffffffu) return fail(RTG_ERR_INVALID, "rtg_debug_box_plan: program too large");
+  if (hi->size() > 0x7fffffffu) return fail(RTG_ERR_INVALID, std::string(who) + ": program too large");
+  return RTG_OK;
+}
+
+// Host-only (include/rtiow_gpu_debug.h): the box plan of a lean program -- per record 0 kept, 1 box-chain follower, 2 pruned
+// (rt_box_plan.h) -- by the function rtg_scene_create calls (which skips it for programs too large to be staged; this does not).  `words` (8 per record, as rtg_debug_flatten writes them) replaces the
+// flattened world when given.  Returns the record count, or a negative error code.
+int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records, uint8_t* mask_out,
+                       size_t capacity) {
+  std::vector<Packet> lo, hi;
+  bool lean = true;
+  int rc = debug_lean_program("rtg_debug_box_plan", b, world, n, words, n_records, &lo, &hi, &lean);
+  if (rc) return rc;
   std::vector<uint8_t> follower(hi.size(), 0), mask(hi.size(), 0);
   if (lean && !hi.empty()) {
     box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), follower.data());
@@ -218,6 +227,33 @@ int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint
   }
   if (mask_out) std::memcpy(mask_out, mask.data(), std::min(mask.size(), capacity));
   return (int)hi.size();
+}
+
+// Host-only (include/rtiow_gpu_debug.h): the production program of a lean program (rt_box_plan.h box_tree_rebuild), which record
+// of the given program every record copies, and the plan over it -- by the functions rtg_scene_create calls.  Another program
+// comes back unchanged with origin[i] = i and a mask of zeros.  Returns the record count, or a negative error code.
+int rtg_debug_production_program(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
+                                 uint32_t* words_out, uint32_t* origin_out, uint8_t* mask_out, size_t capacity) {
+  std::vector<Packet> lo, hi;
+  bool lean = true;
+  int rc = debug_lean_program("rtg_debug_production_program", b, world, n, words, n_records, &lo, &hi, &lean);
+  if (rc) return rc;
+  const size_t m = hi.size();
+  std::vector<Packet> plo(lo), phi(hi);
+  std::vector<uint32_t> origin(m);
+  std::vector<uint8_t> follower(m, 0), mask(m, 0);
+  for (size_t i = 0; i < m; i++) origin[i] = (uint32_t)i;
+  if (lean && m) {
+    box_tree_rebuild(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), m,
+                     reinterpret_cast<uint32_t (*)[4]>(plo.data()), reinterpret_cast<uint32_t (*)[4]>(phi.data()), origin.data());
+    box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(plo.data()), reinterpret_cast<const uint32_t (*)[4]>(phi.data()), m, follower.data());
+    box_plan(reinterpret_cast<const uint32_t (*)[4]>(plo.data()), reinterpret_cast<const uint32_t (*)[4]>(phi.data()), m, follower.data(), mask.data(), nullptr, BOX_PLAN_PROBES, BOX_TREE_PLAN);
+  }
+  const size_t k = std::min(m, capacity);
+  for (size_t i = 0; words_out && i < k; i++) std::memcpy(words_out + 8 * i, plo[i].w, 16), std::memcpy(words_out + 8 * i + 4, phi[i].w, 16);
+  if (origin_out) std::memcpy(origin_out, origin.data(), k * sizeof(uint32_t));
+  if (mask_out) std::memcpy(mask_out, mask.data(), k);
+  return (int)m;
 }
 
 int rtg_debug_math(int device, int op, size_t n, const float* in, const float* in2, float* out) {
