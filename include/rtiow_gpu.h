@@ -272,6 +272,36 @@ typedef struct rtg_features {
   uint32_t reserved[8]; /* out: 0                                                                                       */
 } rtg_features;
 
+#define RTG_FLAG_DENOISE_ERROR 512u /* out ends with an error plane: the variance of every filtered pixel (below) */
+
+/* The error of the filtered frame.  RTG_FLAG_DENOISE_ERROR needs RTG_FLAG_DENOISE (else RTG_ERR_INVALID, nothing written or
+ * enqueued) and combines with everything that flag combines with.  It adds no block: `out` grows at its very end by an error
+ * plane of nx * ny * 3 floats (the pixel layout of plane 0), at the first even word (8-byte aligned) behind everything the
+ * call's other flags put in the frame -- behind the denoise output plane (the denoise block's word + 16 + 3 * nx * ny) or, with
+ * RTG_FLAG_FEATURES, behind the depth plane (the features block's word + 16 + 7 * nx * ny).  No other offset moves.  Compute it
+ * in 64 bits.
+ * For out_c = sum_q w_q m_q,c / sum_q w_q the variance of the output is ev_c = sum_q w_q^2 v_q,c / (sum_q w_q)^2 (the weights
+ * taken as given: the filter's bias is not in it, so the estimate runs low).  In the filter's loop above, for every valid pixel
+ * p and every displacement in raster order, once the pair's final weight w is known (the guided cap and the mask of valid pairs
+ * included):  acc2_c = acc2_c + (w * w) * v_{p+delta,c}, from +0;  after the loop  ev_c = (acc2_c / wsum) / wsum.  Float32,
+ * every operation rounded on its own, no contraction, denormals kept.  rtiow-rust_amd/denoise.py nlm_error / nlm_guided_error
+ * are this in numpy; the error plane equals their second result bit for bit.
+ *   - The error plane gets ev for every valid pixel, +inf (0x7f800000) in all three channels for every other pixel with e_p > 0
+ *     (a pass-through pixel: its error is unknown), and nothing for pixels with e_p == 0, which keep what the plane held.
+ *   - Everything in front of the error plane ends bit for bit as in the same call without the flag.
+ *   - With RTG_FLAG_RETIRE the call's order becomes render, filter, retire, divide (retiring changes no e_p, so the filter's
+ *     output is that of the other order), and the retire rule reads the error plane instead of (S, Q): q is OK when its three
+ *     ev_q,c are finite and (double)ev_q,c <= target_se * target_se (the float64 product, computed once; no square root, so ties
+ *     are exact).  The window, min_samples, pixels with n_q == 0 being ignored, n_p := k and the block's active / retired /
+ *     samples_held stay as above.  Two fields change meaning: estimated counts the owned pixels with n_p > 0 and three finite
+ *     ev; sum_se2 is the sum of ((double)ev_0 + ev_1) + ev_2 over them, in the same fixed order -- sqrt(sum_se2 / (3 estimated))
+ *     is the estimated RMSE of the FILTERED frame.  rtiow-rust_amd/noise.py retire_filtered is the rule in numpy.
+ *   - Without RTG_FLAG_RETIRE the flag only produces the plane.  Without the flag every call is as above, its order included.
+ *   - The refusals are those of the call's other flags.  rtg_par_cast and rtg_par_cast_multi (scene option "multi_planes": the
+ *     first device writes the plane, it never travels between ranks) treat the error plane as they treat the denoise output
+ *     plane: uploaded when that one is, so untouched pixels survive, and copied back.  rtg_debug_samples returns
+ *     RTG_ERR_INVALID. */
+
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */

@@ -31,6 +31,7 @@ FLAG_DENOISE = 128       # after the slice, filter the frame: the framebuffer en
 DENOISE_MAX_RADIUS = 8
 DENOISE_MAX_PATCH = 3
 FLAG_FEATURES = 256      # the framebuffer ends with a Features block and the first-hit albedo / normal / depth planes
+FLAG_DENOISE_ERROR = 512  # (needs FLAG_DENOISE) the framebuffer ends with the error plane: the variance of every filtered pixel
 FEATURES_MAX_GRID = 4
 
 
@@ -140,14 +141,18 @@ class FrameLayout:
     (csrc/rtg_api.hip) and the *_block_word functions (csrc/rt_multi_planes.h) state it.  The float planes (one, or two with
     squares) start at word 0; behind them, each only with its flag: the count plane (`counts`, n = nx * ny words), the Retire
     block (`retire`), the Denoise block (`denoise`) and its output plane (`denoised`, 3n), the Features block (`features`) and
-    the `albedo` (3n), `normal` (3n) and `depth` (n) planes.  A block is 16 words and starts on an even word.  retire implies
+    the `albedo` (3n), `normal` (3n) and `depth` (n) planes, and at the very end, on an even word, the `error` plane (3n;
+    RTG_FLAG_DENOISE_ERROR, needs denoise).  A block is 16 words and starts on an even word.  retire implies
     counts and squares, denoise implies squares (the library refuses a call without them).  The offset of a part the frame
     does not have is None; `words` is the frame's length.  Plain Python integers: exact for frames beyond 2^31 bytes."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=False, features=False):
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=False, features=False, error=False):
+        if error and not denoise:
+            raise ValueError("error=True needs denoise= (the filter writes the error plane)")
         n = self.n = nx * ny
         self.nx, self.ny, self.squares = nx, ny, bool(squares or retire or denoise)
         self.counts = self.retire = self.denoise = self.denoised = self.features = self.albedo = self.normal = self.depth = None
+        self.error = None
         w = (6 if self.squares else 3) * n
         if counts or retire:
             self.counts, w = w, w + n
@@ -163,6 +168,9 @@ class FrameLayout:
             self.albedo = self.features + 16
             self.normal, self.depth = self.albedo + 3 * n, self.albedo + 6 * n
             w = self.depth + n
+        if error:
+            self.error = (w + 1) & ~1
+            w = self.error + 3 * n
         self.words = w
 
 
@@ -181,9 +189,10 @@ def denoise_block_offset(nx, ny, counts=False, retire=False):
     return FrameLayout(nx, ny, True, counts, retire, True).denoise * 4
 
 
-def denoise_frame_bytes(nx, ny, counts=False, retire=False):
-    """Bytes of an RTG_FLAG_DENOISE frame: it ends with the 64-byte Denoise block and the output plane."""
-    return FrameLayout(nx, ny, True, counts, retire, True).words * 4
+def denoise_frame_bytes(nx, ny, counts=False, retire=False, error=False):
+    """Bytes of an RTG_FLAG_DENOISE frame: it ends with the 64-byte Denoise block and the output plane (error=True: and the
+    error plane)."""
+    return FrameLayout(nx, ny, True, counts, retire, True, error=error).words * 4
 
 
 def features_block_offset(nx, ny, squares=False, counts=False, retire=False, denoise=False):
@@ -191,9 +200,10 @@ def features_block_offset(nx, ny, squares=False, counts=False, retire=False, den
     return FrameLayout(nx, ny, squares, counts, retire, denoise, True).features * 4
 
 
-def features_frame_bytes(nx, ny, squares=False, counts=False, retire=False, denoise=False):
-    """Bytes of an RTG_FLAG_FEATURES frame: it ends with the 64-byte Features block and the albedo, normal and depth planes."""
-    return FrameLayout(nx, ny, squares, counts, retire, denoise, True).words * 4
+def features_frame_bytes(nx, ny, squares=False, counts=False, retire=False, denoise=False, error=False):
+    """Bytes of an RTG_FLAG_FEATURES frame: it ends with the 64-byte Features block and the albedo, normal and depth planes
+    (error=True: and the error plane)."""
+    return FrameLayout(nx, ny, squares, counts, retire, denoise, True, error).words * 4
 
 
 class Stats(C.Structure):
@@ -212,13 +222,14 @@ class Stats(C.Structure):
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
                 nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False,
-                denoise=False, features=False):
-    """`features`: RTG_FLAG_FEATURES, the features block and the albedo / normal / depth planes at the framebuffer's end.
+                denoise=False, features=False, error=False):
+    """`error`: RTG_FLAG_DENOISE_ERROR, the error plane at the framebuffer's very end (needs denoise).
+    `features`: RTG_FLAG_FEATURES, the features block and the albedo / normal / depth planes at the framebuffer's end.
     `partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
     RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
     the count plane at the framebuffer's end; `retire`: RTG_FLAG_RETIRE, the retire block behind it; `denoise`:
     RTG_FLAG_DENOISE, the denoise block and the output plane at the framebuffer's end."""
-    flags |= (FLAG_DENOISE if denoise else 0) | (FLAG_FEATURES if features else 0)
+    flags |= (FLAG_DENOISE if denoise else 0) | (FLAG_FEATURES if features else 0) | (FLAG_DENOISE_ERROR if error else 0)
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
     flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0)
     p = Params()
@@ -265,7 +276,7 @@ def _resumes(kw):
 
 
 _FLAG_OF = {"squares": ("squares=True", "SUM_SQUARES"), "counts": ("counts=", "SAMPLE_COUNTS"), "retire": ("retire=", "RETIRE"),
-            "denoise": ("denoise=", "DENOISE"), "features": ("features=", "FEATURES")}
+            "denoise": ("denoise=", "DENOISE"), "features": ("features=", "FEATURES"), "error": ("error=True", "DENOISE_ERROR")}
 
 
 def _supported(be, part):
@@ -279,11 +290,12 @@ def _supported(be, part):
 class Frame:
     """One contiguous, zeroed host framebuffer `buf`, laid out by FrameLayout (`layout`), and a view of every part: `planes`
     ([ny, nx, 3], or [2, ny, nx, 3] with squares), `counts` (uint32 [ny, nx]), `retire`, `denoise`, `features` (the blocks),
-    `denoised`, `albedo`, `normal` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]) -- None when the frame has no such
-    part.  denoise / features: a block, a dict or True (make_denoise / make_features), whose in-fields the block gets."""
+    `denoised`, `albedo`, `normal`, `error` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]) -- None when the frame has no
+    such part.  denoise / features: a block, a dict or True (make_denoise / make_features), whose in-fields the block gets.
+    error=True (needs denoise): the error plane of RTG_FLAG_DENOISE_ERROR at the frame's end."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
-        lay = self.layout = FrameLayout(nx, ny, squares, counts, retire, _given(denoise), _given(features))
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
+        lay = self.layout = FrameLayout(nx, ny, squares, counts, retire, _given(denoise), _given(features), bool(error))
         self.nx, self.ny, self.squares = nx, ny, lay.squares
         self.buf = np.zeros(lay.words, dtype=np.float32)
 
@@ -296,6 +308,7 @@ class Frame:
         self.counts = None if lay.counts is None else plane(lay.counts, ny, nx).view(np.uint32)
         self.denoised, self.albedo, self.normal = (plane(at, ny, nx, 3) for at in (lay.denoised, lay.albedo, lay.normal))
         self.depth = plane(lay.depth, ny, nx)
+        self.error = plane(lay.error, ny, nx, 3)
         self.retire, self.denoise, self.features = block(Retire, lay.retire), block(Denoise, lay.denoise), block(Features, lay.features)
         if self.denoise is not None:
             self.set_in(make_denoise(denoise))
@@ -303,9 +316,12 @@ class Frame:
             self.set_in(make_features(features))
 
     def flags(self):
-        """make_params keywords of the parts the frame has."""
-        return {"squares": self.squares, "counts": self.counts is not None, "retire": self.retire is not None,
-                "denoise": self.denoise is not None, "features": self.features is not None}
+        """make_params keywords of the parts the frame has ("error" only when the frame has an error plane)."""
+        on = {"squares": self.squares, "counts": self.counts is not None, "retire": self.retire is not None,
+              "denoise": self.denoise is not None, "features": self.features is not None}
+        if self.error is not None:
+            on["error"] = True
+        return on
 
     def set_in(self, block):
         """Write the in-fields of `block` (a Retire, Denoise or Features) to the frame's block of that class; the out-fields,
@@ -347,8 +363,8 @@ class DenoiseFrame(Frame):
     Retire block with retire=True (implies counts), then the Denoise block and the output plane.  par_cast(out=frame,
     denoise=...) renders in place."""
 
-    def __init__(self, nx, ny, counts=False, retire=False, denoise=None):
-        super().__init__(nx, ny, True, counts, retire, denoise if _given(denoise) else True)
+    def __init__(self, nx, ny, counts=False, retire=False, denoise=None, error=False):
+        super().__init__(nx, ny, True, counts, retire, denoise if _given(denoise) else True, None, error)
 
 
 class FeaturesFrame(Frame):
@@ -357,18 +373,20 @@ class FeaturesFrame(Frame):
     True; implies squares) -- then the Features block and the albedo, normal and depth planes.  par_cast(out=frame,
     features=True) renders in place."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
-        super().__init__(nx, ny, squares, counts, retire, denoise, features if _given(features) else True)
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
+        super().__init__(nx, ny, squares, counts, retire, denoise, features if _given(features) else True, error)
 
 
-def features_frame(nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None):
-    """A zeroed FeaturesFrame whose blocks hold the in-fields of `features` (make_features) and `denoise` (make_denoise)."""
-    return FeaturesFrame(nx, ny, squares, counts, retire, denoise, features)
+def features_frame(nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
+    """A zeroed FeaturesFrame whose blocks hold the in-fields of `features` (make_features) and `denoise` (make_denoise);
+    error=True: with the error plane."""
+    return FeaturesFrame(nx, ny, squares, counts, retire, denoise, features, error)
 
 
-def denoise_frame(nx, ny, counts=False, retire=False, denoise=None):
-    """A zeroed DenoiseFrame whose block holds the in-fields of `denoise` (make_denoise: the defaults when None)."""
-    return DenoiseFrame(nx, ny, counts, retire, denoise)
+def denoise_frame(nx, ny, counts=False, retire=False, denoise=None, error=False):
+    """A zeroed DenoiseFrame whose block holds the in-fields of `denoise` (make_denoise: the defaults when None); error=True:
+    with the error plane."""
+    return DenoiseFrame(nx, ny, counts, retire, denoise, error)
 
 
 def counts_frame(nx, ny, squares=False, retire=False):
@@ -415,14 +433,19 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
     forward (par_cast_multi): plain flags beside a plain array (counts=True, ...) go to the library as they are."""
     kw = dict(kw)
     squares = kw.pop("squares", None)
-    has_rt, has_dn, has_ft = _given(retire), _given(denoise), _given(features)
+    error = kw.pop("error", None)   # (RTG_FLAG_DENOISE_ERROR: True, or None / False)
+    has_rt, has_dn, has_ft, has_er = _given(retire), _given(denoise), _given(features), _given(error)
     in_place = isinstance(out, Frame)
     f = None
     plain = forward and not (in_place or isinstance(counts, np.ndarray) or isinstance(retire, Retire)
                              or isinstance(denoise, (dict, Denoise)) or isinstance(features, (dict, Features)))
     if plain:   # (the library's to answer)
         flags, parts = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features}, ()
+        if has_er:
+            flags["error"], parts = True, ("error",)
     else:
+        if has_er and not (has_dn or (in_place and out.denoise is not None)):
+            raise ValueError("error=True needs denoise= (the filter writes the error plane)")
         if has_dn and not squares and (exact or not in_place):
             raise ValueError("denoise= needs squares=True (the filter reads both planes)")
         blocks = [make(x) for x, make in ((denoise, make_denoise), (features, make_features)) if _given(x) and x is not True]
@@ -439,6 +462,8 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
             if ((squares is not None or exact) and bool(squares) != f.squares) or (
                     exact and (has_dn != (f.denoise is not None) or has_ft != (f.features is not None))):
                 raise ValueError("out= a %s: squares= / denoise= / features= must say what the frame holds" % name)
+            if (has_er and f.error is None) or (exact and not has_er and f.error is not None):
+                raise ValueError("out= a %s: error= must say whether the frame has an error plane" % name)
             if isinstance(retire, Retire):
                 blocks.append(retire)
             flags = f.flags()
@@ -450,7 +475,9 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
             if out is None and _resumes(kw):
                 raise ValueError("resume=True needs out= (the running sum to continue)")
             flags = {"squares": bool(squares), "counts": counts is not None, "retire": has_rt, "denoise": has_dn, "features": has_ft}
-        parts = [part for part, on in flags.items() if on]
+            if has_er:
+                flags["error"] = True
+        parts = sorted((part for part, on in flags.items() if on), key=lambda part: part != "error")   # (the newest flag first)
     for part in parts:
         supported(part)
     if in_place:
@@ -458,8 +485,8 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
             f.set_in(block)
         ret, buf = f, f.buf
     elif (has_dn or has_ft) and not plain:
-        f = (FeaturesFrame(nx, ny, squares, counts is not None, has_rt, denoise if has_dn else None, features) if has_ft else
-             DenoiseFrame(nx, ny, counts is not None, has_rt, denoise))
+        f = (FeaturesFrame(nx, ny, squares, counts is not None, has_rt, denoise if has_dn else None, features, has_er) if has_ft else
+             DenoiseFrame(nx, ny, counts is not None, has_rt, denoise, has_er))
         f.copy_in(None if out is None else _host_frame(out, nx, ny, squares, kw), counts, retire if has_rt else None)
         ret, buf = f, f.buf
     else:
@@ -473,21 +500,26 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
     return (ret, st.as_dict()) if stats else ret
 
 
-def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw):
+def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw,
+                   error=False):
     """The host-frame loop of Scene.adaptive and Backend.adaptive_multi: `cast(ns, **keywords)` is the par_cast of either
-    (camera and frame size bound); denoise / features: a checked Denoise / Features, or None."""
+    (camera and frame size bound); denoise / features: a checked Denoise / Features, or None; error: the frame has the error
+    plane of RTG_FLAG_DENOISE_ERROR and the rule is noise.retire_filtered on it."""
     if features is not None:
-        f = FeaturesFrame(nx, ny, True, True, False, denoise) if out is None else out
+        f = FeaturesFrame(nx, ny, True, True, False, denoise, None, error) if out is None else out
         what = "features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)"
     elif denoise is not None:
-        f = DenoiseFrame(nx, ny, True) if out is None else out
+        f = DenoiseFrame(nx, ny, True, error=error) if out is None else out
         what = "denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)"
     else:
         f = CountsFrame(nx, ny, True) if out is None else out
         what = "out= must be a CountsFrame(nx, ny, squares=True)"
     on = {"denoise": True if denoise is not None else None, "features": True if features is not None else None}
-    if not isinstance(f, Frame) or (f.nx, f.ny) != (nx, ny) or f.flags() != {
-            "squares": True, "counts": True, "retire": False, "denoise": denoise is not None, "features": features is not None}:
+    want = {"squares": True, "counts": True, "retire": False, "denoise": denoise is not None, "features": features is not None}
+    if error:
+        on["error"] = want["error"] = True
+        what += " with error=True"
+    if not isinstance(f, Frame) or (f.nx, f.ny) != (nx, ny) or f.flags() != want:
         raise ValueError(what)
     for block in (features, denoise):
         if block is not None:
@@ -507,8 +539,10 @@ def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out
             stats.append(st)
         done = end
         held = np.minimum(f.counts, done).astype(np.uint32)
-        se = noise.standard_error_counts(f.planes[0], f.planes[1], held)
-        if radius:
+        se = f.error.copy() if error else noise.standard_error_counts(f.planes[0], f.planes[1], held)
+        if error:   # (the library wrote the plane of every pixel that holds samples: the filter ran in the slice's call)
+            retire = noise.retire_filtered(active, done, se, f.counts, min_samples, target_se, radius=radius)
+        elif radius:
             retire = noise.retire(active, done, se, min_samples, target_se, radius=radius, present=f.counts > 0)
         else:
             retire = noise.retire(active, done, se, min_samples, target_se)
@@ -682,20 +716,25 @@ class Backend:
         return st
 
     def adaptive_multi(self, scenes, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
-                       stats=None, radius=0, denoise=None, features=None, **kw):
+                       stats=None, radius=0, denoise=None, features=None, filtered_error=False, **kw):
         """Scene.adaptive's host-frame loop over several handles (scene option "multi_planes" on one of them): every slice is
         one par_cast_multi call, the retire rule is noise.retire on the host, and the loop yields the same tuples --
-        (counts, preview, stderr), then the filtered frame with denoise=, then the FeaturesFrame with features=."""
+        (counts, preview, stderr), then the filtered frame with denoise=, then the FeaturesFrame with features=.
+        filtered_error=True (needs denoise=): as in Scene.adaptive -- the rule is noise.retire_filtered on the error plane."""
         if step < 1:
             raise ValueError("step must be >= 1")
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
+        if filtered_error:
+            _supported(self, "error")
         _supported(self, "squares")
         _supported(self, "counts")
+        if filtered_error and not _given(denoise):
+            raise ValueError("filtered_error=True needs denoise= (the filter writes the error plane)")
         features = make_features(features) if _given(features) else None
         denoise = make_denoise(denoise) if _given(denoise) else None
         yield from _adaptive_host(lambda n, **k: self.par_cast_multi(scenes, camera, nx, ny, n, **k), nx, ny, ns, step,
-                                  target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw)
+                                  target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error))
 
     def multi_reset(self, rccl_library=None):
         """rtg_multi_reset: drop the cached RCCL communicators, unload librccl, choose the library to load next (None =
@@ -958,6 +997,9 @@ class Scene:
         denoise= the filter is the guided one (denoise.nlm_guided) over the frame's feature planes.  out= a FeaturesFrame is
         rendered in place and returned (features=True / denoise=True: its blocks as they stand); anything else is copied into
         a new frame and written back as without features=.
+        error=True (RTG_FLAG_DENOISE_ERROR; needs denoise=): the frame the call returns also has the `error` view, the variance
+        of every filtered pixel (denoise.nlm_error / nlm_guided_error), +inf where a pixel was passed through; with retire= the
+        rule is noise.retire_filtered on that plane.  out= a frame made with error=True is rendered in place.
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
         def call(p, buf):
             st = Stats.new()
@@ -968,7 +1010,7 @@ class Scene:
                        stats if counters is None else counters, counts, retire, denoise, features, kw, exact=True)
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None, counts=None, retire=None, denoise=None, features=None):
+                        resume=None, squares=None, counts=None, retire=None, denoise=None, features=None, error=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
         With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
         counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
@@ -982,17 +1024,21 @@ class Scene:
         `d_out_ptr` then holds denoise_frame_bytes(nx, ny, counts, retire) for the flags the call ends up with.
         features= (RTG_FLAG_FEATURES): True, the flag alone (the caller has written the block's in-fields on the device); a
         Features, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
-        `d_out_ptr` then holds features_frame_bytes(nx, ny, squares, counts, retire, denoise) for the flags the call ends up with."""
-        over = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features}
+        `d_out_ptr` then holds features_frame_bytes(nx, ny, squares, counts, retire, denoise) for the flags the call ends up with.
+        error= (RTG_FLAG_DENOISE_ERROR; needs the denoise part): True, the flag -- `d_out_ptr` then ends with the error plane
+        (FrameLayout(..., error=True).words words in all)."""
+        over = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features, "error": error}
         bits = {"squares": FLAG_SUM_SQUARES, "counts": FLAG_SAMPLE_COUNTS, "retire": FLAG_RETIRE, "denoise": FLAG_DENOISE,
-                "features": FLAG_FEATURES}
+                "features": FLAG_FEATURES, "error": FLAG_DENOISE_ERROR}
         # the parts the call ends up with: those of `params` unless overridden (an array or a block turns its part on).
         # Every refusal first: a refused call has written nothing to the caller's frame
         has = {part: bool(params.flags & bits[part] if on is None else on if isinstance(on, (bool, int)) else True)
                for part, on in over.items()}
-        for part in ("features", "denoise", "squares", "counts", "retire"):
+        for part in ("error", "features", "denoise", "squares", "counts", "retire"):
             if has[part] if part == "squares" else _given(over[part]):
                 _supported(self.be, part)
+        if has["error"] and not has["denoise"]:
+            raise ValueError("error=True needs the denoise part (the filter writes the error plane)")
         lay = FrameLayout(params.nx, params.ny, **has)
         # blocks of the caller's: (block, byte offset, bytes written before the call); all of a block is read back after it
         blocks = [(over[part], 4 * at, n) for part, at, n in (("retire", lay.retire, C.sizeof(Retire)),
@@ -1051,7 +1097,8 @@ class Scene:
         return make(given)
 
     def adaptive(self, camera, nx, ny, ns, step, target_se, min_samples=16, budget_s=None, out=None, seed=0xDEADBEEF,
-                 stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, features=None, **kw):
+                 stats=None, radius=0, preview=None, stream=None, denoise=None, denoised=None, features=None,
+                 filtered_error=False, **kw):
         """Adaptive sampling (include/rtiow_gpu.h RTG_FLAG_SAMPLE_COUNTS).  Every slice renders `step` more samples of the
         pixels still active, with RTG_FLAG_SUM_SQUARES + RTG_FLAG_SAMPLE_COUNTS + RTG_FLAG_PARTIAL.  After the slice that ends
         at k samples, an active pixel retires when noise.retire says so (k >= min_samples and its largest per-channel standard
@@ -1078,13 +1125,23 @@ class Scene:
         item at the end of its tuple.  Host frames: `out`, when given, is a FeaturesFrame(nx, ny, counts=True, squares=True,
         denoise=...); the item is that frame (views `albedo`, `normal`, `depth`).  Device frames: `out` holds
         features_frame_bytes(nx, ny, True, True, True, denoise) and the item is the byte offset of the features block in it
-        (the planes start 64 bytes behind it)."""
+        (the planes start 64 bytes behind it).
+        filtered_error=True (needs denoise=; RTG_FLAG_DENOISE_ERROR): every slice's call also writes the error plane of the
+        filtered frame, and the retire rule is noise.retire_filtered on it -- a pixel retires once the estimated variance of
+        its FILTERED value (every one of its window) is <= target_se^2.  Host frames: `out`, when given, is a frame made with
+        error=True; the loop's third item is the error plane (float32 [ny, nx, 3]: variances, +inf where unknown) instead of
+        stderr.  Device frames: `out` ends with the error plane (FrameLayout(nx, ny, True, True, True, True, features,
+        True).words words); info's estimated / sum_se2 / est_rmse are those of the filtered frame."""
         if step < 1:
             raise ValueError("step must be >= 1")
+        if filtered_error:
+            _supported(self.be, "error")
         _supported(self.be, "squares")
         _supported(self.be, "counts")
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
             raise ValueError("radius must be in 0 .. %d" % RETIRE_MAX_RADIUS)
+        if filtered_error and not _given(denoise):
+            raise ValueError("filtered_error=True needs denoise= (the filter writes the error plane)")
         features, denoise = self._loop_block("features", features, make_features), self._loop_block("denoise", denoise, make_denoise)
         if out is not None and not isinstance(out, Frame):
             _supported(self.be, "retire")
@@ -1093,16 +1150,16 @@ class Scene:
             if denoise is not None and denoised is None:
                 raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
-                                             radius, preview, stream, kw, denoise, denoised, features)
+                                             radius, preview, stream, kw, denoise, denoised, features, bool(filtered_error))
             return
         yield from _adaptive_host(lambda n, **k: self.par_cast(camera, nx, ny, n, **k), nx, ny, ns, step, target_se,
-                                  min_samples, budget_s, out, seed, stats, radius, denoise, features, kw)
+                                  min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error))
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
-                         stream, kw, denoise=None, denoised=None, features=None):
+                         stream, kw, denoise=None, denoised=None, features=None, error=False):
         hip, hs, ok = _hip_runtime(), _stream(stream), _hip_ok
         d_out, d_pv = _device_ptr(out), _device_ptr(preview)
-        lay = FrameLayout(nx, ny, True, True, True, denoise is not None, features is not None)
+        lay = FrameLayout(nx, ny, True, True, True, denoise is not None, features is not None, error)
         plane, counts_at = lay.n, d_out + 4 * lay.counts
         # every pixel's target count is ns; the block's in-fields are written once (the library never writes them)
         ok(hip.hipMemsetD32Async(C.c_void_p(counts_at), ns - (1 << 32) if ns >= 1 << 31 else ns, plane, hs), "hipMemsetD32Async(counts)")
@@ -1120,7 +1177,7 @@ class Scene:
             end = min(ns, done + step)
             st = self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
                                                           squares=True, counts=True, retire=True, denoise=denoise is not None,
-                                                          features=features is not None, **kw), d_out, hs,
+                                                          features=features is not None, error=error, **kw), d_out, hs,
                                       want_stats=stats is not None)
             if features is not None and features.compute:
                 features.compute = 0

@@ -14,6 +14,10 @@
 // and depth planes into a second 32-byte record per pixel, and the filter's guided instantiations cap every colour weight by
 // the feature weight of the pair -- reading the neighbour's record through the caches (GUIDED = 1) or from an LDS copy of the
 // tile plus a halo of R (GUIDED = 2).  A pair whose colour weight is +0 skips the feature weight: min(wf, +0) is +0 for every wf.
+// With RTG_FLAG_DENOISE_ERROR the prepare and filter kernels are their ERR instantiations (denoise.py nlm_error / nlm_guided_error):
+// the filter also folds (w * w) * v_q per pair -- one more recB read, inside the staged halo -- and stores ev = (acc2 / wsum) / wsum
+// into the frame's error plane; prepare writes the +inf of the pass-through pixels there.  ERR = false compiles to the code
+// without the flag.
 #pragma once
 #include "rt_pool.h"
 
@@ -39,6 +43,7 @@ struct DenoiseBufs {
   float* outp;             // the output plane
   uint32_t* block;         // the caller's rtg_denoise, as 16 words
   uint32_t* blk_u32;       // per prepare block: filtered, passed
+  float* errp;             // RTG_FLAG_DENOISE_ERROR: the error plane (the ERR instantiations alone read this field)
 };
 
 // The guided filter's own arguments: the feature records ((a0, a1, a2, z) (n0, n1, n2, all seven finite ? word 1 : 0) per pixel)
@@ -57,6 +62,7 @@ static inline size_t denoise_lds_bytes(uint32_t radius, uint32_t patch, bool gui
 
 RT_DEV bool dn_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+template <bool ERR>
 __global__ __launch_bounds__(256) void denoise_prepare_kernel(uint32_t n_pix, DenoiseArgs a, DenoiseBufs b) {
   __shared__ uint32_t s_f[4], s_p[4];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -89,6 +95,10 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(uint32_t n_pix, De
     if (pass) {
       float* o = b.outp + 3ull * p;
       o[0] = m[0], o[1] = m[1], o[2] = m[2];
+      if (ERR) {  // a pass-through pixel: its error is unknown
+        float* ev = b.errp + 3ull * p;
+        ev[0] = ev[1] = ev[2] = __uint_as_float(0x7f800000u);
+      }
     }
   }
   const uint32_t n_f = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid));
@@ -131,7 +141,8 @@ RT_DEV float dn_feature_weight(float4 pA, float4 pB, float4 qA, float4 qB, float
 }
 
 // GUIDED: 0 = the colour-only filter; 1 / 2 = the guided filter, the neighbours' feature records read through the caches / from LDS
-template <int GUIDED>
+// ERR: also the variance of the output into the error plane
+template <int GUIDED, bool ERR>
 __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32_t ny, DenoiseArgs a, DenoiseBufs b, DenoiseGuide gd) {
   extern __shared__ float4 dn_lds[];
   const int R = (int)a.radius, F = (int)a.patch, H = R + F;
@@ -181,6 +192,7 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
   int at[2];
   bool ok[2];
   float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, wsum[2] = {0.f, 0.f};
+  float acc2[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // (ERR)
   for (int j = 0; j < 2; j++) {
     at[j] = (y0 + 8 * j + H) * WR + x + H;
     ok[j] = __float_as_uint(recA[at[j]].w) != 0u;  // valid (pixels outside the image are not)
@@ -271,6 +283,13 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
         acc[j][1] = acc[j][1] + w * qA.y;
         acc[j][2] = acc[j][2] + w * qA.z;
         wsum[j] = wsum[j] + w;
+        if (ERR && w > 0.f) {  // (w = +0 adds three +0 products)
+          const float4 qB = recB[at[j] + delta];
+          const float w2 = w * w;
+          acc2[j][0] = acc2[j][0] + w2 * qB.x;
+          acc2[j][1] = acc2[j][1] + w2 * qB.y;
+          acc2[j][2] = acc2[j][2] + w2 * qB.z;
+        }
       }
       // (the next displacement's pd stores follow this one's row folds by the second barrier; its row folds follow these reads
       // by its first barrier)
@@ -280,6 +299,10 @@ __global__ __launch_bounds__(256) void denoise_filter_kernel(uint32_t nx, uint32
     const size_t p = (size_t)(ty0 + y0 + 8 * j) * nx + (size_t)(tx0 + x);
     float* o = b.outp + 3ull * p;
     o[0] = acc[j][0] / wsum[j], o[1] = acc[j][1] / wsum[j], o[2] = acc[j][2] / wsum[j];
+    if (ERR) {
+      float* ev = b.errp + 3ull * p;
+      ev[0] = (acc2[j][0] / wsum[j]) / wsum[j], ev[1] = (acc2[j][1] / wsum[j]) / wsum[j], ev[2] = (acc2[j][2] / wsum[j]) / wsum[j];
+    }
   }
 }
 

@@ -35,6 +35,16 @@ inline uint64_t features_block_word(uint32_t nx, uint32_t ny, const Slice& sl) {
   return (end + 1u) & ~1ull;
 }
 
+// RTG_FLAG_DENOISE_ERROR (needs RTG_FLAG_DENOISE): the error plane's word offset in the framebuffer -- the first even word behind
+// the denoise output plane or, with RTG_FLAG_FEATURES, behind the depth plane: the frame's old end
+template <typename Slice>
+inline uint64_t error_plane_word(uint32_t nx, uint32_t ny, const Slice& sl) {
+  const uint64_t n = (uint64_t)nx * ny;
+  uint64_t end = denoise_block_word(nx, ny, sl.counts, sl.retire) + 16u + 3u * n;
+  if (sl.features) end = features_block_word(nx, ny, sl) + 16u + 7u * n;
+  return (end + 1u) & ~1ull;
+}
+
 // ---- what travels ------------------------------------------------------------------------------------------------------------
 // The planes a rank of a multi_planes call writes, as groups (first word of the plane in the frame, words per pixel): the sum
 // (3), under RTG_FLAG_SUM_SQUARES the squares (3), under RTG_FLAG_FEATURES with compute = 1 the albedo (3), the normal (3) and

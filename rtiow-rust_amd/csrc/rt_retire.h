@@ -8,6 +8,8 @@
 //   finish -- one workgroup sums the block partials in a fixed order into the caller's rtg_retire block.
 // Every reduction has a fixed order (wave butterflies, then the 4 waves of a block in order, then the blocks by a fixed
 // stride-and-tree), so sum_se2 has the same bits however the kernels are scheduled.  All stores are plain stores.
+// With RTG_FLAG_DENOISE_ERROR the mark kernel is retire_mark_error_kernel: the same bit plane and partials from the frame's error
+// plane (rt_denoise.h: the variance ev of every filtered pixel) instead of (S, Q); apply and finish are shared.
 #pragma once
 #include "rt_pool.h"
 
@@ -30,6 +32,7 @@ struct RetireBufs {
   uint32_t* blk_u32;     // per block: estimated, active, retired
   unsigned long long* blk_held;  // per block: the samples held (sum of e_p)
   double* blk_se2;       // per block: the sum of se^2 over its estimated pixels
+  const float* errp;     // RTG_FLAG_DENOISE_ERROR: the error plane (retire_mark_error_kernel alone reads this field)
 };
 
 // noise.standard_error_counts of one channel with e >= 2 samples, in its operation order (the build has -ffp-contract=off: no
@@ -70,6 +73,49 @@ __global__ __launch_bounds__(256) void retire_mark_kernel(DevParams P, PixMap pm
   }
   // A wave is one 8x8 block of a tile (work_to_pixel: tiles are multiples of 8, so lane = index in the block): byte j of the
   // ballot holds the OK bits of the block's row j, pixels x0 .. x0 + 7 with x0 a multiple of 8 -- byte x0 / 8 of that row.
+  const uint64_t m = __builtin_amdgcn_ballot_w64(ok);
+  if (in && (lane & 7u) == 0u) reinterpret_cast<uint8_t*>(b.okbits + (size_t)row * b.pitch)[x >> 3] = (uint8_t)(m >> (lane & 56u));
+  const uint32_t n_est = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(est));
+  for (int off = 32; off > 0; off >>= 1) {
+    held += __shfl_xor(held, off, 64);
+    se2 += __shfl_xor(se2, off, 64);
+  }
+  if (lane == 0u) s_est[wave] = n_est, s_held[wave] = held, s_se2[wave] = se2;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    b.blk_u32[3u * blockIdx.x] = s_est[0] + s_est[1] + s_est[2] + s_est[3];
+    b.blk_held[blockIdx.x] = s_held[0] + s_held[1] + s_held[2] + s_held[3];
+    b.blk_se2[blockIdx.x] = ((s_se2[0] + s_se2[1]) + s_se2[2]) + s_se2[3];
+  }
+}
+
+// RTG_FLAG_DENOISE_ERROR (noise.py retire_filtered): q is OK when its three ev are finite and (double)ev <= target2, the float64
+// product target_se * target_se the launcher computed once; estimated = the pixels with n > 0 and three finite ev, their
+// partial ((double)ev_0 + ev_1) + ev_2.  The filter of the same call wrote the plane of every pixel with n > 0.
+__global__ __launch_bounds__(256) void retire_mark_error_kernel(DevParams P, PixMap pm, RetireArgs a, RetireBufs b, double target2) {
+  __shared__ uint32_t s_est[4];
+  __shared__ unsigned long long s_held[4];
+  __shared__ double s_se2[4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  uint32_t x = 0, row = 0;
+  const bool in = work_to_pixel(P, pm, blockIdx.x * 256u + threadIdx.x, x, row);
+  bool ok = true, est = false;  // (outside the image: no veto -- the window is clipped anyway)
+  unsigned long long held = 0;
+  double se2 = 0.0;
+  if (in) {
+    const size_t p = (size_t)row * P.nx + x;
+    const uint32_t n = b.counts[p];
+    held = n < a.k ? n : a.k;
+    if (n != 0u) {
+      const float* ev = b.errp + 3ull * p;
+      const float e0 = ev[0], e1 = ev[1], e2 = ev[2];
+      est = (__float_as_uint(e0) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(e1) & 0x7f800000u) != 0x7f800000u &&
+            (__float_as_uint(e2) & 0x7f800000u) != 0x7f800000u;
+      ok = est && (double)e0 <= target2 && (double)e1 <= target2 && (double)e2 <= target2;
+      if (est) se2 = ((double)e0 + (double)e1) + (double)e2;
+    }
+  }
+  // (the bit plane and the partials as retire_mark_kernel writes them)
   const uint64_t m = __builtin_amdgcn_ballot_w64(ok);
   if (in && (lane & 7u) == 0u) reinterpret_cast<uint8_t*>(b.okbits + (size_t)row * b.pitch)[x >> 3] = (uint8_t)(m >> (lane & 56u));
   const uint32_t n_est = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(est));

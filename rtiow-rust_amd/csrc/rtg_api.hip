@@ -259,6 +259,7 @@ struct SampleSlice {
   bool denoise = false; // RTG_FLAG_DENOISE: the framebuffer ends with an rtg_denoise block and the output plane; the filter runs before the division
   bool features = false; // RTG_FLAG_FEATURES: the framebuffer ends with an rtg_features block and the albedo / normal / depth planes
   bool features_done = false;  // ... set by the launcher once the feature pass of the call is enqueued
+  bool error = false;   // RTG_FLAG_DENOISE_ERROR: the framebuffer ends with the error plane; the filter runs before the retire step, which reads it
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -270,6 +271,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_RETIRE) sl.retire = true;
   if (p->flags & RTG_FLAG_DENOISE) sl.denoise = true;
   if (p->flags & RTG_FLAG_FEATURES) sl.features = true;
+  if (p->flags & RTG_FLAG_DENOISE_ERROR) sl.error = true;
   return sl;
 }
 
@@ -893,6 +895,7 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   if ((p->flags & RTG_FLAG_RETIRE) && (~p->flags & (RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES)))
     return fail(RTG_ERR_INVALID, "RTG_FLAG_RETIRE needs RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES");
   if ((p->flags & RTG_FLAG_DENOISE) && !(p->flags & RTG_FLAG_SUM_SQUARES)) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE needs RTG_FLAG_SUM_SQUARES");
+  if ((p->flags & RTG_FLAG_DENOISE_ERROR) && !(p->flags & RTG_FLAG_DENOISE)) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE_ERROR needs RTG_FLAG_DENOISE");
   if ((p->flags & RTG_FLAG_DENOISE) && d.nranks > 1u) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE needs nranks = 1 (the neighbours live on other ranks)");
   *out = d;
   return RTG_OK;
@@ -1050,6 +1053,7 @@ struct FrameLayout {
   size_t block_bytes = 0, dblock_bytes = 0, fblock_bytes = 0;  // where the retire / denoise / features block starts (0: no such block)
   size_t plane_bytes = 0, fplanes_bytes = 0;                   // the denoise output plane; the three feature planes
   size_t in_bytes = 0;     // everything in front of the features block
+  size_t eplane_bytes = 0; // where the error plane starts (RTG_FLAG_DENOISE_ERROR; 0: no such plane): a plane_bytes at the frame's end
   size_t frame_bytes = 0;  // the whole frame
 };
 static FrameLayout frame_layout(uint32_t nx, uint32_t ny, const SampleSlice& sl) {
@@ -1063,6 +1067,7 @@ static FrameLayout frame_layout(uint32_t nx, uint32_t ny, const SampleSlice& sl)
   L.plane_bytes = n * 3 * sizeof(float), L.fplanes_bytes = n * 7 * sizeof(float);
   L.in_bytes = sl.denoise ? L.dblock_bytes + sizeof(rtg_denoise) + L.plane_bytes : sl.retire ? L.block_bytes + sizeof(rtg_retire) : L.bytes + L.count_bytes;
   L.frame_bytes = sl.features ? L.fblock_bytes + sizeof(rtg_features) + L.fplanes_bytes : L.in_bytes;
+  if (sl.error) L.eplane_bytes = error_plane_word(nx, ny, sl) * sizeof(float), L.frame_bytes = L.eplane_bytes + L.plane_bytes;
   return L;
 }
 static int check_blocks(const FrameLayout& L, const SampleSlice& sl, const float* out_rgb, uint32_t nranks, FrameBlocks* fb) {
@@ -1081,9 +1086,9 @@ static int check_blocks(const FrameLayout& L, const SampleSlice& sl, const float
   }
   return RTG_OK;
 }
-// Byte ranges [lo, hi) of a frame, at most four
+// Byte ranges [lo, hi) of a frame, at most six
 struct Extents {
-  struct { size_t lo, hi; } e[4];
+  struct { size_t lo, hi; } e[6];
   int n = 0;
   void add(size_t lo, size_t hi) {
     if (hi > lo) e[n].lo = lo, e[n].hi = hi, n++;
@@ -1093,11 +1098,12 @@ struct Extents {
 // left them.  A single rank overwrites every pixel -- unless it resumes a progressive frame, whose running sums are in the
 // frame, or renders per-pixel counts (pixels with n_p = 0 stay as they are).  Under RTG_FLAG_SAMPLE_COUNTS the count plane
 // travels with the float planes, under RTG_FLAG_RETIRE / RTG_FLAG_DENOISE their blocks (and the output plane: pixels with
-// e_p = 0 keep what it held).
+// e_p = 0 keep what it held); the error plane of RTG_FLAG_DENOISE_ERROR whenever the output plane travels.
 static Extents upload_extents(const FrameLayout& L, const SampleSlice& sl, bool other_ranks, uint32_t features_compute) {
   Extents x;
   if (other_ranks || sl.begin != 0u || sl.counts) x.add(0, L.in_bytes);
   else if (sl.denoise) x.add(L.dblock_bytes, L.dblock_bytes + sizeof(rtg_denoise));  // (the block alone: a whole frame without counts writes every pixel of every plane)
+  if (sl.error && (other_ranks || sl.begin != 0u || sl.counts)) x.add(L.eplane_bytes, L.eplane_bytes + L.plane_bytes);
   // the features block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other
   // ranks' pixels must come back as the caller left them
   if (sl.features) x.add(L.fblock_bytes, L.fblock_bytes + sizeof(rtg_features) + (other_ranks || (features_compute == 0u && sl.denoise) ? L.fplanes_bytes : 0));
@@ -1105,13 +1111,15 @@ static Extents upload_extents(const FrameLayout& L, const SampleSlice& sl, bool 
 }
 // ... and back afterwards: the float planes; under RTG_FLAG_RETIRE the count plane and the block's out-fields (active ..
 // samples_held); under RTG_FLAG_DENOISE the out-fields (filtered .. reserved) and the output plane behind them; under
-// RTG_FLAG_FEATURES the out-fields (traced .. reserved) and, when this call traced them, the planes behind them
+// RTG_FLAG_FEATURES the out-fields (traced .. reserved) and, when this call traced them, the planes behind them; under
+// RTG_FLAG_DENOISE_ERROR the error plane
 static Extents copy_back_extents(const FrameLayout& L, const SampleSlice& sl, uint32_t features_compute) {
   Extents x;
   x.add(0, sl.retire ? L.bytes + L.count_bytes : L.bytes);
   if (sl.retire) x.add(L.block_bytes + offsetof(rtg_retire, active), L.block_bytes + offsetof(rtg_retire, reserved2));
   if (sl.denoise) x.add(L.dblock_bytes + offsetof(rtg_denoise, filtered), L.in_bytes);
   if (sl.features) x.add(L.fblock_bytes + offsetof(rtg_features, traced), L.fblock_bytes + sizeof(rtg_features) + (features_compute ? L.fplanes_bytes : 0));
+  if (sl.error) x.add(L.eplane_bytes, L.eplane_bytes + L.plane_bytes);
   return x;
 }
 

@@ -562,7 +562,10 @@ static hipError_t launch_resolve_counts(const DevParams& d, float* d_out, hipStr
 // RTG_FLAG_RETIRE (include/rtiow_gpu.h): the retire step of a counts call over this rank's work items (rt_retire.h) -- mark the
 // OK bits and the estimate's partials, retire the candidates whose window is OK, sum the partials into the caller's block.
 // `r`: the block's in-fields, already validated.  A rank without work items (pix_work = 0) only writes the block's zeros.
-static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, uint64_t pix_work, const rtg_retire& r) {
+// `errp` (RTG_FLAG_DENOISE_ERROR, else nullptr): the error plane the filter of this call has written -- the rule reads it instead
+// of (S, Q).
+static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, uint64_t pix_work, const rtg_retire& r,
+                                const float* errp = nullptr) {
   const uint32_t n_blk = (uint32_t)(pix_work / 256u);
   const uint64_t plane = (uint64_t)d.nx * d.ny;
   RetireBufs b;
@@ -577,10 +580,12 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
   b.planes = d_out;
   b.counts = reinterpret_cast<uint32_t*>(d_out + 6ull * plane);
   b.block = reinterpret_cast<uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
+  b.errp = errp;
   const RetireArgs a{r.target_se, d.ns, r.min_samples, r.radius};
   if (n_blk != 0u) {
     const PixMap pm = make_pixmap(d);
-    hipLaunchKernelGGL(retire_mark_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b);
+    if (errp) hipLaunchKernelGGL(retire_mark_error_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b, r.target_se * r.target_se);
+    else hipLaunchKernelGGL(retire_mark_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b);
     hipLaunchKernelGGL(retire_apply_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, a, b);
   }
   hipLaunchKernelGGL(retire_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
@@ -593,6 +598,7 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
 // in-fields, already validated.
 // `guide` (RTG_FLAG_FEATURES in the same call, else nullptr): the features block's in-fields -- the filter is the guided one, over
 // the feature planes the frame holds now (the callers run the feature pass first).
+// RTG_FLAG_DENOISE_ERROR (sl.error): the ERR instantiations, which also write the frame's error plane.
 static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const rtg_denoise& in,
                                  const rtg_features* guide = nullptr) {
   const uint64_t n_pix = (uint64_t)d.nx * d.ny;
@@ -609,11 +615,13 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   b.blk_u32 = reinterpret_cast<uint32_t*>(b.rec + 2ull * n_pix);
   b.block = words + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
   b.outp = reinterpret_cast<float*>(b.block + 16);
+  b.errp = sl.error ? d_out + error_plane_word(d.nx, d.ny, sl) : nullptr;
   const DenoiseArgs a{in.k, in.radius, in.patch, d.ns};
   // the guided filter reads its neighbours' feature records through the caches, or (option guide_lds) from an LDS copy
   const int guided = !guide ? 0 : (s->guide_lds > 0 ? 2 : 1);
   void (*filter)(uint32_t, uint32_t, DenoiseArgs, DenoiseBufs, DenoiseGuide) =
-      guided == 0 ? denoise_filter_kernel<0> : (guided == 1 ? denoise_filter_kernel<1> : denoise_filter_kernel<2>);
+      sl.error ? (guided == 0 ? denoise_filter_kernel<0, true> : (guided == 1 ? denoise_filter_kernel<1, true> : denoise_filter_kernel<2, true>))
+               : (guided == 0 ? denoise_filter_kernel<0, false> : (guided == 1 ? denoise_filter_kernel<1, false> : denoise_filter_kernel<2, false>));
   const size_t lds = denoise_lds_bytes(in.radius, in.patch, guided == 2);
   int per_cu = 0;
   e = kernel_setup(s, (const void*)filter, (int)DN_THREADS, lds, &per_cu);  // (the raise of the dynamic-LDS limit)
@@ -627,7 +635,7 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
     gd = DenoiseGuide{frec, guide->sigma_normal, guide->sigma_albedo, guide->sigma_depth};
     hipLaunchKernelGGL(denoise_guide_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, albedo, albedo + 3ull * n_pix, albedo + 6ull * n_pix, frec);
   }
-  hipLaunchKernelGGL(denoise_prepare_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
+  hipLaunchKernelGGL(sl.error ? denoise_prepare_kernel<true> : denoise_prepare_kernel<false>, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
   hipLaunchKernelGGL(filter, dim3((uint32_t)tiles), dim3(DN_THREADS), lds, stream, d.nx, d.ny, a, b, gd);
   hipLaunchKernelGGL(denoise_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
   return hipGetLastError();
@@ -681,6 +689,7 @@ static hipError_t read_features_block(const DevParams& d, const float* d_out, hi
 // RTG_FLAG_RETIRE: the block's in-fields come back with that read-back (on their own when the call renders nothing); refused
 // ones end the call before it renders (s->cx->refusal), accepted ones run the retire step between the render and the division.
 // RTG_FLAG_DENOISE: its in-fields travel in the same read-back; the filter runs after the retire step, before the division.
+// RTG_FLAG_DENOISE_ERROR: the filter runs BEFORE the retire step, whose rule then reads the error plane it wrote.
 // RTG_FLAG_FEATURES: likewise its in-fields (a call that renders, retires and filters nothing syncs for them alone); the feature
 // pass runs first, before the render.
 template <bool COUNT>
@@ -765,12 +774,16 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     if (sl.features && (s->cx->refusal = features_refusal(fin, sl.denoise))) return hipSuccess;
     if (sl.features && (e = launch_features(s, cam, d, d_out, stream, sl, fin)) != hipSuccess) return e;
   }
-  if (sl.retire) {
+  if (sl.retire && !sl.error) {
     e = launch_retire(s, d, d_out, stream, pix_work, rin);
     if (e != hipSuccess) return e;
   }
   if (sl.denoise) {
     e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &fin : nullptr);
+    if (e != hipSuccess) return e;
+  }
+  if (sl.retire && sl.error) {
+    e = launch_retire(s, d, d_out, stream, pix_work, rin, d_out + error_plane_word(d.nx, d.ny, sl));
     if (e != hipSuccess) return e;
   }
   return sl.divide ? launch_resolve_counts(d, d_out, stream, ls.list.counts) : hipSuccess;

@@ -399,7 +399,7 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   const uint32_t compute = sl.features ? fb.features.compute : 0u;
   const PlaneSet ps = make_plane_set(params->nx, params->ny, sl, compute != 0u);
   rtg_params rp = *params;  // what the ranks render: the slice, never resolved
-  rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_FEATURES)) | RTG_FLAG_PARTIAL;
+  rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR | RTG_FLAG_FEATURES)) | RTG_FLAG_PARTIAL;
   const SampleSlice rsl = slice_of(&rp);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
   const DevCamera cam = to_dev(camera);
@@ -504,8 +504,11 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   if (!head->post0) HIP_TRY(hipEventCreate(&head->post0));
   if (!head->post1) HIP_TRY(hipEventCreate(&head->post1));
   HIP_TRY(hipEventRecord(head->post0, hs));
-  if (sl.retire) HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire));
+  // (RTG_FLAG_DENOISE_ERROR: the filter first, then the retire rule on the error plane it wrote -- as on one handle)
+  if (sl.retire && !sl.error) HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire));
   if (sl.denoise) HIP_TRY(launch_denoise(head, d1, head->d_frame, hs, sl, fb.denoise, sl.features ? &fb.features : nullptr));
+  if (sl.retire && sl.error)
+    HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire, head->d_frame + error_plane_word(d1.nx, d1.ny, sl)));
   if (sl.divide)
     HIP_TRY(sl.counts ? launch_resolve_counts(d1, head->d_frame, hs, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(head->d_frame) + L.bytes))
                       : launch_resolve(d1, head->d_frame, hs));
@@ -566,6 +569,7 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   if (params->struct_size != sizeof(rtg_params)) return fail(RTG_ERR_INVALID, "rtg_params.struct_size mismatch");
   if (params->nranks > 1u) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi shards by itself: params.rank / nranks must be 0 / 0|1");
   if (stats && stats->struct_size != sizeof(rtg_stats)) return fail(RTG_ERR_INVALID, "rtg_stats.struct_size mismatch");
+  if ((params->flags & RTG_FLAG_DENOISE_ERROR) && !(params->flags & RTG_FLAG_DENOISE)) return fail(RTG_ERR_INVALID, "RTG_FLAG_DENOISE_ERROR needs RTG_FLAG_DENOISE");
   if ((params->flags & RTG_FLAG_RESUME) && params->sample_begin > params->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   // the flagged frames need scene option multi_planes on a handle (include/rtiow_gpu.h, at rtg_par_cast_multi)
   bool planes = false;

@@ -232,6 +232,8 @@ struct CastOptions {
   // perlin.rs:24-29 tables (only needed when a perlin texture is used)
   const float* perlin_vecs = nullptr;
   const uint8_t *perm_x = nullptr, *perm_y = nullptr, *perm_z = nullptr;
+  // par_cast_denoised / par_cast_multi_denoised: also ask for the error plane (RTG_FLAG_DENOISE_ERROR)
+  bool denoise_error = false;
 };
 
 using SceneHandle = std::unique_ptr<rtg_scene, void (*)(rtg_scene*)>;
@@ -394,9 +396,11 @@ inline AdaptiveImage par_cast_adaptive(size_t nx, size_t ny, size_t ns, size_t s
 
 // Not in the reference: par_cast with RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE.  `image` is exactly what par_cast returns;
 // `denoised` is the frame filtered by the library's variance-driven non-local-means filter (strength k, search radius `radius`,
-// patch radius `patch`: see the header), `block` the denoise block with its out-fields.
+// patch radius `patch`: see the header), `block` the denoise block with its out-fields.  With CastOptions::denoise_error the
+// call sets RTG_FLAG_DENOISE_ERROR too and `error` is the variance of every filtered pixel (+inf where a pixel was passed
+// through); else `error` stays empty.
 struct DenoisedImage {
-  Image image, denoised;
+  Image image, denoised, error;
   rtg_denoise block{};
 };
 
@@ -404,17 +408,22 @@ struct DenoisedImage {
 template <typename Cast>
 inline DenoisedImage denoised_frame(size_t nx, size_t ny, size_t ns, float k, uint32_t radius, uint32_t patch, const CastOptions& opt, Cast&& cast) {
   const size_t n = nx * ny, block_word = (6 * n + 1) & ~size_t(1);  // two planes, padding to 8 bytes, the block, the output plane
-  std::vector<float> frame(block_word + sizeof(rtg_denoise) / sizeof(float) + 3 * n, 0.f);
+  const size_t error_word = (block_word + 16 + 3 * n + 1) & ~size_t(1);  // the error plane: the first even word behind the output plane
+  std::vector<float> frame(opt.denoise_error ? error_word + 3 * n : block_word + sizeof(rtg_denoise) / sizeof(float) + 3 * n, 0.f);
   rtg_denoise d{};
   d.k = k, d.radius = radius, d.patch = patch;
   std::memcpy(frame.data() + block_word, &d, sizeof(d));
   rtg_params p = cast_params(nx, ny, ns, opt);
-  p.flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE;
+  p.flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE | (opt.denoise_error ? RTG_FLAG_DENOISE_ERROR : 0u);
   cast(p, frame.data());
   DenoisedImage out;
   out.image.nx = out.denoised.nx = nx, out.image.ny = out.denoised.ny = ny;
   out.image.rgb.assign(frame.begin(), frame.begin() + 3 * n);
-  out.denoised.rgb.assign(frame.begin() + block_word + 16, frame.end());
+  out.denoised.rgb.assign(frame.begin() + block_word + 16, frame.begin() + block_word + 16 + 3 * n);
+  if (opt.denoise_error) {
+    out.error.nx = nx, out.error.ny = ny;
+    out.error.rgb.assign(frame.begin() + error_word, frame.end());
+  }
   std::memcpy(&out.block, frame.data() + block_word, sizeof(rtg_denoise));
   return out;
 }

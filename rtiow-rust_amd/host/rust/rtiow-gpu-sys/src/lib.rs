@@ -39,6 +39,8 @@ pub const RTG_DENOISE_MAX_PATCH: u32 = 3;
 /// The framebuffer ends with an `rtg_features` block and the first-hit albedo, normal and depth planes (see the header).
 pub const RTG_FLAG_FEATURES: u32 = 256;
 pub const RTG_FEATURES_MAX_GRID: u32 = 4;
+/// Needs `RTG_FLAG_DENOISE`: the framebuffer ends with the error plane, the variance of every filtered pixel (see the header).
+pub const RTG_FLAG_DENOISE_ERROR: u32 = 512;
 
 #[repr(C)]
 pub struct rtg_builder {

@@ -210,10 +210,12 @@ pub struct CastOptions {
     pub seed: u64,
     pub max_bounces: u32,
     pub t_near: f32,
+    /// `par_cast_denoised`: also ask for the error plane (`RTG_FLAG_DENOISE_ERROR`)
+    pub denoise_error: bool,
 }
 impl Default for CastOptions {
     fn default() -> Self {
-        CastOptions { seed: 0xDEAD_BEEF, max_bounces: 50, t_near: 0.001 }
+        CastOptions { seed: 0xDEAD_BEEF, max_bounces: 50, t_near: 0.001, denoise_error: false }
     }
 }
 fn params(nx: usize, ny: usize, ns: usize, o: &CastOptions) -> sys::rtg_params {
@@ -326,20 +328,25 @@ impl GpuScene {
     /// Not in the reference: par_cast with `RTG_FLAG_SUM_SQUARES | RTG_FLAG_DENOISE` (see the header): the image exactly as
     /// `par_cast` returns it, the frame filtered by the library's variance-driven non-local-means filter (strength `k`, search
     /// radius `radius`, patch radius `patch`), and the block with its out-fields.  (Uncompiled, like the rest of this crate.)
+    /// With `options.denoise_error` the call sets `RTG_FLAG_DENOISE_ERROR` too and the last item is the error plane as an image of
+    /// its own: the variance of every filtered pixel (+inf where a pixel was passed through); `None` without the option.
     pub fn par_cast_denoised(&mut self, nx: usize, ny: usize, ns: usize, k: f32, radius: u32, patch: u32, camera: &Camera,
-                             options: &CastOptions) -> Result<(Image, Image, sys::rtg_denoise)> {
+                             options: &CastOptions) -> Result<(Image, Image, sys::rtg_denoise, Option<Image>)> {
         let n = nx * ny;
         let block_word = (6 * n + 1) & !1; // two planes, padding to 8 bytes, the block, then the output plane
-        let mut frame = vec![0f32; block_word + 16 + 3 * n];
+        // (the error plane: on the first even word behind the output plane)
+        let error_word = (block_word + 16 + 3 * n + 1) & !1;
+        let mut frame = vec![0f32; if options.denoise_error { error_word + 3 * n } else { block_word + 16 + 3 * n }];
         let block = sys::rtg_denoise { k, radius, patch, ..Default::default() };
         unsafe { ptr::write_unaligned(frame.as_mut_ptr().add(block_word) as *mut sys::rtg_denoise, block) };
         let mut p = params(nx, ny, ns, options);
-        p.flags = sys::RTG_FLAG_SUM_SQUARES | sys::RTG_FLAG_DENOISE;
+        p.flags = sys::RTG_FLAG_SUM_SQUARES | sys::RTG_FLAG_DENOISE | if options.denoise_error { sys::RTG_FLAG_DENOISE_ERROR } else { 0 };
         check(unsafe { sys::rtg_par_cast(self.raw, &camera.0, &p, frame.as_mut_ptr(), ptr::null_mut()) })?;
         let block = unsafe { ptr::read_unaligned(frame.as_ptr().add(block_word) as *const sys::rtg_denoise) };
-        let denoised = frame[block_word + 16..].to_vec();
+        let denoised = frame[block_word + 16..block_word + 16 + 3 * n].to_vec();
+        let error = if options.denoise_error { Some(Image { nx, ny, rgb: frame[error_word..error_word + 3 * n].to_vec() }) } else { None };
         frame.truncate(3 * n);
-        Ok((Image { nx, ny, rgb: frame }, Image { nx, ny, rgb: denoised }, block))
+        Ok((Image { nx, ny, rgb: frame }, Image { nx, ny, rgb: denoised }, block, error))
     }
 
     /// Not in the reference: the same frame rendered `step` samples at a time (`RTG_FLAG_PARTIAL` / `RTG_FLAG_RESUME`).

@@ -10,7 +10,8 @@ of squares Q = sum c_i^2 (plane 1).  From (S, Q, n):
 and the frame's estimated RMS error against the converged image is sqrt(mean over pixels and channels of se^2).
 Everything is computed in float64.  With RTG_FLAG_SAMPLE_COUNTS every pixel has its own n (standard_error_counts), and
 adaptive sampling retires a pixel once its estimate -- or, with a radius, every estimate around it -- is good enough (retire;
-RTG_FLAG_RETIRE runs the same rule on the device).
+RTG_FLAG_RETIRE runs the same rule on the device).  retire_filtered is the rule on the error plane of a filtered frame
+(RTG_FLAG_DENOISE_ERROR).
 """
 import numpy as np
 
@@ -65,6 +66,33 @@ def retire(active, k, stderr, min_samples, target_se, radius=0, present=None):
     if radius:
         ok = window_all(ok, int(radius))
     return active & ok
+
+
+def retire_filtered(active, k, ev, counts, min_samples, target_se, radius=0):
+    """The retire rule of RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR, after the slice that ends at k samples:
+    `ev` (float32 [ny, nx, 3]) is the error plane the filter wrote (denoise.nlm_error), `counts` the count plane n.  A pixel
+    is OK when its three ev are finite and float64(ev) <= target_se * target_se (the float64 product; no square root); pixels
+    with n == 0 are not part of the frame and never veto a window.  Returns the bool mask of the active pixels with
+    k >= min_samples whose (2 radius + 1)^2 window, clipped to the image, is OK."""
+    active = np.asarray(active, dtype=bool)
+    if k < min_samples:
+        return np.zeros_like(active)
+    e = np.asarray(ev, dtype=np.float32)
+    target2 = float(target_se) * float(target_se)
+    ok = np.isfinite(e).all(axis=-1) & (e.astype(np.float64) <= target2).all(axis=-1)
+    ok |= np.asarray(counts) == 0
+    if radius:
+        ok = window_all(ok, int(radius))
+    return active & ok
+
+
+def filtered_estimate(ev, counts):
+    """(estimated, sum_se2) of the retire block under RTG_FLAG_DENOISE_ERROR: the pixels with n > 0 and three finite ev, and the
+    sum of (float64(ev_0) + ev_1) + ev_2 over them (here in numpy's order: the library's fixed order agrees to rounding);
+    sqrt(sum_se2 / (3 estimated)) is the estimated RMSE of the filtered frame."""
+    e = np.asarray(ev, dtype=np.float32).astype(np.float64)
+    est = np.isfinite(e).all(axis=-1) & (np.asarray(counts) > 0)
+    return int(est.sum()), float(((e[..., 0] + e[..., 1]) + e[..., 2])[est].sum())
 
 
 def window_all(ok, radius):
