@@ -137,8 +137,8 @@ def _given(x):
 
 
 class FrameLayout:
-    """Where every part of a framebuffer starts, in 4-byte words: the one rule of include/rtiow_gpu.h, as frame_layout
-    (csrc/rtg_api.hip) and the *_block_word functions (csrc/rt_multi_planes.h) state it.  The float planes (one, or two with
+    """Where every part of a framebuffer starts, in 4-byte words: the one rule of include/rtiow_gpu.h, field for field the
+    library's own struct FrameLayout (csrc/rt_multi_planes.h, host part).  The float planes (one, or two with
     squares) start at word 0; behind them, each only with its flag: the count plane (`counts`, n = nx * ny words), the Retire
     block (`retire`), the Denoise block (`denoise`) and its output plane (`denoised`, 3n), the Features block (`features`) and
     the `albedo` (3n), `normal` (3n) and `depth` (n) planes, and at the very end, on an even word, the `error` plane (3n;

@@ -91,13 +91,11 @@ struct LaunchCtx {
   unsigned long long counts_samples = 0;  // ... rtg_stats.samples of the last counts call
   void* d_retire = nullptr;     // RTG_FLAG_RETIRE: the OK bit plane and the retire kernels' per-block partials (rt_retire.h)
   size_t retire_bytes = 0;
-  const char* refusal = nullptr;  // ... set by launch_counts when the block's in-fields are refused (RTG_ERR_INVALID, nothing written)
+  const char* refusal = nullptr;  // ... set by launch_counts when a block's in-fields are refused (RTG_ERR_INVALID, nothing written)
   void* d_denoise = nullptr;    // RTG_FLAG_DENOISE: the per-pixel (m, v, valid) records and the prepare kernel's per-block counts (rt_denoise.h)
   size_t denoise_bytes = 0;
-  rtg_denoise denoise_in{};     // ... the block's in-fields of a call without a count plane, read back before its first kernel
   uint32_t* d_features = nullptr;  // RTG_FLAG_FEATURES: the feature kernel's per-block counts (rt_features.h)
   size_t features_bytes = 0;
-  rtg_features features_in{};   // ... the block's in-fields of a call without a count plane, read back before its first kernel
 };
 
 // The LDS images of ONE lean program (rt_pool.h): the full one, the one without box-chain followers and the ones without the
@@ -258,7 +256,6 @@ struct SampleSlice {
   bool retire = false;  // RTG_FLAG_RETIRE: the framebuffer ends with an rtg_retire block; the retire step runs before the division
   bool denoise = false; // RTG_FLAG_DENOISE: the framebuffer ends with an rtg_denoise block and the output plane; the filter runs before the division
   bool features = false; // RTG_FLAG_FEATURES: the framebuffer ends with an rtg_features block and the albedo / normal / depth planes
-  bool features_done = false;  // ... set by the launcher once the feature pass of the call is enqueued
   bool error = false;   // RTG_FLAG_DENOISE_ERROR: the framebuffer ends with the error plane; the filter runs before the retire step, which reads it
   bool sliced() const { return begin != 0u || !divide; }
 };
@@ -275,7 +272,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   return sl;
 }
 
-// The frame layout (retire_block_word, denoise_block_word, features_block_word) is rt_multi_planes.h's host part.
+// The frame layout (FrameLayout) is rt_multi_planes.h's host part.
 // RTG_FLAG_RETIRE: why the block's in-fields are refused (nullptr: accepted)
 static const char* retire_refusal(const rtg_retire& r, uint32_t nranks) {
   if (r.radius > RTG_RETIRE_MAX_RADIUS) return "RTG_FLAG_RETIRE: radius > RTG_RETIRE_MAX_RADIUS";
@@ -301,6 +298,30 @@ static const char* features_refusal(const rtg_features& r, bool denoise) {
   if (r.reserved_in != 0u) return "RTG_FLAG_FEATURES: reserved_in != 0";
   for (float sg : {r.sigma_normal, r.sigma_albedo, r.sigma_depth})
     if (denoise && (!(sg > 0.f) || !std::isfinite(sg))) return "RTG_FLAG_FEATURES with RTG_FLAG_DENOISE: a sigma is NaN, infinite or <= 0";
+  return nullptr;
+}
+
+// The in-fields of a flagged frame's blocks, in ONE place: read (from the host frame by check_blocks, from the device frame by
+// read_blocks), checked by blocks_refusal, then handed to the launchers as an argument.
+struct FrameBlocks {
+  rtg_retire retire{};
+  rtg_denoise denoise{};
+  rtg_features features{};
+};
+// Enqueue on `stream` the read-backs of the in-fields of the blocks the slice's flags name; the caller synchronises
+static hipError_t read_blocks(const FrameLayout& L, const SampleSlice& sl, const float* d_out, hipStream_t stream, FrameBlocks* fb) {
+  hipError_t e = hipSuccess;
+  if (sl.retire) e = hipMemcpyAsync(&fb->retire, d_out + L.retire, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && sl.denoise) e = hipMemcpyAsync(&fb->denoise, d_out + L.denoise, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && sl.features) e = hipMemcpyAsync(&fb->features, d_out + L.features, offsetof(rtg_features, traced), hipMemcpyDeviceToHost, stream);
+  return e;
+}
+// Why a call of `nranks` ranks refuses those in-fields (nullptr: accepted)
+static const char* blocks_refusal(const SampleSlice& sl, const FrameBlocks& fb, uint32_t nranks) {
+  const char* why = nullptr;
+  if (sl.retire && (why = retire_refusal(fb.retire, nranks))) return why;
+  if (sl.denoise && (why = denoise_refusal(fb.denoise, nranks))) return why;
+  if (sl.features && (why = features_refusal(fb.features, sl.denoise))) return why;
   return nullptr;
 }
 
@@ -963,6 +984,8 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   DevCamera cam = to_dev(camera);
   bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
   const SampleSlice sl = slice_of(params);
+  const FrameLayout L(d.nx, d.ny, params->flags);
+  FrameBlocks fb;
   // From here on work of this frame may sit on `stream`: a failure must not hand the context out again while kernels of the
   // partly enqueued frame still run (they read d_consts / d_lpt / the scratch the next call would rewrite) -- drain first.
 #define HIP_TRY_CTX(expr)                               \
@@ -976,16 +999,9 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
   if ((sl.denoise || sl.features) && !sl.counts) {
     // RTG_FLAG_DENOISE / RTG_FLAG_FEATURES without a count plane: the blocks' in-fields come back now, in one copy-and-wait, before
     // anything of the frame is enqueued and outside the timed span (a counts call reads them with its compaction result: launch_counts)
-    if (sl.denoise) {
-      const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, false, false);
-      HIP_TRY(hipMemcpyAsync(&s->cx->denoise_in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream));
-    }
-    if (sl.features) HIP_TRY(read_features_block(d, d_out, stream, sl, &s->cx->features_in));
+    HIP_TRY(read_blocks(L, sl, d_out, stream, &fb));
     HIP_TRY(hipStreamSynchronize(stream));
-    if (sl.denoise)
-      if (const char* why = denoise_refusal(s->cx->denoise_in, d.nranks)) return fail(RTG_ERR_INVALID, why);
-    if (sl.features)
-      if (const char* why = features_refusal(s->cx->features_in, sl.denoise)) return fail(RTG_ERR_INVALID, why);
+    if (const char* why = blocks_refusal(sl, fb, d.nranks)) return fail(RTG_ERR_INVALID, why);
   }
   if (count) {
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), stream));
@@ -1005,7 +1021,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
 #endif
   if (stats) HIP_TRY_CTX(hipEventRecord(s->cx->ev0, stream));
   s->cx->refusal = nullptr;
-  HIP_TRY_CTX(count ? launch_render<true>(s, cam, d, d_out, stream, sl) : launch_render<false>(s, cam, d, d_out, stream, sl));
+  HIP_TRY_CTX(count ? launch_render<true>(s, cam, d, d_out, stream, sl, L, fb) : launch_render<false>(s, cam, d, d_out, stream, sl, L, fb));
   if ((rc = ctx_release(s, stream))) {
     (void)hipStreamSynchronize(stream);
     return rc;
@@ -1040,87 +1056,13 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
 
 // ---- what rtg_par_cast does around rtg_par_cast_device, shared with rtg_par_cast_multi's flagged frames (rtg_multi.inc) ------
 // The host copies of a flagged frame's blocks, checked: the refusals of include/rtiow_gpu.h for a call of `nranks` ranks, made
-// before anything is uploaded or enqueued.
-struct FrameBlocks {
-  rtg_retire retire{};
-  rtg_denoise denoise{};
-  rtg_features features{};
-};
-// Byte offsets and sizes of the parts of a host frame (rt_multi_planes.h: the layout)
-struct FrameLayout {
-  size_t bytes = 0;        // the float planes: one, or two under RTG_FLAG_SUM_SQUARES
-  size_t count_bytes = 0;  // the count plane behind them (RTG_FLAG_SAMPLE_COUNTS)
-  size_t block_bytes = 0, dblock_bytes = 0, fblock_bytes = 0;  // where the retire / denoise / features block starts (0: no such block)
-  size_t plane_bytes = 0, fplanes_bytes = 0;                   // the denoise output plane; the three feature planes
-  size_t in_bytes = 0;     // everything in front of the features block
-  size_t eplane_bytes = 0; // where the error plane starts (RTG_FLAG_DENOISE_ERROR; 0: no such plane): a plane_bytes at the frame's end
-  size_t frame_bytes = 0;  // the whole frame
-};
-static FrameLayout frame_layout(uint32_t nx, uint32_t ny, const SampleSlice& sl) {
-  FrameLayout L;
-  const size_t n = (size_t)nx * ny;
-  L.bytes = n * 3 * sizeof(float) * (sl.squares ? 2 : 1);
-  L.count_bytes = sl.counts ? n * sizeof(uint32_t) : 0;
-  L.block_bytes = sl.retire ? retire_block_word(nx, ny) * sizeof(float) : 0;
-  L.dblock_bytes = sl.denoise ? denoise_block_word(nx, ny, sl.counts, sl.retire) * sizeof(float) : 0;
-  L.fblock_bytes = sl.features ? features_block_word(nx, ny, sl) * sizeof(float) : 0;
-  L.plane_bytes = n * 3 * sizeof(float), L.fplanes_bytes = n * 7 * sizeof(float);
-  L.in_bytes = sl.denoise ? L.dblock_bytes + sizeof(rtg_denoise) + L.plane_bytes : sl.retire ? L.block_bytes + sizeof(rtg_retire) : L.bytes + L.count_bytes;
-  L.frame_bytes = sl.features ? L.fblock_bytes + sizeof(rtg_features) + L.fplanes_bytes : L.in_bytes;
-  if (sl.error) L.eplane_bytes = error_plane_word(nx, ny, sl) * sizeof(float), L.frame_bytes = L.eplane_bytes + L.plane_bytes;
-  return L;
-}
+// before anything is uploaded or enqueued.  (The upload and copy-back extents are rt_multi_planes.h's host part.)
 static int check_blocks(const FrameLayout& L, const SampleSlice& sl, const float* out_rgb, uint32_t nranks, FrameBlocks* fb) {
-  const char* base = reinterpret_cast<const char*>(out_rgb);
-  if (sl.retire) {
-    memcpy(&fb->retire, base + L.block_bytes, sizeof(rtg_retire));
-    if (const char* why = retire_refusal(fb->retire, nranks)) return fail(RTG_ERR_INVALID, why);
-  }
-  if (sl.denoise) {
-    memcpy(&fb->denoise, base + L.dblock_bytes, sizeof(rtg_denoise));
-    if (const char* why = denoise_refusal(fb->denoise, nranks)) return fail(RTG_ERR_INVALID, why);
-  }
-  if (sl.features) {
-    memcpy(&fb->features, base + L.fblock_bytes, sizeof(rtg_features));
-    if (const char* why = features_refusal(fb->features, sl.denoise)) return fail(RTG_ERR_INVALID, why);
-  }
+  if (sl.retire) memcpy(&fb->retire, out_rgb + L.retire, sizeof(rtg_retire));
+  if (sl.denoise) memcpy(&fb->denoise, out_rgb + L.denoise, sizeof(rtg_denoise));
+  if (sl.features) memcpy(&fb->features, out_rgb + L.features, sizeof(rtg_features));
+  if (const char* why = blocks_refusal(sl, *fb, nranks)) return fail(RTG_ERR_INVALID, why);
   return RTG_OK;
-}
-// Byte ranges [lo, hi) of a frame, at most six
-struct Extents {
-  struct { size_t lo, hi; } e[6];
-  int n = 0;
-  void add(size_t lo, size_t hi) {
-    if (hi > lo) e[n].lo = lo, e[n].hi = hi, n++;
-  }
-};
-// What travels to the device before the call.  `other_ranks` (nranks > 1): pixels of other ranks must come back as the caller
-// left them.  A single rank overwrites every pixel -- unless it resumes a progressive frame, whose running sums are in the
-// frame, or renders per-pixel counts (pixels with n_p = 0 stay as they are).  Under RTG_FLAG_SAMPLE_COUNTS the count plane
-// travels with the float planes, under RTG_FLAG_RETIRE / RTG_FLAG_DENOISE their blocks (and the output plane: pixels with
-// e_p = 0 keep what it held); the error plane of RTG_FLAG_DENOISE_ERROR whenever the output plane travels.
-static Extents upload_extents(const FrameLayout& L, const SampleSlice& sl, bool other_ranks, uint32_t features_compute) {
-  Extents x;
-  if (other_ranks || sl.begin != 0u || sl.counts) x.add(0, L.in_bytes);
-  else if (sl.denoise) x.add(L.dblock_bytes, L.dblock_bytes + sizeof(rtg_denoise));  // (the block alone: a whole frame without counts writes every pixel of every plane)
-  if (sl.error && (other_ranks || sl.begin != 0u || sl.counts)) x.add(L.eplane_bytes, L.eplane_bytes + L.plane_bytes);
-  // the features block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other
-  // ranks' pixels must come back as the caller left them
-  if (sl.features) x.add(L.fblock_bytes, L.fblock_bytes + sizeof(rtg_features) + (other_ranks || (features_compute == 0u && sl.denoise) ? L.fplanes_bytes : 0));
-  return x;
-}
-// ... and back afterwards: the float planes; under RTG_FLAG_RETIRE the count plane and the block's out-fields (active ..
-// samples_held); under RTG_FLAG_DENOISE the out-fields (filtered .. reserved) and the output plane behind them; under
-// RTG_FLAG_FEATURES the out-fields (traced .. reserved) and, when this call traced them, the planes behind them; under
-// RTG_FLAG_DENOISE_ERROR the error plane
-static Extents copy_back_extents(const FrameLayout& L, const SampleSlice& sl, uint32_t features_compute) {
-  Extents x;
-  x.add(0, sl.retire ? L.bytes + L.count_bytes : L.bytes);
-  if (sl.retire) x.add(L.block_bytes + offsetof(rtg_retire, active), L.block_bytes + offsetof(rtg_retire, reserved2));
-  if (sl.denoise) x.add(L.dblock_bytes + offsetof(rtg_denoise, filtered), L.in_bytes);
-  if (sl.features) x.add(L.fblock_bytes + offsetof(rtg_features, traced), L.fblock_bytes + sizeof(rtg_features) + (features_compute ? L.fplanes_bytes : 0));
-  if (sl.error) x.add(L.eplane_bytes, L.eplane_bytes + L.plane_bytes);
-  return x;
 }
 
 int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* params, float* out_rgb, rtg_stats* stats) {
@@ -1131,23 +1073,23 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
     if (rc0) return rc0;
   }
   const SampleSlice sl = slice_of(params);
-  const FrameLayout L = frame_layout(params->nx, params->ny, sl);
+  const FrameLayout L(params->nx, params->ny, params->flags);
   // the blocks' in-fields are checked here, before anything is uploaded
   FrameBlocks fb;
   if (int rc0 = check_blocks(L, sl, out_rgb, params->nranks ? params->nranks : 1u, &fb)) return rc0;
   HIP_TRY(hipSetDevice(s->device));
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
-  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.frame_bytes ? L.frame_bytes : 16);
+  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.words ? L.words * sizeof(float) : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
   float* d_out = s->d_frame;
   char* dev = reinterpret_cast<char*>(d_out);
   char* host = reinterpret_cast<char*>(out_rgb);
-  const Extents up = upload_extents(L, sl, params->nranks > 1, fb.features.compute);
+  const Extents up = upload_extents(L, params->nranks > 1, sl.begin, fb.features.compute);
   for (int i = 0; i < up.n && e == hipSuccess; i++) e = hipMemcpy(dev + up.e[i].lo, host + up.e[i].lo, up.e[i].hi - up.e[i].lo, hipMemcpyHostToDevice);
   int rc = (e == hipSuccess) ? rtg_par_cast_device(s, camera, params, d_out, nullptr, stats) : hip_fail(e, "hipMemcpy");
   if (rc == RTG_OK) {
     e = hipDeviceSynchronize();
-    const Extents back = copy_back_extents(L, sl, fb.features.compute);
+    const Extents back = copy_back_extents(L, fb.features.compute);
     for (int i = 0; i < back.n && e == hipSuccess; i++) e = hipMemcpy(host + back.e[i].lo, dev + back.e[i].lo, back.e[i].hi - back.e[i].lo, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = hip_fail(e, "render / copy back");
   }

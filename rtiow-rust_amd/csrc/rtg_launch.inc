@@ -55,6 +55,38 @@ static hipError_t grow(void** buf, size_t* have, size_t need) {
   return e;
 }
 
+// ---- one pick per kernel family ------------------------------------------------------------------------------------------------
+// The baseline walk's FEAT template argument for a scene (rt_trace.h), handed to `f` as a std::integral_constant: FEAT_DEEP graphs
+// take the general walk, lean programs the lean one, every other scene the full one.  SIZED (render_kernel alone): the general
+// walk instantiated for the graph's real depths (flat_scene.h FEAT_DEEP_FEW_WRAPPERS / FEAT_DEEP_ONE_LEVEL, option deep_sized);
+// every other kernel keeps its largest instantiation: the same arithmetic.
+template <bool SIZED, typename F>
+static void with_feat(const rtg_scene* s, F&& f) {
+  constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+  if (s->features & FEAT_DEEP) {
+    if constexpr (SIZED) {
+      const bool few = s->deep_sized && (s->features & FEAT_DEEP_FEW_WRAPPERS) != 0, one = s->deep_sized && (s->features & FEAT_DEEP_ONE_LEVEL) != 0;
+      if (few && one) return f(std::integral_constant<uint32_t, D | FEAT_DEEP_FEW_WRAPPERS | FEAT_DEEP_ONE_LEVEL>{});
+      if (few) return f(std::integral_constant<uint32_t, D | FEAT_DEEP_FEW_WRAPPERS>{});
+      if (one) return f(std::integral_constant<uint32_t, D | FEAT_DEEP_ONE_LEVEL>{});
+    }
+    return f(std::integral_constant<uint32_t, D>{});
+  }
+  if ((s->features & (FEAT_ALL | FEAT_BOUNDARY)) == 0) return f(std::integral_constant<uint32_t, 0u>{});
+  return f(std::integral_constant<uint32_t, FEAT_ALL>{});
+}
+// Runtime bools as template arguments: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).  For kernel families of which
+// every combination is instantiated.
+template <typename F>
+static void with_bools(F&& f) {
+  f();
+}
+template <typename F, typename... Rest>
+static void with_bools(F&& f, bool b, Rest... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity);
 static void launch_pass_setup(rtg_scene* s, const LaunchConsts& c, uint32_t* queue, hipStream_t stream);
 
@@ -248,6 +280,8 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   size_t lds = pool_lds_bytes(image, s->n_mat, waves, use_lds, ray_lds);
   if (s->verbose && s->ray_lds && !ray_lds && use_lds && image >= (1u << 17) && pool_lds_bytes(image, s->n_mat, waves, use_lds, true) <= lds_limit)
     fprintf(stderr, "[rtg] pool: the LDS image is %u B (>= 128 KB): the slots' hot fields stay in global memory although they would fit LDS (their 16-bit best_pc holds image offsets / 8 < 2^14)\n", image);
+  // A table, not with_bools: only 10 of the 16 (STAGED, RAY_LDS, WIDE, LIST) combinations exist -- the 4-wide walk has neither a
+  // LIST nor an unstaged variant.
   void (*kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, uint32_t*);
   if (sl.counts) {
     if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true, false, true> : render_lean_pool<false, COUNT, true, false, true>;
@@ -435,21 +469,14 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   void (*kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, uint32_t*, float*,
                  uint32_t);
   const bool genb = (s->features & FEAT_BOUNDARY) != 0;  // a medium bounded by an object graph: the nested-walk variant
-  if (sl.counts && genb) {
-    if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, true, true> : render_full_pool<0, false, COUNT, true, true>;
-    else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, true, true> : render_full_pool<1, false, COUNT, true, true>;
-    else kernel = tex ? render_full_pool<2, true, COUNT, true, true> : render_full_pool<2, false, COUNT, true, true>;
-  } else if (sl.counts) {
-    if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, false, true> : render_full_pool<0, false, COUNT, false, true>;
-    else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, false, true> : render_full_pool<1, false, COUNT, false, true>;
-    else kernel = tex ? render_full_pool<2, true, COUNT, false, true> : render_full_pool<2, false, COUNT, false, true>;
-  } else if (genb) {
-    if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT, true> : render_full_pool<0, false, COUNT, true>;
-    else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT, true> : render_full_pool<1, false, COUNT, true>;
-    else kernel = tex ? render_full_pool<2, true, COUNT, true> : render_full_pool<2, false, COUNT, true>;
-  } else if (prog == 0) kernel = tex ? render_full_pool<0, true, COUNT> : render_full_pool<0, false, COUNT>;
-  else if (prog == 1) kernel = tex ? render_full_pool<1, true, COUNT> : render_full_pool<1, false, COUNT>;
-  else kernel = tex ? render_full_pool<2, true, COUNT> : render_full_pool<2, false, COUNT>;
+  void (*sync_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
+  void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
+  with_bools([&](auto tex_c, auto genb_c, auto list_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
+    constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value;
+    kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, LI> : (prog == 1 ? render_full_pool<1, T, COUNT, G, LI> : render_full_pool<2, T, COUNT, G, LI>);
+    sync_kernel = render_full_sync<1, T, COUNT, G, LI>;
+    pool2_kernel = render_full_pool2<T, COUNT, LI>;
+  }, tex, genb, sl.counts);
   // The lock-step kernel (rt_sync_full.h: one path per lane, no stacks, no pools) renders list worlds without a Bvh -- and, by
   // default (option sync = -1), programs whose Bvhs are tiny (<= 32 BOX records: the Criterion scene of benches/scene.rs has 15,
   // volume_test under bvh::from_scene 5; a box loop has nothing to batch there) and frames with fewer work items than the chip has
@@ -475,14 +502,8 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   consts.parent = s->d_parent;
   e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
   if (e != hipSuccess) return e;
-  void (*sync_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
-  void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
   if (lock_step) {
     L.kind = KernelKind::lock_step;
-    if (sl.counts && genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true, true> : render_full_sync<1, false, COUNT, true, true>;
-    else if (sl.counts) sync_kernel = tex ? render_full_sync<1, true, COUNT, false, true> : render_full_sync<1, false, COUNT, false, true>;
-    else if (genb) sync_kernel = tex ? render_full_sync<1, true, COUNT, true> : render_full_sync<1, false, COUNT, true>;
-    else sync_kernel = tex ? render_full_sync<1, true, COUNT, false> : render_full_sync<1, false, COUNT, false>;
     L.lds = (size_t)window * 32;
     // the lock-step kernel keeps ONE path per lane (64 per wave, not the pool kernel's FPOOL): its grid comes from that, and
     // the cap from ITS occupancy -- with the pool kernel's figures a frame of 0.3 .. 0.9 M work items left CUs idle
@@ -491,8 +512,6 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
     e = kernel_setup(s, (const void*)sync_kernel, bt, L.lds, &L.per_cu);
   } else if (pool2) {
     L.kind = KernelKind::pool2;
-    if (sl.counts) pool2_kernel = tex ? render_full_pool2<true, COUNT, true> : render_full_pool2<false, COUNT, true>;
-    else pool2_kernel = tex ? render_full_pool2<true, COUNT> : render_full_pool2<false, COUNT>;
     L.lds = lds3;
     const uint32_t tab = s->n_prog2 * 32u + DC_WORDS * 4u;
     consts.mat_lds = mats3 ? tab + P2_TABLE_BYTES : 0u;
@@ -551,23 +570,24 @@ static hipError_t launch_resolve(const DevParams& d, float* d_out, hipStream_t s
 }
 
 // ... and of a counts frame: every owned pixel with e_p > 0 divided by e_p = min(n_p, ns)
-static hipError_t launch_resolve_counts(const DevParams& d, float* d_out, hipStream_t stream, const uint32_t* counts) {
+static hipError_t launch_resolve_counts(const DevParams& d, float* d_out, hipStream_t stream, const FrameLayout& L) {
   const uint64_t pix_work = rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(resolve_counts_kernel, dim3((uint32_t)(pix_work / 256u)), dim3(256), 0, stream, d, make_pixmap(d), (uint32_t)pix_work, d_out, counts);
+  hipLaunchKernelGGL(resolve_counts_kernel, dim3((uint32_t)(pix_work / 256u)), dim3(256), 0, stream, d, make_pixmap(d), (uint32_t)pix_work, d_out,
+                     L.at(reinterpret_cast<const uint32_t*>(d_out), L.counts));
   return hipGetLastError();
 }
 
 // RTG_FLAG_RETIRE (include/rtiow_gpu.h): the retire step of a counts call over this rank's work items (rt_retire.h) -- mark the
 // OK bits and the estimate's partials, retire the candidates whose window is OK, sum the partials into the caller's block.
 // `r`: the block's in-fields, already validated.  A rank without work items (pix_work = 0) only writes the block's zeros.
-// `errp` (RTG_FLAG_DENOISE_ERROR, else nullptr): the error plane the filter of this call has written -- the rule reads it instead
-// of (S, Q).
-static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, uint64_t pix_work, const rtg_retire& r,
-                                const float* errp = nullptr) {
+// A frame with an error plane (RTG_FLAG_DENOISE_ERROR): the rule reads that plane, which the filter of this call has written,
+// instead of (S, Q) -- launch_post_steps orders the two.
+static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const FrameLayout& L, uint64_t pix_work,
+                                const rtg_retire& r) {
   const uint32_t n_blk = (uint32_t)(pix_work / 256u);
-  const uint64_t plane = (uint64_t)d.nx * d.ny;
+  const float* errp = L.at(d_out, L.error);
   RetireBufs b;
   b.pitch = (d.nx + 31u) / 32u + 1u;
   // [blk_se2: f64 x n_blk] [blk_held: u64 x n_blk] [blk_u32: 3 x n_blk] [okbits: ny x pitch words]
@@ -578,8 +598,8 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
   b.blk_u32 = reinterpret_cast<uint32_t*>(b.blk_held + n_blk);
   b.okbits = b.blk_u32 + 3ull * n_blk;
   b.planes = d_out;
-  b.counts = reinterpret_cast<uint32_t*>(d_out + 6ull * plane);
-  b.block = reinterpret_cast<uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
+  b.counts = reinterpret_cast<uint32_t*>(d_out) + L.counts;
+  b.block = reinterpret_cast<uint32_t*>(d_out) + L.retire;
   b.errp = errp;
   const RetireArgs a{r.target_se, d.ns, r.min_samples, r.radius};
   if (n_blk != 0u) {
@@ -598,10 +618,11 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
 // in-fields, already validated.
 // `guide` (RTG_FLAG_FEATURES in the same call, else nullptr): the features block's in-fields -- the filter is the guided one, over
 // the feature planes the frame holds now (the callers run the feature pass first).
-// RTG_FLAG_DENOISE_ERROR (sl.error): the ERR instantiations, which also write the frame's error plane.
-static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const rtg_denoise& in,
+// A frame with an error plane (RTG_FLAG_DENOISE_ERROR): the ERR instantiations, which also write it.
+static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const FrameLayout& L, const rtg_denoise& in,
                                  const rtg_features* guide = nullptr) {
-  const uint64_t n_pix = (uint64_t)d.nx * d.ny;
+  const uint64_t n_pix = L.n;
+  const bool error = L.has(L.error);
   const uint32_t n_blk = (uint32_t)((n_pix + 255u) / 256u);
   // [records: 32 B x n_pix] [blk_u32: 2 x n_blk, padded to 16 B] [guided: feature records: 32 B x n_pix]
   const size_t frec_at = (size_t)n_pix * 32u + (((size_t)n_blk * 8u + 15u) & ~(size_t)15u);
@@ -610,17 +631,17 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   uint32_t* words = reinterpret_cast<uint32_t*>(d_out);
   DenoiseBufs b;
   b.planes = d_out;
-  b.counts = sl.counts ? words + 6ull * n_pix : nullptr;
+  b.counts = L.at(words, L.counts);
   b.rec = reinterpret_cast<float4*>(s->cx->d_denoise);
   b.blk_u32 = reinterpret_cast<uint32_t*>(b.rec + 2ull * n_pix);
-  b.block = words + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
-  b.outp = reinterpret_cast<float*>(b.block + 16);
-  b.errp = sl.error ? d_out + error_plane_word(d.nx, d.ny, sl) : nullptr;
+  b.block = words + L.denoise;
+  b.outp = d_out + L.denoised;
+  b.errp = L.at(d_out, L.error);
   const DenoiseArgs a{in.k, in.radius, in.patch, d.ns};
   // the guided filter reads its neighbours' feature records through the caches, or (option guide_lds) from an LDS copy
   const int guided = !guide ? 0 : (s->guide_lds > 0 ? 2 : 1);
   void (*filter)(uint32_t, uint32_t, DenoiseArgs, DenoiseBufs, DenoiseGuide) =
-      sl.error ? (guided == 0 ? denoise_filter_kernel<0, true> : (guided == 1 ? denoise_filter_kernel<1, true> : denoise_filter_kernel<2, true>))
+      error ? (guided == 0 ? denoise_filter_kernel<0, true> : (guided == 1 ? denoise_filter_kernel<1, true> : denoise_filter_kernel<2, true>))
                : (guided == 0 ? denoise_filter_kernel<0, false> : (guided == 1 ? denoise_filter_kernel<1, false> : denoise_filter_kernel<2, false>));
   const size_t lds = denoise_lds_bytes(in.radius, in.patch, guided == 2);
   int per_cu = 0;
@@ -631,84 +652,112 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   DenoiseGuide gd{nullptr, 1.f, 1.f, 1.f};
   if (guide) {
     float4* frec = reinterpret_cast<float4*>(reinterpret_cast<char*>(s->cx->d_denoise) + frec_at);
-    const float* albedo = d_out + features_block_word(d.nx, d.ny, sl) + 16u;
     gd = DenoiseGuide{frec, guide->sigma_normal, guide->sigma_albedo, guide->sigma_depth};
-    hipLaunchKernelGGL(denoise_guide_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, albedo, albedo + 3ull * n_pix, albedo + 6ull * n_pix, frec);
+    hipLaunchKernelGGL(denoise_guide_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, (const float*)d_out + L.albedo, (const float*)d_out + L.normal,
+                       (const float*)d_out + L.depth, frec);
   }
-  hipLaunchKernelGGL(sl.error ? denoise_prepare_kernel<true> : denoise_prepare_kernel<false>, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
+  hipLaunchKernelGGL(error ? denoise_prepare_kernel<true> : denoise_prepare_kernel<false>, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, a, b);
   hipLaunchKernelGGL(filter, dim3((uint32_t)tiles), dim3(DN_THREADS), lds, stream, d.nx, d.ny, a, b, gd);
   hipLaunchKernelGGL(denoise_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
   return hipGetLastError();
-}
-// ... and the read-back of its in-fields on the launch stream, with a counts call's other read-backs
-static hipError_t read_denoise_block(const DevParams& d, const float* d_out, hipStream_t stream, const SampleSlice& sl, rtg_denoise* in) {
-  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + denoise_block_word(d.nx, d.ny, sl.counts, sl.retire);
-  return hipMemcpyAsync(in, d_block, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream);
 }
 
 // RTG_FLAG_FEATURES (include/rtiow_gpu.h): the feature pass over this rank's pixels (rt_features.h) -- the three planes behind the
 // features block and the block's out-fields.  `in`: the block's in-fields, already validated; compute = 0 writes the
 // out-fields alone.  The kernel is instantiated per scene-feature set as the probes' (rtg_probes.inc): deep graphs take the
 // general walk.
-static hipError_t launch_features(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl,
+static hipError_t launch_features(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const FrameLayout& L,
                                   const rtg_features& in) {
-  const uint64_t n_pix = (uint64_t)d.nx * d.ny;
   const uint64_t blocks = (uint64_t)((d.nx + 15u) / 16u) * ((d.ny + 15u) / 16u);
   if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
   const uint32_t n_blk = in.compute ? (uint32_t)blocks : 0u;
   hipError_t e = grow((void**)&s->cx->d_features, &s->cx->features_bytes, (size_t)std::max<uint64_t>(blocks, 1) * 8u);
   if (e != hipSuccess) return e;
   FeatureBufs b;
-  b.block = reinterpret_cast<uint32_t*>(d_out) + features_block_word(d.nx, d.ny, sl);
-  b.albedo = reinterpret_cast<float*>(b.block + 16);
-  b.normal = b.albedo + 3ull * n_pix;
-  b.depth = b.normal + 3ull * n_pix;
+  b.block = reinterpret_cast<uint32_t*>(d_out) + L.features;
+  b.albedo = d_out + L.albedo, b.normal = d_out + L.normal, b.depth = d_out + L.depth;
   b.blk_u32 = s->cx->d_features;
-  if (n_blk != 0u) {
-    const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
-    if (s->features & FEAT_DEEP)
-      hipLaunchKernelGGL((features_kernel<FEAT_ALL | FEAT_DEEP>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
-    else if (geom == 0)
-      hipLaunchKernelGGL((features_kernel<0u>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
-    else
-      hipLaunchKernelGGL((features_kernel<FEAT_ALL>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b);
-  }
+  if (n_blk != 0u)
+    with_feat<false>(s, [&](auto feat) { hipLaunchKernelGGL((features_kernel<decltype(feat)::value>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b); });
   hipLaunchKernelGGL(features_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
   return hipGetLastError();
 }
-// ... and the read-back of its in-fields on the launch stream, with the call's other read-backs
-static hipError_t read_features_block(const DevParams& d, const float* d_out, hipStream_t stream, const SampleSlice& sl, rtg_features* in) {
-  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + features_block_word(d.nx, d.ny, sl);
-  return hipMemcpyAsync(in, d_block, offsetof(rtg_features, traced), hipMemcpyDeviceToHost, stream);
+
+// What follows the render of a slice, in the one order of include/rtiow_gpu.h: the retire step (a frame without an error plane),
+// the filter (guided when the slice has feature planes), the retire step on the error plane the filter wrote, then the division
+// when the slice divides.  `fb`: the blocks' in-fields, already validated.  Called by launch_counts, launch_render and, on the
+// first device over the gathered frame, by rtg_par_cast_multi's flagged frames.
+static hipError_t launch_post_steps(rtg_scene* s, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl, const FrameLayout& L,
+                                    const FrameBlocks& fb) {
+  const uint64_t pix_work = rank_pix_work(d);
+  hipError_t e = hipSuccess;
+  if (sl.retire && !sl.error) e = launch_retire(s, d, d_out, stream, L, pix_work, fb.retire);
+  if (e == hipSuccess && sl.denoise) e = launch_denoise(s, d, d_out, stream, L, fb.denoise, sl.features ? &fb.features : nullptr);
+  if (e == hipSuccess && sl.retire && sl.error) e = launch_retire(s, d, d_out, stream, L, pix_work, fb.retire);
+  if (e != hipSuccess || !sl.divide) return e;
+  return sl.counts ? launch_resolve_counts(d, d_out, stream, L) : launch_resolve(d, d_out, stream);
+}
+
+// The render of the samples [sl.begin, d.ns), by the kernel the scene's features pick.  A counts call (sl.counts) runs the pool
+// kernels over its list; the baseline kernel walks every pixel and skips the inactive ones itself.
+template <bool COUNT>
+static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl) {
+  // geometry / texture features pick the kernel; the albedo-range bits only say whether the pool kernels' "accum
+  // is +0" argument holds (rt_pool.h PoolField)
+  const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
+  const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
+  // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
+  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
+  if (pool_ok) {  // (launch_full_pool names the kernel it picks)
+    s->cx->last_kernel = geom != 0 ? KernelKind::full_pool : KernelKind::lean_pool;
+    return geom != 0 ? launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl) : launch_pool<COUNT>(s, cam, d, d_out, stream, sl);
+  }
+  // the baseline kernels: counts, squares and slices of a progressive frame have instantiations of their own
+  const dim3 grid(((d.nx + 15) / 16) * ((d.ny + 15) / 16)), block(256);
+  const uint32_t divide = sl.divide ? 1u : 0u;
+  if (sl.counts)
+    with_feat<false>(s, [&](auto feat) {
+      constexpr uint32_t F = decltype(feat)::value;
+      void (*k)(DevScene, DevCamera, DevParams, float*, unsigned long long*, uint32_t, const uint32_t*) =
+          sl.squares ? render_counts_kernel<F, COUNT, true> : render_counts_kernel<F, COUNT, false>;
+      hipLaunchKernelGGL(k, grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, sl.list.counts);
+    });
+  else if (sl.squares)
+    with_feat<false>(s, [&](auto feat) {
+      hipLaunchKernelGGL((render_squares_kernel<decltype(feat)::value, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    });
+  else if (sl.sliced())
+    with_feat<false>(s, [&](auto feat) {
+      hipLaunchKernelGGL((render_slice_kernel<decltype(feat)::value, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
+    });
+  else
+    with_feat<true>(s, [&](auto feat) { hipLaunchKernelGGL((render_kernel<decltype(feat)::value, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters); });
+  return hipGetLastError();
 }
 
 // RTG_FLAG_SAMPLE_COUNTS (include/rtiow_gpu.h): compact this rank's active pixels (e_p > sl.begin) into the list the pool
 // kernels run over (rt_pool.h compact_*), read back its length and the call's sample count -- the one synchronisation of the
-// stream a counts call makes -- render the list with the kernel the features pick (the baseline kernel walks every pixel and
-// skips the inactive ones itself), then, without RTG_FLAG_PARTIAL, divide every owned pixel with e_p > 0 by e_p.
-// RTG_FLAG_RETIRE: the block's in-fields come back with that read-back (on their own when the call renders nothing); refused
-// ones end the call before it renders (s->cx->refusal), accepted ones run the retire step between the render and the division.
-// RTG_FLAG_DENOISE: its in-fields travel in the same read-back; the filter runs after the retire step, before the division.
-// RTG_FLAG_DENOISE_ERROR: the filter runs BEFORE the retire step, whose rule then reads the error plane it wrote.
-// RTG_FLAG_FEATURES: likewise its in-fields (a call that renders, retires and filters nothing syncs for them alone); the feature
-// pass runs first, before the render.
+// stream a counts call makes -- render the list (launch_slice), then the post-steps (launch_post_steps): without
+// RTG_FLAG_PARTIAL every owned pixel with e_p > 0 ends divided by e_p.
+// The in-fields of the slice's blocks (RTG_FLAG_RETIRE / DENOISE / FEATURES) come back with that read-back (on their own when the
+// call renders nothing; a call that renders nothing and has no block does not synchronise); refused ones end the call before it
+// renders (s->cx->refusal).  The feature pass runs first, before the render.
 template <bool COUNT>
 static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
-                                const SampleSlice& sl, uint32_t geom, bool pool_ok) {
+                                const SampleSlice& sl, const FrameLayout& L) {
   s->cx->counts_samples = 0;
   const uint64_t pix_work = rank_pix_work(d);
   if (pix_work == 0 && !sl.retire && !sl.features) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
-  rtg_retire rin{};  // (RTG_FLAG_RETIRE: the in-fields, read back below)
-  rtg_denoise din{};  // (RTG_FLAG_DENOISE: likewise)
-  rtg_features fin{};  // (RTG_FLAG_FEATURES: likewise)
-  const void* d_block = reinterpret_cast<const uint32_t*>(d_out) + retire_block_word(d.nx, d.ny);
+  FrameBlocks fb;
   SampleSlice ls = sl;
-  ls.list.counts = reinterpret_cast<const uint32_t*>(d_out + (sl.squares ? 6ull : 3ull) * d.nx * d.ny);
-  const PixMap pm = make_pixmap(d);
-  const uint32_t n_blk = (uint32_t)(pix_work / 256u);
-  hipError_t e;
-  if (sl.begin < d.ns && pix_work != 0) {
+  ls.list.counts = L.at(reinterpret_cast<const uint32_t*>(d_out), L.counts);
+  const bool renders = sl.begin < d.ns && pix_work != 0;
+  CompactResult h{};
+  hipError_t e = hipSuccess;
+  if (renders) {
+    const PixMap pm = make_pixmap(d);
+    const uint32_t n_blk = (uint32_t)(pix_work / 256u);
     e = grow((void**)&s->cx->d_list, &s->cx->list_bytes, 2 * pix_work * sizeof(uint32_t));
     if (e != hipSuccess) return e;
     // [blk_samples: u64 x n_blk] [CompactResult] [blk_active: n_blk] [blk_offset: n_blk]
@@ -727,152 +776,46 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     hipLaunchKernelGGL(write_list_consts, dim3(1), dim3(1), 0, stream, reinterpret_cast<ListConsts*>(s->cx->d_consts + 1), ls.list);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    CompactResult h{};
     e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && sl.retire) e = hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
-    if (e == hipSuccess && sl.features) e = read_features_block(d, d_out, stream, sl, &fin);
+  }
+  if (renders || sl.retire || sl.denoise || sl.features) {  // the blocks ride with the compaction result: ONE synchronisation
+    if (e == hipSuccess) e = read_blocks(L, sl, d_out, stream, &fb);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
-    if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
-    if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
-    if (sl.features && (s->cx->refusal = features_refusal(fin, sl.denoise))) return hipSuccess;
-    if (sl.features && (e = launch_features(s, cam, d, d_out, stream, sl, fin)) != hipSuccess) return e;
+    if ((s->cx->refusal = blocks_refusal(sl, fb, d.nranks))) return hipSuccess;
+  }
+  if (sl.features && (e = launch_features(s, cam, d, d_out, stream, L, fb.features)) != hipSuccess) return e;
+  if (renders) {
     s->cx->counts_samples = h.samples;
     ls.list_work = h.padded;
     if (s->verbose)
       fprintf(stderr, "[rtg] sample counts: samples [%u, %u): %u of %llu owned pixels active (list of %u work items), %llu samples\n",
               sl.begin, d.ns, h.active, (unsigned long long)owned_pixels(d), h.padded, h.samples);
-    if (h.active != 0u) {
-      if (geom != 0 && pool_ok) {
-        s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)
-        e = launch_full_pool<COUNT>(s, cam, d, d_out, stream, ls);
-      } else if (geom == 0 && pool_ok) {
-        s->cx->last_kernel = KernelKind::lean_pool;
-        e = launch_pool<COUNT>(s, cam, d, d_out, stream, ls);
-      } else {
-        // the baseline kernel (FEAT_DEEP graphs on the largest general walk, as the slices)
-        constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
-        const dim3 grid(((d.nx + 15) / 16) * ((d.ny + 15) / 16)), block(256);
-        void (*k)(DevScene, DevCamera, DevParams, float*, unsigned long long*, uint32_t, const uint32_t*);
-        if (s->features & FEAT_DEEP) k = sl.squares ? render_counts_kernel<D, COUNT, true> : render_counts_kernel<D, COUNT, false>;
-        else if (geom == 0) k = sl.squares ? render_counts_kernel<0u, COUNT, true> : render_counts_kernel<0u, COUNT, false>;
-        else k = sl.squares ? render_counts_kernel<FEAT_ALL, COUNT, true> : render_counts_kernel<FEAT_ALL, COUNT, false>;
-        hipLaunchKernelGGL(k, grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, ls.list.counts);
-        e = hipGetLastError();
-      }
-      if (e != hipSuccess) return e;
-    }
-  } else if (sl.retire || sl.denoise || sl.features) {
-    e = sl.retire ? hipMemcpyAsync(&rin, d_block, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream) : hipSuccess;
-    if (e == hipSuccess && sl.denoise) e = read_denoise_block(d, d_out, stream, sl, &din);
-    if (e == hipSuccess && sl.features) e = read_features_block(d, d_out, stream, sl, &fin);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return e;
-    if (sl.retire && (s->cx->refusal = retire_refusal(rin, d.nranks))) return hipSuccess;
-    if (sl.denoise && (s->cx->refusal = denoise_refusal(din, d.nranks))) return hipSuccess;
-    if (sl.features && (s->cx->refusal = features_refusal(fin, sl.denoise))) return hipSuccess;
-    if (sl.features && (e = launch_features(s, cam, d, d_out, stream, sl, fin)) != hipSuccess) return e;
+    if (h.active != 0u && (e = launch_slice<COUNT>(s, cam, d, d_out, stream, ls)) != hipSuccess) return e;
   }
-  if (sl.retire && !sl.error) {
-    e = launch_retire(s, d, d_out, stream, pix_work, rin);
-    if (e != hipSuccess) return e;
-  }
-  if (sl.denoise) {
-    e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &fin : nullptr);
-    if (e != hipSuccess) return e;
-  }
-  if (sl.retire && sl.error) {
-    e = launch_retire(s, d, d_out, stream, pix_work, rin, d_out + error_plane_word(d.nx, d.ny, sl));
-    if (e != hipSuccess) return e;
-  }
-  return sl.divide ? launch_resolve_counts(d, d_out, stream, ls.list.counts) : hipSuccess;
+  return launch_post_steps(s, d, d_out, stream, sl, L, fb);
 }
 
-// `sl` (rtg_api.hip SampleSlice): the samples of a progressive frame this call renders; the default is the whole frame.
+// One call's frame: the feature pass, the render, the post-steps.  `sl` (rtg_api.hip SampleSlice): the samples of a progressive
+// frame this call renders and what it does at the end; `L`: the frame's layout; `fb`: the in-fields of the slice's blocks, read
+// and validated by the caller (a counts call reads them itself, with its compaction result: launch_counts).
+// The kernel that renders also divides -- unless a post-step follows: then it renders an undivided slice and launch_post_steps
+// divides last.  A call with nothing to render (sample_begin = ns) and no post-step is the resolve step alone.
 template <bool COUNT>
-static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
-                                hipStream_t stream, const SampleSlice& sl = SampleSlice{}) {
-  // geometry / texture features pick the kernel; the albedo-range bits only say whether the pool kernels' "accum
-  // is +0" argument holds (rt_pool.h PoolField)
-  const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
-  const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
-  // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
-  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
+static hipError_t launch_render(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl,
+                                const FrameLayout& L, const FrameBlocks& fb) {
   s->cx->last_kernel = KernelKind::baseline;
-  if (sl.counts) return launch_counts<COUNT>(s, cam, d, d_out, stream, sl, geom, pool_ok);
-  if (sl.features && !sl.features_done) {
-    // RTG_FLAG_FEATURES without a count plane (the block's in-fields were read back and checked by rtg_par_cast_device): the
-    // feature pass first, then the call as without the flag (the filter, if any, guided)
-    hipError_t e = launch_features(s, cam, d, d_out, stream, sl, s->cx->features_in);
-    if (e != hipSuccess) return e;
-    SampleSlice rest = sl;
-    rest.features_done = true;
-    return launch_render<COUNT>(s, cam, d, d_out, stream, rest);
-  }
-  if (sl.denoise) {
-    // RTG_FLAG_DENOISE without a count plane (the block's in-fields were read back and checked by rtg_par_cast_device): render
-    // the slice as a PARTIAL one, whichever kernel takes it, filter the undivided sums, then divide as the resolve step does
-    const rtg_denoise din = s->cx->denoise_in;
+  if (sl.counts) return launch_counts<COUNT>(s, cam, d, d_out, stream, sl, L);
+  hipError_t e = sl.features ? launch_features(s, cam, d, d_out, stream, L, fb.features) : hipSuccess;
+  if (e != hipSuccess) return e;
+  const bool post = sl.denoise;  // (the retire step needs a count plane)
+  if (sl.begin != d.ns) {
     SampleSlice render = sl;
-    render.denoise = false, render.divide = false;
-    hipError_t e = launch_render<COUNT>(s, cam, d, d_out, stream, render);
-    if (e == hipSuccess) e = launch_denoise(s, d, d_out, stream, sl, din, sl.features ? &s->cx->features_in : nullptr);
-    if (e != hipSuccess) return e;
+    if (post) render.divide = false;
+    e = launch_slice<COUNT>(s, cam, d, d_out, stream, render);
+  } else if (!post) {
     return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;
   }
-  if (sl.begin == d.ns) return sl.divide ? launch_resolve(d, d_out, stream) : hipSuccess;  // nothing to render
-  if (geom != 0 && pool_ok) {
-    s->cx->last_kernel = KernelKind::full_pool;  // (launch_full_pool names the kernel it picks)
-    return launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl);
-  }
-  if (geom == 0 && pool_ok) {
-    s->cx->last_kernel = KernelKind::lean_pool;
-    return launch_pool<COUNT>(s, cam, d, d_out, stream, sl);
-  }
-  uint32_t nbx = (d.nx + 15) / 16, nby = (d.ny + 15) / 16;
-  dim3 grid(nbx * nby), block(256);
-  if (sl.squares) {
-    // RTG_FLAG_SUM_SQUARES, whole frames and slices: the squares' own instantiations (FEAT_DEEP as below)
-    constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
-    const uint32_t divide = sl.divide ? 1u : 0u;
-    if (s->features & FEAT_DEEP)
-      hipLaunchKernelGGL((render_squares_kernel<D, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    else if (geom == 0)
-      hipLaunchKernelGGL((render_squares_kernel<0u, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    else
-      hipLaunchKernelGGL((render_squares_kernel<FEAT_ALL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    return hipGetLastError();
-  }
-  if (sl.sliced()) {
-    // a slice of a progressive frame: its own instantiations (FEAT_DEEP graphs on the largest general walk, as the probes)
-    constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
-    const uint32_t divide = sl.divide ? 1u : 0u;
-    if (s->features & FEAT_DEEP)
-      hipLaunchKernelGGL((render_slice_kernel<D, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    else if (geom == 0)
-      hipLaunchKernelGGL((render_slice_kernel<0u, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    else
-      hipLaunchKernelGGL((render_slice_kernel<FEAT_ALL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters, sl.begin, divide);
-    return hipGetLastError();
-  }
-  if (s->features & FEAT_DEEP) {
-    // the general walk, sized for what the graph needs (flat_scene.h FEAT_DEEP_FEW_WRAPPERS / FEAT_DEEP_ONE_LEVEL; the probes
-    // of rtg_probes.inc keep the largest instantiation: same arithmetic)
-    const bool few = s->deep_sized && (s->features & FEAT_DEEP_FEW_WRAPPERS) != 0, one = s->deep_sized && (s->features & FEAT_DEEP_ONE_LEVEL) != 0;
-    constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
-    if (few && one)
-      hipLaunchKernelGGL((render_kernel<D | FEAT_DEEP_FEW_WRAPPERS | FEAT_DEEP_ONE_LEVEL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-    else if (few)
-      hipLaunchKernelGGL((render_kernel<D | FEAT_DEEP_FEW_WRAPPERS, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-    else if (one)
-      hipLaunchKernelGGL((render_kernel<D | FEAT_DEEP_ONE_LEVEL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-    else
-      hipLaunchKernelGGL((render_kernel<D, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-  } else if (geom == 0)
-    hipLaunchKernelGGL((render_kernel<0u, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-  else
-    hipLaunchKernelGGL((render_kernel<FEAT_ALL, COUNT>), grid, block, 0, stream, s->dev, cam, d, d_out, s->cx->d_counters);
-  return hipGetLastError();
+  if (e != hipSuccess || !post) return e;
+  return launch_post_steps(s, d, d_out, stream, sl, L, fb);
 }
-

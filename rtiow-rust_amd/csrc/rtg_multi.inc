@@ -252,6 +252,8 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
   const size_t bytes = n_floats * sizeof(float);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
   const SampleSlice sl = slice_of(params);
+  const FrameLayout L(params->nx, params->ny, 0u);  // (the plain frame)
+  const FrameBlocks fb;
   // (1) every scene renders ITS tiles (tile % n_scenes == i) into its own zero-filled full frame, on its own stream (resuming a
   // progressive frame: its tiles hold the caller's running sums)
   for (int i = 0; i < n_scenes; i++) {
@@ -278,7 +280,7 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
     }
     HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
     const DevCamera cam = to_dev(camera);
-    HIP_TRY(count ? launch_render<true>(s, cam, d, s->d_frame, s->own_stream, sl) : launch_render<false>(s, cam, d, s->d_frame, s->own_stream, sl));
+    HIP_TRY(count ? launch_render<true>(s, cam, d, s->d_frame, s->own_stream, sl, L, fb) : launch_render<false>(s, cam, d, s->d_frame, s->own_stream, sl, L, fb));
     HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
     {
       const int rc_ctx = ctx_release(s, s->own_stream);
@@ -385,20 +387,20 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
 // (2) the packed collective over EVERY plane the ranks wrote (rt_multi_planes.h PlaneSet: one pack kernel, one ncclSend /
 //     ncclRecv pair and one unpack kernel per handle that travels; handles on the first device are unpacked from their own
 //     buffer) assembles the frame on the first device.  Copies only;
-// (3) the first device runs what a one-handle call with sample_begin == ns runs on that frame: launch_retire (any radius: the
-//     window sees the whole frame), launch_denoise (guided over the gathered feature planes), the division;
+// (3) the first device runs what a one-handle call with sample_begin == ns runs on that frame: launch_post_steps (the retire
+//     step with any radius: the window sees the whole frame; the filter guided over the gathered feature planes; the division);
 // (4) copy back what rtg_par_cast copies back; traced / missed of the features block are the sums over the ranks.
 int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params, float* out_rgb,
                                rtg_stats* stats) {
   const SampleSlice sl = slice_of(params);
   DevParams d1;  // the one-handle call's parameters (nranks = 1, the caller's tiles): the first device's step runs over them
   if (int rc = check_params(scenes[0], camera, params, &d1)) return rc;
-  const FrameLayout L = frame_layout(params->nx, params->ny, sl);
+  const FrameLayout L(params->nx, params->ny, params->flags);
   FrameBlocks fb;
   if (int rc = check_blocks(L, sl, out_rgb, 1u, &fb)) return rc;
   const uint32_t compute = sl.features ? fb.features.compute : 0u;
-  const PlaneSet ps = make_plane_set(params->nx, params->ny, sl, compute != 0u);
-  rtg_params rp = *params;  // what the ranks render: the slice, never resolved
+  const PlaneSet ps = make_plane_set(L, compute != 0u);
+  rtg_params rp = *params;  // what the ranks render into that frame: the slice, never retired, filtered or resolved
   rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR | RTG_FLAG_FEATURES)) | RTG_FLAG_PARTIAL;
   const SampleSlice rsl = slice_of(&rp);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
@@ -416,15 +418,15 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   // output plane survive); the others get what their slice reads -- the float planes when it resumes or renders counts (pixels
   // with n_p = 0 must travel back as they came), and the count plane.  The feature pass takes its in-fields from the host copy.
   Extents rank_up;
-  if (sl.begin != 0u || sl.counts) rank_up.add(0, L.bytes + L.count_bytes);
+  if (sl.begin != 0u || sl.counts) rank_up.add(0, sl.counts ? L.counts + L.n : L.planes());
   for (int i = 0; i < n_scenes; i++) {
     rtg_scene* s = scenes[i];
     HIP_TRY(hipSetDevice(s->device));
     if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.frame_bytes);
+    hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.words * sizeof(float));
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
     char* dev = reinterpret_cast<char*>(s->d_frame);
-    const Extents up = i == 0 ? upload_extents(L, sl, false, compute) : rank_up;
+    const Extents up = i == 0 ? upload_extents(L, false, sl.begin, compute) : rank_up;
     for (int k = 0; k < up.n; k++) HIP_TRY(hipMemcpyAsync(dev + up.e[k].lo, host + up.e[k].lo, up.e[k].hi - up.e[k].lo, hipMemcpyHostToDevice, s->own_stream));
     {
       const int rc_ctx = ctx_acquire(s);
@@ -435,10 +437,10 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
       HIP_TRY(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), s->own_stream));
     }
     HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
-    HIP_TRY(count ? launch_render<true>(s, cam, dps[i], s->d_frame, s->own_stream, rsl) : launch_render<false>(s, cam, dps[i], s->d_frame, s->own_stream, rsl));
+    HIP_TRY(count ? launch_render<true>(s, cam, dps[i], s->d_frame, s->own_stream, rsl, L, fb) : launch_render<false>(s, cam, dps[i], s->d_frame, s->own_stream, rsl, L, fb));
     // the feature pass BEHIND the render (the planes do not depend on each other): a counts call's compaction wait, the rank's
-    // one host wait, then covers no feature kernel, and the next rank is launched while this one traces (`sl`: the frame's layout)
-    if (sl.features) HIP_TRY(launch_features(s, cam, dps[i], s->d_frame, s->own_stream, sl, fb.features));
+    // one host wait, then covers no feature kernel, and the next rank is launched while this one traces
+    if (sl.features) HIP_TRY(launch_features(s, cam, dps[i], s->d_frame, s->own_stream, L, fb.features));
     HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
     samples += rsl.counts ? s->cx->counts_samples : owned_pixels(dps[i]) * (dps[i].ns - rsl.begin);
     {
@@ -504,14 +506,7 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   if (!head->post0) HIP_TRY(hipEventCreate(&head->post0));
   if (!head->post1) HIP_TRY(hipEventCreate(&head->post1));
   HIP_TRY(hipEventRecord(head->post0, hs));
-  // (RTG_FLAG_DENOISE_ERROR: the filter first, then the retire rule on the error plane it wrote -- as on one handle)
-  if (sl.retire && !sl.error) HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire));
-  if (sl.denoise) HIP_TRY(launch_denoise(head, d1, head->d_frame, hs, sl, fb.denoise, sl.features ? &fb.features : nullptr));
-  if (sl.retire && sl.error)
-    HIP_TRY(launch_retire(head, d1, head->d_frame, hs, rank_pix_work(d1), fb.retire, head->d_frame + error_plane_word(d1.nx, d1.ny, sl)));
-  if (sl.divide)
-    HIP_TRY(sl.counts ? launch_resolve_counts(d1, head->d_frame, hs, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(head->d_frame) + L.bytes))
-                      : launch_resolve(d1, head->d_frame, hs));
+  HIP_TRY(launch_post_steps(head, d1, head->d_frame, hs, sl, L, fb));
   HIP_TRY(hipEventRecord(head->post1, hs));
   // (4) wait, copy out
   HIP_TRY(hipStreamSynchronize(hs));
@@ -521,7 +516,7 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   }
   if (sl.features) {  // traced / missed: the sums over the ranks' blocks, into the first scene's before it is copied out
     uint32_t sum[2] = {0u, 0u};
-    const size_t at = L.fblock_bytes + offsetof(rtg_features, traced);
+    const size_t at = L.features * sizeof(uint32_t) + offsetof(rtg_features, traced);
     for (int i = 0; i < n_scenes; i++) {
       uint32_t tm[2] = {0u, 0u};
       HIP_TRY(hipSetDevice(scenes[i]->device));
@@ -532,7 +527,7 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
     HIP_TRY(hipMemcpy(reinterpret_cast<char*>(head->d_frame) + at, sum, sizeof(sum), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipSetDevice(head->device));
-  const Extents back = copy_back_extents(L, sl, compute);
+  const Extents back = copy_back_extents(L, compute);
   for (int k = 0; k < back.n; k++)
     HIP_TRY(hipMemcpy(host + back.e[k].lo, reinterpret_cast<const char*>(head->d_frame) + back.e[k].lo, back.e[k].hi - back.e[k].lo, hipMemcpyDeviceToHost));
   if (verbose) {  // the pack kernels (summed over the handles) and the first device's unpack kernels, by their events

@@ -11,17 +11,11 @@ int rtg_debug_hit_top(rtg_scene* s, size_t n, const float* rays, uint64_t seed, 
   HIP_TRY(d_mat.alloc(n));
   HIP_TRY(hipMemcpy(d_rays.p, rays, 7 * n * sizeof(float), hipMemcpyHostToDevice));
   dim3 grid((uint32_t)((n + 63) / 64)), block(64);
-  if (n) {
-    if (s->features & FEAT_DEEP)
-      hipLaunchKernelGGL((debug_hit_top_kernel<FEAT_ALL | FEAT_DEEP>), grid, block, 0, 0, s->dev, (uint32_t)n, d_rays.p, (uint32_t)seed,
-                         (uint32_t)(seed >> 32), t_near, d_out.p, d_mat.p);
-    else if (s->features == 0)
-      hipLaunchKernelGGL((debug_hit_top_kernel<0u>), grid, block, 0, 0, s->dev, (uint32_t)n, d_rays.p, (uint32_t)seed,
-                         (uint32_t)(seed >> 32), t_near, d_out.p, d_mat.p);
-    else
-      hipLaunchKernelGGL((debug_hit_top_kernel<FEAT_ALL>), grid, block, 0, 0, s->dev, (uint32_t)n, d_rays.p,
-                         (uint32_t)seed, (uint32_t)(seed >> 32), t_near, d_out.p, d_mat.p);
-  }
+  if (n)
+    with_feat<false>(s, [&](auto feat) {
+      hipLaunchKernelGGL((debug_hit_top_kernel<decltype(feat)::value>), grid, block, 0, 0, s->dev, (uint32_t)n, d_rays.p, (uint32_t)seed, (uint32_t)(seed >> 32),
+                         t_near, d_out.p, d_mat.p);
+    });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, d_out.p, 8 * n * sizeof(float), hipMemcpyDeviceToHost));
@@ -63,7 +57,7 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
     HIP_TRY(hipMemcpy(s->cx->d_counters + 30, ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
     const DevCamera cam = to_dev(camera);
     s->whole_scratch = true;  // the trace reads every sample colour back: one sample pass
-    hipError_t e = launch_render<true>(s, cam, d, s->d_frame, nullptr);
+    hipError_t e = launch_render<true>(s, cam, d, s->d_frame, nullptr, SampleSlice{}, FrameLayout(d.nx, d.ny, 0u), FrameBlocks{});
     s->whole_scratch = false;
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipMemset(s->cx->d_counters + 30, 0, 2 * sizeof(unsigned long long));
@@ -99,17 +93,10 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
   HIP_TRY(hipMemcpy(ds.p, samples, n * 4, hipMemcpyHostToDevice));
   DevCamera cam = to_dev(camera);
   dim3 grid((uint32_t)((n + 63) / 64)), block(64);
-  if (n) {
-    if (s->features & FEAT_DEEP)
-      hipLaunchKernelGGL((debug_samples_kernel<FEAT_ALL | FEAT_DEEP>), grid, block, 0, 0, s->dev, cam, d, (uint32_t)n, dx.p, dy.p, ds.p,
-                         drgb.p, dinfo.p);
-    else if (s->features == 0)
-      hipLaunchKernelGGL((debug_samples_kernel<0u>), grid, block, 0, 0, s->dev, cam, d, (uint32_t)n, dx.p, dy.p, ds.p,
-                         drgb.p, dinfo.p);
-    else
-      hipLaunchKernelGGL((debug_samples_kernel<FEAT_ALL>), grid, block, 0, 0, s->dev, cam, d, (uint32_t)n, dx.p, dy.p,
-                         ds.p, drgb.p, dinfo.p);
-  }
+  if (n)
+    with_feat<false>(s, [&](auto feat) {
+      hipLaunchKernelGGL((debug_samples_kernel<decltype(feat)::value>), grid, block, 0, 0, s->dev, cam, d, (uint32_t)n, dx.p, dy.p, ds.p, drgb.p, dinfo.p);
+    });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out_rgb, drgb.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));

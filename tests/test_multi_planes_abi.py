@@ -1,5 +1,6 @@
-"""Flagged frames over several handles, the parts that need no GPU: the scene option and its block in the header; PlaneSet
-(csrc/rt_multi_planes.h, host part) against the binding's layout helpers and the plane-major packed index, through a stand-alone
+"""Flagged frames over several handles, the parts that need no GPU: the scene option and its block in the header; FrameLayout,
+the upload / copy-back extents and PlaneSet (csrc/rt_multi_planes.h, host part) against the binding's layout and the plane-major
+packed index, through a stand-alone
 C++ program built with the address and undefined-behaviour sanitizers and run as a child process; the binding's own checks; and
 that host/rtiow.hpp's multi calls compile."""
 import itertools
@@ -23,30 +24,49 @@ PROGRAM = r"""
 #include <vector>
 #include "rt_multi_planes.h"
 using namespace rtg;
-struct Slice { bool squares, counts, retire, denoise, features; };
 static void fail(const char* what) { std::printf("FAIL %%s\n", what); std::exit(1); }
+static void print_extents(const Extents& x) {
+  for (int i = 0; i < x.n; i++) std::printf(" %%llu-%%llu", (unsigned long long)x.e[i].lo, (unsigned long long)x.e[i].hi);
+}
 int main() {
   const uint32_t sizes[][2] = {%(sizes)s};
+  const uint32_t flag_of[6] = {RTG_FLAG_SUM_SQUARES, RTG_FLAG_SAMPLE_COUNTS, RTG_FLAG_RETIRE, RTG_FLAG_DENOISE, RTG_FLAG_FEATURES, RTG_FLAG_DENOISE_ERROR};
   for (auto& sz : sizes)
-    for (int bitsv = 0; bitsv < 64; bitsv++) {
-      const Slice sl{(bitsv & 1) != 0, (bitsv & 2) != 0, (bitsv & 4) != 0, (bitsv & 8) != 0, (bitsv & 16) != 0};
-      const bool compute = (bitsv & 32) != 0;
-      if ((sl.retire && !(sl.squares && sl.counts)) || (sl.denoise && !sl.squares) || (compute && !sl.features)) continue;
-      const PlaneSet ps = make_plane_set(sz[0], sz[1], sl, compute);
-      std::printf("set %%u %%u %%d %%d %%d %%d %%d %%d : %%u %%u :", sz[0], sz[1], sl.squares, sl.counts, sl.retire, sl.denoise, sl.features, compute,
+    for (int bitsv = 0; bitsv < 128; bitsv++) {
+      const bool squares = (bitsv & 1) != 0, counts = (bitsv & 2) != 0, retire = (bitsv & 4) != 0, denoise = (bitsv & 8) != 0, features = (bitsv & 16) != 0;
+      const bool error = (bitsv & 32) != 0, compute = (bitsv & 64) != 0;
+      if ((retire && !(squares && counts)) || (denoise && !squares) || (error && !denoise) || (compute && !features)) continue;
+      uint32_t flags = 0;
+      for (int k = 0; k < 6; k++) if (bitsv & (1 << k)) flags |= flag_of[k];
+      const FrameLayout L(sz[0], sz[1], flags);
+      const PlaneSet ps = make_plane_set(L, compute);
+      std::printf("set %%u %%u %%d %%d %%d %%d %%d %%d %%d : %%u %%u :", sz[0], sz[1], squares, counts, retire, denoise, features, error, compute,
                   ps.n_groups, ps.words_per_pixel);
       for (uint32_t g = 0; g < ps.n_groups; g++) std::printf(" %%llu/%%u/%%u", (unsigned long long)ps.g[g].first, ps.g[g].wpp, ps.g[g].k0);
-      std::printf(" : %%llu %%llu %%llu\n", (unsigned long long)retire_block_word(sz[0], sz[1]),
-                  (unsigned long long)denoise_block_word(sz[0], sz[1], sl.counts, sl.retire), (unsigned long long)features_block_word(sz[0], sz[1], sl));
+      // the parts, -1 = absent; first the retire block of the frame that has one, whatever this frame's flags
+      const FrameLayout R(sz[0], sz[1], RTG_FLAG_SUM_SQUARES | RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RETIRE);
+      std::printf(" : %%lld", (long long)R.retire);
+      for (uint64_t part : {L.n, L.counts, L.retire, L.denoise, L.denoised, L.features, L.albedo, L.normal, L.depth, L.error, L.words})
+        std::printf(" %%lld", L.has(part) ? (long long)part : -1ll);
+      std::printf("\n");
+      for (int other = 0; other < 2; other++)
+        for (uint32_t begin = 0; begin < 2; begin++)
+          for (uint32_t cmp = 0; cmp < 2; cmp++) {
+            std::printf("ext %%u %%u %%d %%d %%u %%u :", sz[0], sz[1], bitsv & 63, other, begin, cmp);
+            print_extents(upload_extents(L, other != 0, begin, cmp));
+            std::printf(" :");
+            print_extents(copy_back_extents(L, cmp));
+            std::printf("\n");
+          }
     }
   // pack and unpack a host frame of pix_work pixels through the plane-major index: every packed word visited once, none beyond
   // pix_work * words_per_pixel (the vectors are exactly that long: the address sanitizer sees an overrun)
   const uint32_t works[] = {%(works)s};
   for (int full = 0; full < 2; full++) {
-    const Slice sl{full != 0, false, false, false, full != 0};
     for (uint32_t pw : works) {
-      const PlaneSet ps = make_plane_set(pw ? pw : 1u, 1u, sl, full != 0);  // a frame of pw x 1 pixels: work item w = pixel w
-      const uint64_t n = pw, frame_words = features_block_word(pw ? pw : 1u, 1u, sl) + 16u + 7u * n;
+      const FrameLayout L(pw ? pw : 1u, 1u, RTG_FLAG_FEATURES | (full ? RTG_FLAG_SUM_SQUARES : 0u));  // a frame of pw x 1 pixels: work item w = pixel w
+      const PlaneSet ps = make_plane_set(L, full != 0);
+      const uint64_t n = pw, frame_words = L.features + 16u + 7u * n;
       std::vector<uint32_t> frame(frame_words), back(frame_words, 0u), packed((size_t)pw * ps.words_per_pixel, 0xdeadbeefu);
       std::vector<uint32_t> seen(packed.size(), 0u);
       for (uint64_t i = 0; i < frame_words; i++) frame[i] = (uint32_t)(i * 2654435761u + 17u);
@@ -98,17 +118,25 @@ def program_output(tmp_path_factory):
     return r.stdout.splitlines()
 
 
+def _combos():
+    """The legal (squares, counts, retire, denoise, features, error) combinations: retire needs squares and counts, denoise
+    needs squares, error needs denoise."""
+    return [c for c in itertools.product((0, 1), repeat=6)
+            if not (c[2] and not (c[0] and c[1])) and not (c[3] and not c[0]) and not (c[5] and not c[3])]
+
+
 def test_plane_set_against_the_layout_helpers(pkg, program_output):
     capi = pkg.capi
     lines = [ln for ln in program_output if ln.startswith("set ")]
-    combos = [c for c in itertools.product((0, 1), repeat=6)
-              if not (c[2] and not (c[0] and c[1])) and not (c[3] and not c[0]) and not (c[5] and not c[4])]
-    assert len(lines) == len(SIZES) * len(combos) and len(combos) == 24
+    combos = [c + (k,) for c in _combos() for k in ((0, 1) if c[4] else (0,))]
+    assert len(_combos()) == 22 and len(combos) == 33
+    assert len([c for c in combos if not c[5]]) == 24   # (the combinations without the error flag, as before it existed)
+    assert len(lines) == len(SIZES) * len(combos)
     seen = set()
     for ln in lines:
         head, sizes, groups, blocks = [part.split() for part in ln[4:].split(":")]
-        nx, ny, squares, counts, retire, denoise, features, compute = map(int, head)
-        seen.add((nx, ny, squares, counts, retire, denoise, features, compute))
+        nx, ny, squares, counts, retire, denoise, features, error, compute = map(int, head)
+        seen.add((nx, ny, squares, counts, retire, denoise, features, error, compute))
         n = nx * ny
         want = [(0, 3)]
         if squares:
@@ -121,15 +149,63 @@ def test_plane_set_against_the_layout_helpers(pkg, program_output):
         assert got == [(f, w, k) for (f, w), k in zip(want, k0)], ln
         wpp = sum(w for _, w in want)
         assert list(map(int, sizes)) == [len(want), wpp] and 3 <= wpp <= 13, ln
-        r_word, d_word, f_word = map(int, blocks)
-        assert r_word * 4 == capi.retire_block_offset(nx, ny), ln
+        r_any, n_got, c_word, r_word, d_word, dd_word, f_word, a_word, nm_word, dp_word, e_word, words = map(int, blocks)
+        assert r_any * 4 == capi.retire_block_offset(nx, ny), ln
+        if retire:
+            assert r_word == r_any, ln
         if denoise:
             assert d_word * 4 == capi.denoise_block_offset(nx, ny, bool(counts), bool(retire)), ln
         if features:
             assert f_word * 4 == capi.features_block_offset(nx, ny, bool(squares), bool(counts), bool(retire), bool(denoise)), ln
-            # the planes end where the frame ends
+            # the planes end where the frame ends (or, with the error flag, where the error plane's padding begins)
             assert (f_word + 16 + 7 * n) * 4 == capi.features_frame_bytes(nx, ny, bool(squares), bool(counts), bool(retire), bool(denoise)), ln
+        # ... and field for field the binding's layout: absent parts are absent in both
+        L = capi.FrameLayout(nx, ny, bool(squares), bool(counts), bool(retire), bool(denoise), bool(features), bool(error))
+        have = (n_got, c_word, r_word, d_word, dd_word, f_word, a_word, nm_word, dp_word, e_word, words)
+        ref = (L.n, L.counts, L.retire, L.denoise, L.denoised, L.features, L.albedo, L.normal, L.depth, L.error, L.words)
+        assert have == tuple(-1 if v is None else v for v in ref), ln
+        assert (e_word >= 0) == bool(error) and words * 4 == L.words * 4, ln
+        if error:
+            assert e_word * 4 == L.error * 4 and e_word % 2 == 0 and words == e_word + 3 * n, ln
+            if features:
+                assert words * 4 == capi.features_frame_bytes(nx, ny, True, bool(counts), bool(retire), True, error=True), ln
+            else:
+                assert words * 4 == capi.denoise_frame_bytes(nx, ny, bool(counts), bool(retire), error=True), ln
     assert seen == {(nx, ny) + c for nx, ny in SIZES for c in combos}
+
+
+def test_upload_and_copy_back_extents(pkg, program_output):
+    """upload_extents / copy_back_extents (csrc/rt_multi_planes.h) for every legal flag combination, other_ranks, begin and
+    compute in {0, 1}: ascending, disjoint byte ranges inside the frame; nothing copied back covers a block's in-fields."""
+    capi = pkg.capi
+    lines = [ln for ln in program_output if ln.startswith("ext ")]
+    combos = _combos()
+    assert len(lines) == len(SIZES) * 33 * 8
+    seen = set()
+    for ln in lines:
+        head, up, back = [part.split() for part in ln[4:].split(":")]
+        nx, ny, bits, other, begin, compute = map(int, head)
+        c = tuple((bits >> k) & 1 for k in range(6))
+        assert c in combos, ln
+        seen.add((nx, ny) + c + (other, begin, compute))
+        L = capi.FrameLayout(nx, ny, *map(bool, c))
+        in_fields = [(4 * at, 4 * at + getattr(cls, first_out).offset)
+                     for at, cls, first_out in ((L.retire, capi.Retire, "active"), (L.denoise, capi.Denoise, "filtered"), (L.features, capi.Features, "traced"))
+                     if at is not None]
+        assert len(in_fields) == c[2] + c[3] + c[4] and all(hi > lo for lo, hi in in_fields), ln
+        for name, ranges in (("upload", up), ("copy back", back)):
+            r = [tuple(map(int, x.split("-"))) for x in ranges]
+            assert all(lo < hi for lo, hi in r), (name, ln)
+            assert all(a[1] <= b[0] for a, b in zip(r, r[1:])), (name, ln)       # ascending and disjoint
+            assert all(0 <= lo and hi <= 4 * L.words for lo, hi in r), (name, ln)
+            assert len(r) <= 6, (name, ln)
+        for lo, hi in [tuple(map(int, x.split("-"))) for x in back]:
+            assert all(hi <= f_lo or lo >= f_hi for f_lo, f_hi in in_fields), ln
+        # the float planes always come back, and the in-fields of every block the frame has always travel up
+        assert back and back[0].startswith("0-"), ln
+        ups = [tuple(map(int, x.split("-"))) for x in up]
+        assert all(any(lo <= f_lo and f_hi <= hi for lo, hi in ups) for f_lo, f_hi in in_fields), ln
+    assert seen == {(nx, ny) + c + okc for nx, ny in SIZES for c in combos for okc in itertools.product((0, 1), repeat=3)}
 
 
 def test_plane_major_pack_and_unpack(program_output):
