@@ -742,7 +742,10 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
         r[2] = l.x, r[3] = l.y, r[4] = l.z, r[5] = l.w, r[6] = h.x, r[7] = h.y;
         r[8] = l.y, r[9] = l.x, r[10] = l.w, r[11] = l.z, r[12] = h.y, r[13] = h.x;
       } else if (op == OP_SPHERE) {  // lo = (offset.xyz, radius), hi = (-, -, material, flags)
-        r[0] = h.z, r[1] = h.w, r[2] = l.x, r[3] = l.y, r[4] = l.z, r[5] = l.w;
+        // a record without a Translate carries the offset +0.0f, whatever its packet holds: the sphere pass subtracts the
+        // offset of EVERY record (see there)
+        const bool tr = (h.w & F_TRANSLATE) != 0u;
+        r[0] = h.z, r[1] = h.w, r[2] = tr ? l.x : 0u, r[3] = tr ? l.y : 0u, r[4] = tr ? l.z : 0u, r[5] = l.w;
       } else {  // END + padding
         r[0] = 0u, r[1] = h.w;
         for (uint32_t k = 2; k < LDS_END_BYTES / 4u; k++) r[k] = 0u;
@@ -824,6 +827,8 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
   __syncthreads();  // program staged, pools initialised (the only workgroup barrier)
 
   const float t_near = load_const(&lc->P.t_near);
+  const bool t_near_pos = t_near > 0.f;        // wave-uniform: the sphere pass's one-division form needs it (rt_sphere_hit.h)
+  constexpr bool ZERO_OFF = USE_LDS && !WIDE;  // the staging loop above wrote the image: untranslated SPHERE records hold offset +0
   uint32_t t_count = 0, s_count = 0, e_count = POOL, n_dead = 0;  // wave-uniform list sizes / retired slots
   uint32_t tn_count = 0;  // RT_T_PRIORITY: camera rays of new paths, stacked from the top of tlist downwards (t_count: continuing rays, from 0 upwards)
   uint32_t w_next = 0, w_end = 0;                                  // this wave's reserved range of work items
@@ -1347,10 +1352,15 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
       if (op == OP_SPHERE) {  // Sphere::hit, object.rs:84-111 (+ Translate :275)
         if (COUNT) cnt.prim++;
         const uint4 slo = RT_SPHERE_GEOM(pc);  // (offset.xyz, radius)
-        V3 lo_o = o;
-        if (c_flags & F_TRANSLATE) lo_o = vsub(o, mk(u2f(slo.x), u2f(slo.y), u2f(slo.z)));
+        // The image this kernel stages holds +0.0f as the offset of a record without a Translate, so the subtraction stands
+        // alone, without a select on F_TRANSLATE: x - (+0) is x bit for bit for every x -- a number, an infinity and a NaN
+        // pass through, and -0 - (+0) = -0 + (-0) = -0 in round-to-nearest (only x + (-x) gives +0).  The SCATTER pass keeps
+        // its select: hp + off would turn a -0 into +0.  (Images staged elsewhere -- the 4-wide one, global memory -- keep it.)
+        V3 lo_o = vsub(o, mk(u2f(slo.x), u2f(slo.y), u2f(slo.z)));
+        if (!ZERO_OFF && !(c_flags & F_TRANSLATE)) lo_o = o;
         float t;
-        if (sphere_hit_t_a(lo_o, d, dd, u2f(slo.w), t_near, best, t)) {
+        // one division per lane (rt_sphere_hit.h); a launch whose t_near is not > 0 gets the reference's roots from the same code
+        if (sphere_hit_t_a_1div(lo_o, d, dd, u2f(slo.w), t_near, best, t_near_pos, t)) {
           best = t;
           best_pc = pc;
           best_flags = c_flags;

@@ -3,6 +3,7 @@
 #pragma once
 #include "flat_scene.h"
 #include "rt_device.h"
+#include "rt_sphere_hit.h"
 
 namespace rtg {
 
@@ -82,27 +83,7 @@ struct Counts {
 
 RT_DEV float u2f(uint32_t u) { return __uint_as_float(u); }
 
-// object.rs:84-111 (sphere at the local origin), with a = dot(d, d) handed in: it depends on the ray alone, so a walk that
-// keeps its ray in registers forms it once per ray (rt_pool.h, the refill) instead of once per sphere
-RT_DEV bool sphere_hit_t_a(V3 o, V3 d, float a, float radius, float t0, float t1, float& t_out) {
-  float b = vdot(o, d);
-  float c = vdot(o, o) - radius * radius;
-  float disc = b * b - a * c;
-  if (disc > 0.f) {
-    float sq = __builtin_sqrtf(disc);
-    float t = (-b - sq) / a;
-    if (t < t1 && t >= t0) {
-      t_out = t;
-      return true;
-    }
-    t = (-b + sq) / a;
-    if (t < t1 && t >= t0) {
-      t_out = t;
-      return true;
-    }
-  }
-  return false;
-}
+// Sphere::hit, object.rs:84-111: sphere_hit_t_a (the reference form) and sphere_hit_t_a_1div live in rt_sphere_hit.h
 RT_DEV bool sphere_hit_t(V3 o, V3 d, float radius, float t0, float t1, float& t_out) {
   return sphere_hit_t_a(o, d, vdot(d, d), radius, t0, t1, t_out);
 }

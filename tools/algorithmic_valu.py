@@ -30,7 +30,9 @@ built from the same assembly:
               scatter: in_unit_sphere accepts with p = pi / 6, 3 draws per try -> 5.73 draws -> 1.43 blocks (vec3.rs:19-26);
               camera:  2 draws (lib.rs:368-369) + 2 per in_unit_disc try (p = pi / 4) + 1 (camera.rs:55) -> 5.55 draws -> 1.39 blocks.
 The box step is unrolled twice in every kernel: c_box = region / 2 (exact: no lane-dependent branch inside a step).  c_prim is the
-static Sphere::hit region (both roots).  Nothing here needs a GPU.
+static Sphere::hit region (both roots) -- except in the lean kernel, whose sphere pass divides once per lane (rt_sphere_hit.h,
+sphere_hit_t_a_1div): there the instructions of the slow arm, the second division that only a lane with a first root below t_near
+runs, are left out of c_prim (`slow_arm_valu`).  Nothing here needs a GPU.
 """
 import argparse
 import collections
@@ -48,7 +50,7 @@ FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-
 
 # kernel (mangled-name prefix, demangled for the report) -> regions: name -> (file, first-line anchor, which occurrence, end anchor or +n lines, divisor)
 KERNELS = {
-    "render_lean_pool": ("_ZN3rtg16render_lean_poolILb1ELb0ELb1ELb0E", "rtg::render_lean_pool<true, false, true, false>", {
+    "render_lean_pool": ("_ZN3rtg16render_lean_poolILb1ELb0ELb1ELb0ELb0E", "rtg::render_lean_pool<true, false, true, false, false>", {
         "box": ("rt_pool.h", "        RT_BOX_STEP();", 0, "        RT_BOX_STEP();  // lanes that left", 2),
         "prim": ("rt_pool.h", "      if (op == OP_SPHERE) {  // Sphere::hit", 0, "      if (COUNT) t_sph += RT_TICK", 1),
         "shade": ("rt_pool.h", "      while (s_count >= 64u", 0, "      // (2b) END pass", 1),
@@ -108,13 +110,17 @@ def parse_kernel(lines, prefix):
     return out
 
 
-def region_cost(instrs, fname, a, b, others=()):
+def region_cost(instrs, fname, a, b, others=(), detached=None):
     """`others`: (file, first line, last line) of the kernel's other regions.  The compiler may lay a region's blocks out AROUND
     another region's cluster (the lean kernel's sphere pass around the box run, since its two arms are two `if`s: the pass's
     tail blocks stand in front of the run, its head behind it, and the inlined Sphere::hit behind the last instruction of the
     region's own lines).  First-to-last would then count the nested cluster and miss the helper code.  Such a cluster is counted
     as its pieces: the nested cluster and the instructions of the kernel file's other lines (loop control) are left out, and the
-    header-attributed instructions directly behind the last piece are taken in.  A cluster with nothing nested is counted as ever."""
+    header-attributed instructions directly behind the last piece are taken in.  A cluster with nothing nested is counted as ever
+    `detached` names a header whose inlined code belongs to the region wherever it stands (the lean kernel's sphere pass: its
+    head -- the op compare, the geometry load, the Translate subtraction -- and the inlined rt_sphere_hit.h stand at the end of the
+    kernel, its tail blocks in front of the box run): the block around that header's instructions -- backwards over header and
+    helper lines and the two lines in front of the region, forwards to the header's last instruction -- is added to the cluster."""
     idx = [i for i, (_, (f, ln)) in enumerate(instrs) if f == fname and a <= ln <= b]
     if not idx:
         return None
@@ -140,6 +146,13 @@ def region_cost(instrs, fname, a, b, others=()):
                     and (ins[1][0] != fname or a <= ins[1][1] <= b)]
         else:
             span = instrs[f:l + 1]
+        if detached:
+            di = [i for i, (_, (df, _)) in enumerate(instrs) if df == detached]
+            if di and not (f <= di[0] and di[-1] <= l):
+                d0 = di[0]
+                while d0 - 1 > l and (instrs[d0 - 1][1][0] != fname or a - 2 <= instrs[d0 - 1][1][1] <= b or instrs[d0 - 1][1][1] < 700):
+                    d0 -= 1
+                span = span + instrs[d0:di[-1] + 1]
         valu = sum(1 for op, _ in span if op.startswith("v_"))
         if best is None or valu > best["valu"]:
             best = {"valu": valu, "instructions": len(span), "special_rate": sum(1 for op, _ in span if re.match(r"v_(rcp|sqrt|rsq|mad_u64|mul_hi|mul_lo|div_)", op))}
@@ -149,7 +162,7 @@ def region_cost(instrs, fname, a, b, others=()):
     return best
 
 
-ARITH_FILES = ("rt_device.h", "rt_trace.h", "rt_libm.h")
+ARITH_FILES = ("rt_device.h", "rt_trace.h", "rt_sphere_hit.h", "rt_libm.h")
 PHILOX_LINES = ("rt_device.h", 71, 96)   # SampleRng::refill
 E_BLOCKS = {"shade": (3.0 / (3.14159265358979 / 6.0)) / 4.0, "cam": (2.0 + 2.0 / (3.14159265358979 / 4.0) + 1.0) / 4.0}
 
@@ -188,7 +201,7 @@ def main():
         for name, (fname, begin, _, end, div) in regions.items():
             a, b = find_lines(os.path.join(CSRC, fname), begin, end)
             others = [(of,) + find_lines(os.path.join(CSRC, of), ob_, oe_) for on, (of, ob_, _, oe_, _) in regions.items() if on != name]
-            c = region_cost(instrs, fname, a, b, others)
+            c = region_cost(instrs, fname, a, b, others, detached=("rt_sphere_hit.h" if key == "render_lean_pool" and name == "prim" else None))
             if c is None:
                 raise SystemExit("%s: no instruction for %s:%d-%d" % (pretty, fname, a, b))
             c.update({"file": fname, "lines": [a, b], "per_operation": c["valu"] / float(div)})
@@ -201,6 +214,10 @@ def main():
                     diel = (d0, d1)
                 c["lane_model"] = lane_model(instrs, fname, a, b, name, diel)
                 c["per_operation"] = c["lane_model"]["per_operation"]
+            if key == "render_lean_pool" and name == "prim":
+                sa, sb = find_lines(os.path.join(CSRC, "rt_sphere_hit.h"), "    if (first && !(q >= t1)) {", "  return false;")
+                slow = sum(1 for op, (f, ln) in instrs if op.startswith("v_") and f == "rt_sphere_hit.h" and sa < ln <= sb)   # (the branch's own compare stays)
+                c.update({"slow_arm_valu": slow, "slow_arm_lines": [sa + 1, sb], "per_operation": (c["valu"] - slow) / float(div)})
             k["regions"][name] = c
             k["c_" + name] = c["per_operation"]
         res["kernels"][key] = k
