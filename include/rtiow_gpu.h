@@ -302,6 +302,45 @@ typedef struct rtg_features {
  *     plane: uploaded when that one is, so untouched pixels survive, and copied back.  rtg_debug_samples returns
  *     RTG_ERR_INVALID. */
 
+#define RTG_FLAG_BACKGROUND 1024u /* out ends with a background block: what a ray that leaves the scene sees (below) */
+
+/* A background.  Without the flag a path whose ray misses everything is black (lib.rs:100), so an open scene is lit only by
+ * wrapping it in an emitting dome (FlipNormals(Sphere{10000, DiffuseLight})), which costs every ray a sphere test and makes
+ * every Bvh root box as wide as the dome.  RTG_FLAG_BACKGROUND needs no other flag and combines freely with PARTIAL, RESUME,
+ * SUM_SQUARES, SAMPLE_COUNTS, RETIRE, DENOISE, FEATURES, DENOISE_ERROR and COUNTERS (all of which act on sums the render
+ * produced).  `out` then grows at its very end by a 64-byte background block (rtg_background): it starts at the first even word
+ * (8-byte aligned) behind everything the call's other flags put in the frame, behind the error plane when there is one; without
+ * other flags at word 3 * nx * ny rounded up to even.  No other offset moves.  Compute it in 64 bits.
+ * When hit_top (lib.rs:33) returns None for the ray (o, d) of a path with running `accum` and `strength`, the sample's colour is
+ *   accum + strength * B(d)
+ * -- what lib.rs:76 followed by scatter() == None gives for a light of emission B -- instead of lib.rs:100's black.  strength
+ * is (1, 1, 1) for the camera ray.  Float32, every operation rounded on its own, no contraction:
+ *   mode 0:  B = bottom;
+ *   mode 1:  len = sqrt((dx * dx + dy * dy) + dz * dz);  uy = dy / len;  t = 0.5f * (uy + 1.0f);
+ *            B_c = (1.0f - t) * bottom_c + t * top_c     (the book's sky: bottom (1, 1, 1), top (0.5, 0.7, 1.0)).
+ * rtiow-rust_amd/background.py sky() is this definition in numpy.  The colours are used as given, like a DiffuseLight's: NaN
+ * and infinity propagate.  No RNG draw is made, and the bounce cap is unchanged: a miss ends the path.
+ *   - A constant background equals the dome: the frame of a world under mode 0 is bit for bit the frame of that world with
+ *     FlipNormals(Sphere{10000, DiffuseLight(bottom, 1.0)}) appended (for rays that end inside that sphere).
+ *   - Every render kernel honours the flag, the pool-2 kernel included (its "a miss is booked first" pass reads the missed ray
+ *     and the strength back from the path's slot).
+ *   - rtg_stats and its counters are those of the same scene without the flag: the walk is identical, only the booked colour
+ *     differs.  Feature planes are unchanged: a miss still gives seven +0.
+ *   - The block is in-only: the library never writes it.
+ *   - RTG_ERR_INVALID, nothing written or enqueued: mode > 1, reserved_in != 0.
+ *   - rtg_par_cast reads the block from the host frame.  rtg_par_cast_device reads the in-fields back on `hip_stream` in the
+ *     copy-and-wait of the other blocks' read-backs; a call that has none of those gains one synchronisation, made before its
+ *     first kernel.  rtg_par_cast_multi accepts the flag with and without scene option "multi_planes": every rank gets the
+ *     same host block, and the collective still moves only the planes.  rtg_debug_samples returns RTG_ERR_INVALID.
+ *   - Without the flag every call is bit for bit what it is without this section. */
+typedef struct rtg_background {
+  uint32_t mode;         /* in: 0 = constant (bottom), 1 = gradient along world +y */
+  uint32_t reserved_in;  /* in: must be 0 */
+  float bottom[3];       /* in */
+  float top[3];          /* in: read only in mode 1 */
+  uint32_t reserved[8];  /* never written */
+} rtg_background;
+
 typedef struct rtg_stats {
   uint32_t struct_size; /* = sizeof(rtg_stats)                                                */
   float kernel_ms;      /* HIP-event time of the render kernel on its stream                  */

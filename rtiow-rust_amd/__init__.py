@@ -7,6 +7,7 @@ Layout:
   noise.py     per-pixel standard errors from the sum / sum-of-squares planes (RTG_FLAG_SUM_SQUARES)
   denoise.py   the numpy definition of the RTG_FLAG_DENOISE filter (mean_var, nlm, and nlm_guided under RTG_FLAG_FEATURES)
   features.py  the numpy definition of the RTG_FLAG_FEATURES rays (subpixel_rays) and of the planes' fold
+  background.py the numpy definition of the RTG_FLAG_BACKGROUND colour (sky: constant, or the book's gradient)
   scenes.py    the reference's scene builders (src/lib.rs, src/main.rs, benches/scene.rs)
   small_rng.py SmallRng (Pcg64Mcg) emulation used ONLY for host-side scene construction
   host/        C++ mirror of the crate surface over the C ABI (rtiow.hpp)
@@ -18,7 +19,7 @@ There is NO CPU fallback: load() raises if the HIP library is missing.
 """
 import os
 
-from . import capi, denoise, features, noise, ppm, scenes, small_rng  # noqa: F401  (parallel imports torch: import it explicitly)
+from . import background, capi, denoise, features, noise, ppm, scenes, small_rng  # noqa: F401  (parallel imports torch: import it explicitly)
 from .capi import Backend, Camera, Params, Stats, RtError, make_params  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -33,6 +33,7 @@ DENOISE_MAX_PATCH = 3
 FLAG_FEATURES = 256      # the framebuffer ends with a Features block and the first-hit albedo / normal / depth planes
 FLAG_DENOISE_ERROR = 512  # (needs FLAG_DENOISE) the framebuffer ends with the error plane: the variance of every filtered pixel
 FEATURES_MAX_GRID = 4
+FLAG_BACKGROUND = 1024    # the framebuffer ends with a Background block: what a ray that leaves the scene sees
 
 
 class Camera(C.Structure):
@@ -131,6 +132,45 @@ def make_features(features=None, **fields):
     return f
 
 
+class Background(C.Structure):
+    """include/rtiow_gpu.h rtg_background: the block at the very end of an RTG_FLAG_BACKGROUND frame (64 bytes).  The caller sets
+    mode (0 = constant `bottom`, 1 = gradient from `bottom` to `top` along world +y) and the colours; the library never writes
+    the block."""
+    _fields_ = [("mode", C.c_uint32), ("reserved_in", C.c_uint32), ("bottom", C.c_float * 3), ("top", C.c_float * 3),
+                ("reserved", C.c_uint32 * 8)]
+    OUT_FIELDS = ()
+    OUT_OFFSET = 32   # bytes: the in-fields end here
+
+    def as_dict(self):
+        """The in-fields (the block has no out-fields)."""
+        return {"mode": self.mode, "bottom": tuple(self.bottom), "top": tuple(self.top)}
+
+
+def make_background(background):
+    """A Background with the in-fields set: from a Background (copied), a colour (r, g, b) -- the constant background -- or a
+    dict of bottom / top (/ mode): with `top` the gradient from bottom to top along world +y (background.sky), without it the
+    constant background `bottom`."""
+    g = Background()
+    if isinstance(background, Background):
+        C.memmove(C.addressof(g), C.addressof(background), C.sizeof(Background))
+        return g
+    if isinstance(background, dict):
+        unknown = set(background) - {"bottom", "top", "mode"}
+        if unknown or "bottom" not in background:
+            raise ValueError("background=: a dict of bottom / top / mode, with bottom (unknown: %s)" % sorted(unknown))
+        top = background.get("top")
+        g.mode = int(background.get("mode", 0 if top is None else 1))
+        if g.mode == 1 and top is None:
+            raise ValueError("background=: mode 1 (the gradient) needs top")
+        g.bottom = _f3(background["bottom"])
+        g.top = _f3(top if top is not None else (0.0, 0.0, 0.0))
+        return g
+    if background is None or isinstance(background, bool) or len(background) != 3:
+        raise ValueError("background= must be a colour (r, g, b), a dict of bottom / top, or a Background")
+    g.bottom = _f3(background)
+    return g
+
+
 def _given(x):
     """An optional part of a call or of a frame was asked for: anything but None and False."""
     return x is not None and x is not False
@@ -142,17 +182,19 @@ class FrameLayout:
     squares) start at word 0; behind them, each only with its flag: the count plane (`counts`, n = nx * ny words), the Retire
     block (`retire`), the Denoise block (`denoise`) and its output plane (`denoised`, 3n), the Features block (`features`) and
     the `albedo` (3n), `normal` (3n) and `depth` (n) planes, and at the very end, on an even word, the `error` plane (3n;
-    RTG_FLAG_DENOISE_ERROR, needs denoise).  A block is 16 words and starts on an even word.  retire implies
+    RTG_FLAG_DENOISE_ERROR, needs denoise) and, behind everything else, the Background block (`background`;
+    RTG_FLAG_BACKGROUND).  A block is 16 words and starts on an even word.  retire implies
     counts and squares, denoise implies squares (the library refuses a call without them).  The offset of a part the frame
     does not have is None; `words` is the frame's length.  Plain Python integers: exact for frames beyond 2^31 bytes."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=False, features=False, error=False):
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=False, features=False, error=False,
+                 background=False):
         if error and not denoise:
             raise ValueError("error=True needs denoise= (the filter writes the error plane)")
         n = self.n = nx * ny
         self.nx, self.ny, self.squares = nx, ny, bool(squares or retire or denoise)
         self.counts = self.retire = self.denoise = self.denoised = self.features = self.albedo = self.normal = self.depth = None
-        self.error = None
+        self.error = self.background = None
         w = (6 if self.squares else 3) * n
         if counts or retire:
             self.counts, w = w, w + n
@@ -171,6 +213,9 @@ class FrameLayout:
         if error:
             self.error = (w + 1) & ~1
             w = self.error + 3 * n
+        if background:
+            self.background = (w + 1) & ~1
+            w = self.background + 16
         self.words = w
 
 
@@ -222,8 +267,9 @@ class Stats(C.Structure):
 
 def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_w=0, tile_h=0, rank=0,
                 nranks=1, flags=0, sample_begin=0, partial=False, resume=False, squares=False, counts=False, retire=False,
-                denoise=False, features=False, error=False):
-    """`error`: RTG_FLAG_DENOISE_ERROR, the error plane at the framebuffer's very end (needs denoise).
+                denoise=False, features=False, error=False, background=False):
+    """`background`: RTG_FLAG_BACKGROUND, the background block at the framebuffer's very end.
+    `error`: RTG_FLAG_DENOISE_ERROR, the error plane at the framebuffer's very end (needs denoise).
     `features`: RTG_FLAG_FEATURES, the features block and the albedo / normal / depth planes at the framebuffer's end.
     `partial` / `resume` / `sample_begin`: one slice of a progressive frame (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
     RTG_FLAG_RESUME); `squares`: RTG_FLAG_SUM_SQUARES, the framebuffer's second plane; `counts`: RTG_FLAG_SAMPLE_COUNTS,
@@ -231,7 +277,7 @@ def make_params(nx, ny, ns, seed=0xDEADBEEF, max_bounces=50, t_near=0.001, tile_
     RTG_FLAG_DENOISE, the denoise block and the output plane at the framebuffer's end."""
     flags |= (FLAG_DENOISE if denoise else 0) | (FLAG_FEATURES if features else 0) | (FLAG_DENOISE_ERROR if error else 0)
     flags |= (FLAG_PARTIAL if partial else 0) | (FLAG_RESUME if resume else 0) | (FLAG_SUM_SQUARES if squares else 0)
-    flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0)
+    flags |= (FLAG_SAMPLE_COUNTS if counts else 0) | (FLAG_RETIRE if retire else 0) | (FLAG_BACKGROUND if background else 0)
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.nx, p.ny, p.ns = nx, ny, ns
@@ -276,7 +322,8 @@ def _resumes(kw):
 
 
 _FLAG_OF = {"squares": ("squares=True", "SUM_SQUARES"), "counts": ("counts=", "SAMPLE_COUNTS"), "retire": ("retire=", "RETIRE"),
-            "denoise": ("denoise=", "DENOISE"), "features": ("features=", "FEATURES"), "error": ("error=True", "DENOISE_ERROR")}
+            "denoise": ("denoise=", "DENOISE"), "features": ("features=", "FEATURES"), "error": ("error=True", "DENOISE_ERROR"),
+            "background": ("background=", "BACKGROUND")}
 
 
 def _supported(be, part):
@@ -292,10 +339,12 @@ class Frame:
     ([ny, nx, 3], or [2, ny, nx, 3] with squares), `counts` (uint32 [ny, nx]), `retire`, `denoise`, `features` (the blocks),
     `denoised`, `albedo`, `normal`, `error` (float32 [ny, nx, 3]) and `depth` (float32 [ny, nx]) -- None when the frame has no
     such part.  denoise / features: a block, a dict or True (make_denoise / make_features), whose in-fields the block gets.
-    error=True (needs denoise): the error plane of RTG_FLAG_DENOISE_ERROR at the frame's end."""
+    error=True (needs denoise): the error plane of RTG_FLAG_DENOISE_ERROR at the frame's end.
+    background= (a colour, a dict of bottom / top, or a Background: make_background): the `background` block of
+    RTG_FLAG_BACKGROUND behind everything else."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
-        lay = self.layout = FrameLayout(nx, ny, squares, counts, retire, _given(denoise), _given(features), bool(error))
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False, background=None):
+        lay = self.layout = FrameLayout(nx, ny, squares, counts, retire, _given(denoise), _given(features), bool(error), _given(background))
         self.nx, self.ny, self.squares = nx, ny, lay.squares
         self.buf = np.zeros(lay.words, dtype=np.float32)
 
@@ -310,21 +359,26 @@ class Frame:
         self.depth = plane(lay.depth, ny, nx)
         self.error = plane(lay.error, ny, nx, 3)
         self.retire, self.denoise, self.features = block(Retire, lay.retire), block(Denoise, lay.denoise), block(Features, lay.features)
+        self.background = block(Background, lay.background)
+        if self.background is not None and background is not True:
+            self.set_in(make_background(background))
         if self.denoise is not None:
             self.set_in(make_denoise(denoise))
         if self.features is not None:
             self.set_in(make_features(features))
 
     def flags(self):
-        """make_params keywords of the parts the frame has ("error" only when the frame has an error plane)."""
+        """make_params keywords of the parts the frame has ("error" / "background" only when the frame has that part)."""
         on = {"squares": self.squares, "counts": self.counts is not None, "retire": self.retire is not None,
               "denoise": self.denoise is not None, "features": self.features is not None}
         if self.error is not None:
             on["error"] = True
+        if self.background is not None:
+            on["background"] = True
         return on
 
     def set_in(self, block):
-        """Write the in-fields of `block` (a Retire, Denoise or Features) to the frame's block of that class; the out-fields,
+        """Write the in-fields of `block` (a Retire, Denoise, Features or Background) to the frame's block of that class; the out-fields,
         which only the library writes, stay."""
         C.memmove(C.addressof(getattr(self, type(block).__name__.lower())), C.addressof(block), block.OUT_OFFSET)
 
@@ -352,10 +406,10 @@ class CountsFrame(Frame):
     RTG_FLAG_RETIRE block.  par_cast(out=frame.planes, counts=frame.counts[, retire=frame.retire]) renders in place, without
     copies, as par_cast(out=frame) does."""
 
-    def __init__(self, nx, ny, squares=False, retire=False):
+    def __init__(self, nx, ny, squares=False, retire=False, background=None):
         if retire and not squares:
             raise ValueError("a retire frame has two float planes: squares=True")
-        super().__init__(nx, ny, squares, True, retire)
+        super().__init__(nx, ny, squares, True, retire, background=background)
 
 
 class DenoiseFrame(Frame):
@@ -363,8 +417,8 @@ class DenoiseFrame(Frame):
     Retire block with retire=True (implies counts), then the Denoise block and the output plane.  par_cast(out=frame,
     denoise=...) renders in place."""
 
-    def __init__(self, nx, ny, counts=False, retire=False, denoise=None, error=False):
-        super().__init__(nx, ny, True, counts, retire, denoise if _given(denoise) else True, None, error)
+    def __init__(self, nx, ny, counts=False, retire=False, denoise=None, error=False, background=None):
+        super().__init__(nx, ny, True, counts, retire, denoise if _given(denoise) else True, None, error, background)
 
 
 class FeaturesFrame(Frame):
@@ -373,8 +427,8 @@ class FeaturesFrame(Frame):
     True; implies squares) -- then the Features block and the albedo, normal and depth planes.  par_cast(out=frame,
     features=True) renders in place."""
 
-    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
-        super().__init__(nx, ny, squares, counts, retire, denoise, features if _given(features) else True, error)
+    def __init__(self, nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False, background=None):
+        super().__init__(nx, ny, squares, counts, retire, denoise, features if _given(features) else True, error, background)
 
 
 def features_frame(nx, ny, squares=False, counts=False, retire=False, denoise=None, features=None, error=False):
@@ -430,14 +484,19 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
     caller's is written.
     exact (Scene.par_cast): beside a Frame, squares= / denoise= / features= must say what the frame holds, and it brings its
     own counts and retire.  Otherwise (par_cast_multi) they may say less, and retire= a Retire sets the block's in-fields.
-    forward (par_cast_multi): plain flags beside a plain array (counts=True, ...) go to the library as they are."""
+    forward (par_cast_multi): plain flags beside a plain array (counts=True, ...) go to the library as they are.
+    kw["background"] (RTG_FLAG_BACKGROUND): a colour, a dict of bottom / top or a Background (make_background), written to the
+    frame's block; True beside a Frame that has the block: the block as it stands.  Beside an array the call goes through a
+    staging frame and still returns the array."""
     kw = dict(kw)
     squares = kw.pop("squares", None)
     error = kw.pop("error", None)   # (RTG_FLAG_DENOISE_ERROR: True, or None / False)
+    background = kw.pop("background", None)
     has_rt, has_dn, has_ft, has_er = _given(retire), _given(denoise), _given(features), _given(error)
+    has_bg = _given(background)
     in_place = isinstance(out, Frame)
     f = None
-    plain = forward and not (in_place or isinstance(counts, np.ndarray) or isinstance(retire, Retire)
+    plain = forward and not (in_place or isinstance(counts, np.ndarray) or isinstance(retire, Retire) or has_bg
                              or isinstance(denoise, (dict, Denoise)) or isinstance(features, (dict, Features)))
     if plain:   # (the library's to answer)
         flags, parts = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features}, ()
@@ -448,7 +507,8 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
             raise ValueError("error=True needs denoise= (the filter writes the error plane)")
         if has_dn and not squares and (exact or not in_place):
             raise ValueError("denoise= needs squares=True (the filter reads both planes)")
-        blocks = [make(x) for x, make in ((denoise, make_denoise), (features, make_features)) if _given(x) and x is not True]
+        blocks = [make(x) for x, make in ((denoise, make_denoise), (features, make_features), (background, make_background))
+                  if _given(x) and x is not True]
         if in_place:
             f, name = out, type(out).__name__
             if (f.nx, f.ny) != (nx, ny):
@@ -464,6 +524,8 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
                 raise ValueError("out= a %s: squares= / denoise= / features= must say what the frame holds" % name)
             if (has_er and f.error is None) or (exact and not has_er and f.error is not None):
                 raise ValueError("out= a %s: error= must say whether the frame has an error plane" % name)
+            if has_bg and f.background is None:
+                raise ValueError("background=: out= a %s has no background block (make the frame with background=)" % name)
             if isinstance(retire, Retire):
                 blocks.append(retire)
             flags = f.flags()
@@ -477,6 +539,10 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
             flags = {"squares": bool(squares), "counts": counts is not None, "retire": has_rt, "denoise": has_dn, "features": has_ft}
             if has_er:
                 flags["error"] = True
+            if has_bg:
+                if background is True:
+                    raise ValueError("background=True needs out= a frame that has the block")
+                flags["background"] = True
         parts = sorted((part for part, on in flags.items() if on), key=lambda part: part != "error")   # (the newest flag first)
     for part in parts:
         supported(part)
@@ -484,11 +550,15 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
         for block in blocks:
             f.set_in(block)
         ret, buf = f, f.buf
-    elif (has_dn or has_ft) and not plain:
-        f = (FeaturesFrame(nx, ny, squares, counts is not None, has_rt, denoise if has_dn else None, features, has_er) if has_ft else
-             DenoiseFrame(nx, ny, counts is not None, has_rt, denoise, has_er))
+    elif (has_dn or has_ft or has_bg) and not plain:
+        bg = background if has_bg else None
+        f = (FeaturesFrame(nx, ny, squares, counts is not None, has_rt, denoise if has_dn else None, features, has_er, bg) if has_ft else
+             DenoiseFrame(nx, ny, counts is not None, has_rt, denoise, has_er, bg) if has_dn else
+             Frame(nx, ny, squares, counts is not None, has_rt, background=bg))
+        if not (has_dn or has_ft):   # (a background alone changes no plane: the caller gets the array)
+            out = _host_frame(out, nx, ny, squares, kw)
         f.copy_in(None if out is None else _host_frame(out, nx, ny, squares, kw), counts, retire if has_rt else None)
-        ret, buf = f, f.buf
+        ret, buf = f if has_dn or has_ft else out, f.buf
     else:
         ret = out = buf = _host_frame(out, nx, ny, squares, kw)
         if counts is not None and not plain:   # in place when `out` and `counts` are one CountsFrame's views
@@ -501,27 +571,31 @@ def _render(supported, call, nx, ny, ns, seed, stats, out, counters, counts, ret
 
 
 def _adaptive_host(cast, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw,
-                   error=False):
+                   error=False, background=None):
     """The host-frame loop of Scene.adaptive and Backend.adaptive_multi: `cast(ns, **keywords)` is the par_cast of either
     (camera and frame size bound); denoise / features: a checked Denoise / Features, or None; error: the frame has the error
-    plane of RTG_FLAG_DENOISE_ERROR and the rule is noise.retire_filtered on it."""
+    plane of RTG_FLAG_DENOISE_ERROR and the rule is noise.retire_filtered on it; background: a checked Background (the frame
+    ends with the block of RTG_FLAG_BACKGROUND and every slice renders with it), or None."""
     if features is not None:
-        f = FeaturesFrame(nx, ny, True, True, False, denoise, None, error) if out is None else out
+        f = FeaturesFrame(nx, ny, True, True, False, denoise, None, error, background) if out is None else out
         what = "features=: out= must be a FeaturesFrame(nx, ny, squares=True, counts=True, denoise=...)"
     elif denoise is not None:
-        f = DenoiseFrame(nx, ny, True, error=error) if out is None else out
+        f = DenoiseFrame(nx, ny, True, error=error, background=background) if out is None else out
         what = "denoise=: out= must be a DenoiseFrame(nx, ny, counts=True)"
     else:
-        f = CountsFrame(nx, ny, True) if out is None else out
+        f = CountsFrame(nx, ny, True, background=background) if out is None else out
         what = "out= must be a CountsFrame(nx, ny, squares=True)"
     on = {"denoise": True if denoise is not None else None, "features": True if features is not None else None}
     want = {"squares": True, "counts": True, "retire": False, "denoise": denoise is not None, "features": features is not None}
     if error:
         on["error"] = want["error"] = True
         what += " with error=True"
+    if background is not None:
+        on["background"] = want["background"] = True
+        what += " with background="
     if not isinstance(f, Frame) or (f.nx, f.ny) != (nx, ny) or f.flags() != want:
         raise ValueError(what)
-    for block in (features, denoise):
+    for block in (features, denoise, background):
         if block is not None:
             f.set_in(block)
     more = () if features is None else (f,)
@@ -701,6 +775,8 @@ class Backend:
         [2, ny, nx, 3] array with squares=True as before; and counts= an array, retire= a Retire, denoise= / features= a
         block or a dict beside an array `out` go through a staging frame as in Scene.par_cast (a denoise / features call
         returns that frame).  Plain flags beside a plain array (counts=True, ...) are forwarded to the library as they are.
+        background= (RTG_FLAG_BACKGROUND; a colour, a dict of bottom / top or a Background): as in Scene.par_cast, with and
+        without "multi_planes" -- every handle renders with the same block.
         stats=True returns (frame, rtg_stats as a dict), with the instrumented counters unless counters=False."""
         kw = dict(kw)
         counts, retire, denoise, features = (kw.pop(k, None) for k in ("counts", "retire", "denoise", "features"))
@@ -720,7 +796,8 @@ class Backend:
         """Scene.adaptive's host-frame loop over several handles (scene option "multi_planes" on one of them): every slice is
         one par_cast_multi call, the retire rule is noise.retire on the host, and the loop yields the same tuples --
         (counts, preview, stderr), then the filtered frame with denoise=, then the FeaturesFrame with features=.
-        filtered_error=True (needs denoise=): as in Scene.adaptive -- the rule is noise.retire_filtered on the error plane."""
+        filtered_error=True (needs denoise=): as in Scene.adaptive -- the rule is noise.retire_filtered on the error plane.
+        background= (RTG_FLAG_BACKGROUND): as in Scene.adaptive."""
         if step < 1:
             raise ValueError("step must be >= 1")
         if not 0 <= radius <= RETIRE_MAX_RADIUS:
@@ -733,8 +810,13 @@ class Backend:
             raise ValueError("filtered_error=True needs denoise= (the filter writes the error plane)")
         features = make_features(features) if _given(features) else None
         denoise = make_denoise(denoise) if _given(denoise) else None
+        background = kw.pop("background", None)
+        if _given(background):
+            _supported(self, "background")
+        background = make_background(background) if _given(background) else None
         yield from _adaptive_host(lambda n, **k: self.par_cast_multi(scenes, camera, nx, ny, n, **k), nx, ny, ns, step,
-                                  target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error))
+                                  target_se, min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error),
+                                  background)
 
     def multi_reset(self, rccl_library=None):
         """rtg_multi_reset: drop the cached RCCL communicators, unload librccl, choose the library to load next (None =
@@ -1000,6 +1082,10 @@ class Scene:
         error=True (RTG_FLAG_DENOISE_ERROR; needs denoise=): the frame the call returns also has the `error` view, the variance
         of every filtered pixel (denoise.nlm_error / nlm_guided_error), +inf where a pixel was passed through; with retire= the
         rule is noise.retire_filtered on that plane.  out= a frame made with error=True is rendered in place.
+        background= (RTG_FLAG_BACKGROUND): what a ray that leaves the scene sees instead of black -- a colour (r, g, b), the
+        constant background, or a dict of bottom / top, the gradient along world +y (background.sky; make_background).  It
+        changes no plane's place: beside an array the call still returns the array.  out= a frame made with background= is
+        rendered in place (background=True: its block as it stands).
         stats=True returns (out, rtg_stats as a dict), with the instrumented counters unless counters=False."""
         def call(p, buf):
             st = Stats.new()
@@ -1010,7 +1096,8 @@ class Scene:
                        stats if counters is None else counters, counts, retire, denoise, features, kw, exact=True)
 
     def par_cast_device(self, camera, params, d_out_ptr, stream=None, want_stats=False, sample_begin=None, partial=None,
-                        resume=None, squares=None, counts=None, retire=None, denoise=None, features=None, error=None):
+                        resume=None, squares=None, counts=None, retire=None, denoise=None, features=None, error=None,
+                        background=None):
         """rtg_par_cast_device.  sample_begin / partial / resume / squares, when given, override those of `params` (a copy).
         With RTG_FLAG_SUM_SQUARES `d_out_ptr` must hold 2 * nx * ny * 3 floats.
         counts= (RTG_FLAG_SAMPLE_COUNTS): a uint32 [ny, nx] array -- numpy (copied host to device) or a device tensor
@@ -1026,15 +1113,21 @@ class Scene:
         Features, written to the block before the call and filled from it afterwards (the call then synchronises `stream`).
         `d_out_ptr` then holds features_frame_bytes(nx, ny, squares, counts, retire, denoise) for the flags the call ends up with.
         error= (RTG_FLAG_DENOISE_ERROR; needs the denoise part): True, the flag -- `d_out_ptr` then ends with the error plane
-        (FrameLayout(..., error=True).words words in all)."""
-        over = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features, "error": error}
+        (FrameLayout(..., error=True).words words in all).
+        background= (RTG_FLAG_BACKGROUND): True, the flag alone (the caller has written the block on the device); a colour, a
+        dict of bottom / top or a Background (make_background), written to the block before the call.  `d_out_ptr` then ends
+        with the 64-byte block (FrameLayout(..., background=True).words words in all)."""
+        if _given(background) and background is not True:
+            background = make_background(background)
+        over = {"squares": squares, "counts": counts, "retire": retire, "denoise": denoise, "features": features, "error": error,
+                "background": background}
         bits = {"squares": FLAG_SUM_SQUARES, "counts": FLAG_SAMPLE_COUNTS, "retire": FLAG_RETIRE, "denoise": FLAG_DENOISE,
-                "features": FLAG_FEATURES, "error": FLAG_DENOISE_ERROR}
+                "features": FLAG_FEATURES, "error": FLAG_DENOISE_ERROR, "background": FLAG_BACKGROUND}
         # the parts the call ends up with: those of `params` unless overridden (an array or a block turns its part on).
         # Every refusal first: a refused call has written nothing to the caller's frame
         has = {part: bool(params.flags & bits[part] if on is None else on if isinstance(on, (bool, int)) else True)
                for part, on in over.items()}
-        for part in ("error", "features", "denoise", "squares", "counts", "retire"):
+        for part in ("background", "error", "features", "denoise", "squares", "counts", "retire"):
             if has[part] if part == "squares" else _given(over[part]):
                 _supported(self.be, part)
         if has["error"] and not has["denoise"]:
@@ -1043,7 +1136,8 @@ class Scene:
         # blocks of the caller's: (block, byte offset, bytes written before the call); all of a block is read back after it
         blocks = [(over[part], 4 * at, n) for part, at, n in (("retire", lay.retire, C.sizeof(Retire)),
                                                              ("denoise", lay.denoise, Denoise.OUT_OFFSET),
-                                                             ("features", lay.features, Features.OUT_OFFSET))
+                                                             ("features", lay.features, Features.OUT_OFFSET),
+                                                             ("background", lay.background, Background.OUT_OFFSET))
                   if isinstance(over[part], C.Structure)]
         for block, at, n in blocks:
             self._block_copy(d_out_ptr, block, stream, True, at, n)
@@ -1131,7 +1225,9 @@ class Scene:
         its FILTERED value (every one of its window) is <= target_se^2.  Host frames: `out`, when given, is a frame made with
         error=True; the loop's third item is the error plane (float32 [ny, nx, 3]: variances, +inf where unknown) instead of
         stderr.  Device frames: `out` ends with the error plane (FrameLayout(nx, ny, True, True, True, True, features,
-        True).words words); info's estimated / sum_se2 / est_rmse are those of the filtered frame."""
+        True).words words); info's estimated / sum_se2 / est_rmse are those of the filtered frame.
+        background= (RTG_FLAG_BACKGROUND; a colour, a dict of bottom / top or a Background): every slice renders with it.  Host
+        frames: `out`, when given, is a frame made with background=.  Device frames: `out` ends with the 64-byte block."""
         if step < 1:
             raise ValueError("step must be >= 1")
         if filtered_error:
@@ -1143,6 +1239,7 @@ class Scene:
         if filtered_error and not _given(denoise):
             raise ValueError("filtered_error=True needs denoise= (the filter writes the error plane)")
         features, denoise = self._loop_block("features", features, make_features), self._loop_block("denoise", denoise, make_denoise)
+        background = self._loop_block("background", kw.pop("background", None), make_background)
         if out is not None and not isinstance(out, Frame):
             _supported(self.be, "retire")
             if preview is None:
@@ -1150,16 +1247,18 @@ class Scene:
             if denoise is not None and denoised is None:
                 raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._adaptive_device(camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats,
-                                             radius, preview, stream, kw, denoise, denoised, features, bool(filtered_error))
+                                             radius, preview, stream, kw, denoise, denoised, features, bool(filtered_error), background)
             return
         yield from _adaptive_host(lambda n, **k: self.par_cast(camera, nx, ny, n, **k), nx, ny, ns, step, target_se,
-                                  min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error))
+                                  min_samples, budget_s, out, seed, stats, radius, denoise, features, kw, bool(filtered_error), background)
 
     def _adaptive_device(self, camera, nx, ny, ns, step, target_se, min_samples, budget_s, out, seed, stats, radius, preview,
-                         stream, kw, denoise=None, denoised=None, features=None, error=False):
+                         stream, kw, denoise=None, denoised=None, features=None, error=False, background=None):
         hip, hs, ok = _hip_runtime(), _stream(stream), _hip_ok
         d_out, d_pv = _device_ptr(out), _device_ptr(preview)
-        lay = FrameLayout(nx, ny, True, True, True, denoise is not None, features is not None, error)
+        lay = FrameLayout(nx, ny, True, True, True, denoise is not None, features is not None, error, background is not None)
+        if background is not None:   # (in-only: written once)
+            self._block_copy(d_out, background, stream, True, 4 * lay.background, Background.OUT_OFFSET)
         plane, counts_at = lay.n, d_out + 4 * lay.counts
         # every pixel's target count is ns; the block's in-fields are written once (the library never writes them)
         ok(hip.hipMemsetD32Async(C.c_void_p(counts_at), ns - (1 << 32) if ns >= 1 << 31 else ns, plane, hs), "hipMemsetD32Async(counts)")
@@ -1177,7 +1276,8 @@ class Scene:
             end = min(ns, done + step)
             st = self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
                                                           squares=True, counts=True, retire=True, denoise=denoise is not None,
-                                                          features=features is not None, error=error, **kw), d_out, hs,
+                                                          features=features is not None, error=error,
+                                                          background=background is not None, **kw), d_out, hs,
                                       want_stats=stats is not None)
             if features is not None and features.compute:
                 features.compute = 0
@@ -1229,10 +1329,13 @@ class Scene:
         feature planes, the later ones pass compute = 0; with denoise= the filter is the guided one (denoise.nlm_guided).  The
         loop yields one more item at the end of its tuple.  Host frames: the FeaturesFrame the slices render into (views
         `albedo`, `normal`, `depth`).  Device frames: `out` holds features_frame_bytes(nx, ny, squares, False, False, denoise)
-        and the item is the byte offset of the features block in it (the planes start 64 bytes behind it)."""
+        and the item is the byte offset of the features block in it (the planes start 64 bytes behind it).
+        background= (RTG_FLAG_BACKGROUND; a colour, a dict of bottom / top or a Background): every slice renders with it.
+        Device frames: `out` then ends with the 64-byte block (FrameLayout(..., background=True).words words in all)."""
         if step < 1:
             raise ValueError("step must be >= 1")
         features = self._loop_block("features", features, make_features)
+        background = self._loop_block("background", kw.pop("background", None), make_background)
         squares = bool(squares) or target_rmse is not None or _given(denoise)
         if squares:
             _supported(self.be, "squares")
@@ -1245,18 +1348,22 @@ class Scene:
             if denoise is not None and denoised is None:
                 raise ValueError("denoise= on a device frame needs a device buffer for the filtered frame (denoised=)")
             yield from self._progressive_device(camera, nx, ny, ns, step, seed, budget_s, out, preview, stream, squares, kw,
-                                                denoise, denoised, features)
+                                                denoise, denoised, features, background)
             return
         shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
         acc = np.zeros(shape, dtype=np.float32) if out is None else out
         frame = None   # with a block the slices render into a frame; a caller's `out` is kept up to date beside it
         if features is not None:
-            frame = FeaturesFrame(nx, ny, squares, denoise=denoise, features=features)
+            frame = FeaturesFrame(nx, ny, squares, denoise=denoise, features=features, background=background)
         elif denoise is not None:
-            frame = DenoiseFrame(nx, ny, denoise=denoise)
+            frame = DenoiseFrame(nx, ny, denoise=denoise, background=background)
+        elif background is not None:
+            frame = Frame(nx, ny, squares, background=background)
         if frame is not None:
             frame.copy_in(acc)
         on = {"denoise": True if denoise is not None else None, "features": True if features is not None else None}
+        if background is not None:
+            on["background"] = True
         more = () if features is None else (frame,)
         sums = acc[0] if squares else acc
         t0 = time.perf_counter()
@@ -1286,10 +1393,12 @@ class Scene:
                 return
 
     def _progressive_device(self, camera, nx, ny, ns, step, seed, budget_s, acc, preview, stream, squares, kw, denoise=None,
-                            denoised=None, features=None):
+                            denoised=None, features=None, background=None):
         hip, hs = _hip_runtime(), _stream(stream)
         d_acc, d_preview = C.c_void_p(_device_ptr(acc)), C.c_void_p(_device_ptr(preview))
-        lay = FrameLayout(nx, ny, squares, False, False, denoise is not None, features is not None)
+        lay = FrameLayout(nx, ny, squares, False, False, denoise is not None, features is not None, background=background is not None)
+        if background is not None:   # (in-only: written once)
+            self._block_copy(acc, background, stream, True, 4 * lay.background, Background.OUT_OFFSET)
         if denoise is not None:   # the block's in-fields are written once (the library never writes them)
             self._block_copy(acc, denoise, stream, True, 4 * lay.denoise, Denoise.OUT_OFFSET)
         more = ()
@@ -1302,7 +1411,7 @@ class Scene:
             end = min(ns, done + step)
             self.par_cast_device(camera, make_params(nx, ny, end, seed=seed, sample_begin=done, resume=True, partial=True,
                                                      squares=squares, denoise=denoise is not None, features=features is not None,
-                                                     **kw), d_acc, hs)
+                                                     background=background is not None, **kw), d_acc, hs)
             if features is not None and features.compute:
                 features.compute = 0
                 self._block_copy(acc, features, stream, True, 4 * lay.features, Features.OUT_OFFSET)

@@ -42,6 +42,26 @@ RT_DEV V3 reflect(V3 v, V3 n) { return vsub(v, smul(2.f * vdot(v, n), n)); }
 
 constexpr float F32_MAX = 3.402823466e+38f;
 
+// ---- background (include/rtiow_gpu.h RTG_FLAG_BACKGROUND) ------------------------------------------
+// What a ray that leaves the scene sees; it travels at the end of the frame parameters (rt_trace.h DevParams) and is read in
+// the miss branch alone.  mode 0 = none: a miss is black and accum is discarded (lib.rs:100), the call without the flag.
+constexpr uint32_t BG_NONE = 0u, BG_CONSTANT = 1u, BG_GRADIENT = 2u;  // (rtg_background.mode + 1)
+struct Background {
+  uint32_t mode;
+  float bottom[3], top[3];
+};
+// B(d) for the missed ray's direction d (not normalised): `bottom`, or the book's blend along world +y in the reference's
+// operation order -- rtiow-rust_amd/background.py sky() is this in numpy, bit for bit.
+RT_DEV V3 background_colour(const Background& bg, V3 d) {
+  const V3 bottom = mk(bg.bottom[0], bg.bottom[1], bg.bottom[2]);
+  if (bg.mode != BG_GRADIENT) return bottom;
+  const float uy = d.y / vlen(d);
+  const float t = 0.5f * (uy + 1.0f);
+  return vadd(smul(1.0f - t, bottom), smul(t, mk(bg.top[0], bg.top[1], bg.top[2])));
+}
+// ... and the sample colour of the path that missed: lib.rs:76 for a light of emission B(d), then scatter() == None
+RT_DEV V3 miss_colour(const Background& bg, V3 accum, V3 strength, V3 d) { return vadd(accum, vmul(strength, background_colour(bg, d))); }
+
 // ---- counter RNG ---------------------------------------------------------------------------------
 // Determinism contract: one Philox4x32-10 stream per (seed, pixel, sample, event); key =
 // seed, counter = (block, sample, pixel, event); each block hands out its 4 words in order.  event 0 =

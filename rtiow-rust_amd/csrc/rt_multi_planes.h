@@ -18,8 +18,8 @@ namespace rtg {
 // binding) computes.  Built once per call from (nx, ny, flags); it belongs to the FRAME, whichever slice of it a launch renders.
 // The float planes (one, or two with squares) start at word 0; behind them, each only with its flag: the count plane, the retire
 // block, the denoise block and its output plane (3n), the features block and the albedo (3n), normal (3n) and depth (n) planes
-// and, at the very end, the error plane (3n).  A block is BLOCK_WORDS long; blocks and the error plane start on an even word
-// (8-byte aligned).  RTG_FLAG_RETIRE implies the count plane and the squares, RTG_FLAG_DENOISE the squares (check_params refuses
+// and the error plane (3n) and, at the very end, the background block of RTG_FLAG_BACKGROUND (in-only: it never travels back).
+// A block is BLOCK_WORDS long; blocks and the error plane start on an even word (8-byte aligned).  RTG_FLAG_RETIRE implies the count plane and the squares, RTG_FLAG_DENOISE the squares (check_params refuses
 // a call without them).  A part the frame does not have is ABSENT.
 struct FrameLayout {
   static constexpr uint64_t ABSENT = ~0ull;
@@ -29,6 +29,7 @@ struct FrameLayout {
   uint64_t counts = ABSENT, retire = ABSENT, denoise = ABSENT, denoised = ABSENT;
   uint64_t features = ABSENT, albedo = ABSENT, normal = ABSENT, depth = ABSENT;
   uint64_t error = ABSENT;
+  uint64_t background = ABSENT;
   uint64_t words = 0;       // the whole frame
 
   FrameLayout(uint32_t nx, uint32_t ny, uint32_t flags)
@@ -43,6 +44,7 @@ struct FrameLayout {
       normal = albedo + 3u * n, depth = albedo + 6u * n, w = depth + n;
     }
     if (flags & RTG_FLAG_DENOISE_ERROR) error = even(w), w = error + 3u * n;
+    if (flags & RTG_FLAG_BACKGROUND) background = even(w), w = background + BLOCK_WORDS;
     words = w;
   }
   static bool has(uint64_t part) { return part != ABSENT; }
@@ -60,9 +62,9 @@ struct FrameLayout {
 };
 
 // ---- what rtg_par_cast moves around rtg_par_cast_device (and rtg_par_cast_multi's flagged frames around their ranks) ---------
-// Byte ranges [lo, hi) of a frame, ascending and disjoint, at most six
+// Byte ranges [lo, hi) of a frame, ascending and disjoint, at most seven
 struct Extents {
-  struct { uint64_t lo, hi; } e[6];
+  struct { uint64_t lo, hi; } e[7];
   int n = 0;
   void add(uint64_t lo_word, uint64_t hi_word, uint64_t lo_byte = 0, uint64_t hi_byte = 0) {
     const uint64_t lo = 4u * lo_word + lo_byte, hi = 4u * hi_word + hi_byte;
@@ -73,7 +75,8 @@ struct Extents {
 // left them.  A single rank overwrites every pixel -- unless it resumes a progressive frame (`begin` > 0), whose running sums are
 // in the frame, or renders per-pixel counts (pixels with n_p = 0 stay as they are).  Under RTG_FLAG_SAMPLE_COUNTS the count plane
 // travels with the float planes, under RTG_FLAG_RETIRE / RTG_FLAG_DENOISE their blocks (and the output plane: pixels with
-// e_p = 0 keep what it held); the error plane of RTG_FLAG_DENOISE_ERROR whenever the output plane travels.
+// e_p = 0 keep what it held); the error plane of RTG_FLAG_DENOISE_ERROR whenever the output plane travels; the background
+// block of RTG_FLAG_BACKGROUND always.
 inline Extents upload_extents(const FrameLayout& L, bool other_ranks, uint32_t begin, uint32_t features_compute) {
   Extents x;
   const bool keeps = other_ranks || begin != 0u || L.has(L.counts);
@@ -82,7 +85,8 @@ inline Extents upload_extents(const FrameLayout& L, bool other_ranks, uint32_t b
   // the features block; the planes too when the call does not trace them and the guided filter reads them -- and whenever other
   // ranks' pixels must come back as the caller left them
   if (L.has(L.features)) x.add(L.features, L.albedo + (other_ranks || (features_compute == 0u && L.has(L.denoise)) ? L.feature_planes() : 0u));
-  if (L.has(L.error) && keeps) x.add(L.error, L.words);
+  if (L.has(L.error) && keeps) x.add(L.error, L.error + L.plane());
+  if (L.has(L.background)) x.add(L.background, L.words);  // (rtg_par_cast_device reads the in-fields from the device frame)
   return x;
 }
 // ... and back afterwards: the float planes; under RTG_FLAG_RETIRE the count plane and the block's out-fields (active ..
@@ -95,7 +99,7 @@ inline Extents copy_back_extents(const FrameLayout& L, uint32_t features_compute
   if (L.has(L.retire)) x.add(L.retire, L.retire, offsetof(rtg_retire, active), offsetof(rtg_retire, reserved2));
   if (L.has(L.denoise)) x.add(L.denoise, L.in_end(), offsetof(rtg_denoise, filtered));
   if (L.has(L.features)) x.add(L.features, L.albedo + (features_compute ? L.feature_planes() : 0u), offsetof(rtg_features, traced));
-  if (L.has(L.error)) x.add(L.error, L.words);
+  if (L.has(L.error)) x.add(L.error, L.error + L.plane());
   return x;
 }
 

@@ -1155,6 +1155,11 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
                 const V3 emitted = smul(u2f(mlo.w), mk(u2f(mlo.x), u2f(mlo.y), u2f(mlo.z)));  // material.rs:120-128
                 result = vadd(accum, vmul(strength, emitted));
               }
+            } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the missed ray and the path's strength are still in the slot
+              const Background bg = load_const(&lc->P.bg);  // (loaded here, in the miss branch of a background call alone)
+              V3 strength = mk(SLOT_F(PF_STRENGTH, j), SLOT_F(PF_STRENGTH + 1, j), SLOT_F(PF_STRENGTH + 2, j));
+              if (SLOT_U(PF_BOUNCES, j) == 0u) strength = splat(1.f);  // the camera ray missed: lib.rs:63
+              result = miss_colour(bg, mk(0.f, 0.f, 0.f), strength, mk(RAY_F(PF_D, j), RAY_F(PF_D + 1, j), RAY_F(PF_D + 2, j)));
             }
             if (cm.scratch) {  // chunk mode: park the sample colour, folded in order afterwards
               float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + (LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row)));

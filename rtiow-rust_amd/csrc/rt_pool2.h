@@ -520,7 +520,12 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             if ((ent & E_NEXT) == 0u) {  // E_MISS: the path's colour is black, accum is discarded (lib.rs:100)
               const uint32_t w = LIST ? list_item_of_pixel(lc, P, x, row) : pixel_to_work(P, load_const(&lc->pm), x, row);
               float* sp = cm.scratch + 3ull * ((size_t)s * cm.pix_work + w);
-              RT_SCRATCH_STORE(sp, mk(0.f, 0.f, 0.f));
+              V3 result = mk(0.f, 0.f, 0.f);
+              if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the missed ray and the path's strength are still in the slot
+                const p2_u32x4 a1 = SL_LD4(id, PS_D), a3 = SL_LD4(id, PS_STRENGTH);
+                result = miss_colour(load_const(&lc->P.bg), result, mk(u2f(a3.x), u2f(a3.y), u2f(a3.z)), mk(u2f(a1.x), u2f(a1.y), u2f(a1.z)));
+              }
+              RT_SCRATCH_STORE(sp, result);
               if (COUNT && tr_out) {
                 uint32_t* tp = tr_out + 4ull * ((size_t)s * cm.pix_work + w);
                 tp[0] = SL_LD1(id, PS_BOUNCES), tp[1] = tr_slot[id], tp[2] = tr_slot[P2POOL + id], tp[3] = tr_slot[2u * P2POOL + id];

@@ -534,6 +534,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
                 lpt_on = s < cm.lpt_samples && bounces == cm.lpt_deep;  // phase 1 of the cost-ordered queue (rt_pool.h)
               }
             }
+          } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the miss sees the background (rt_device.h)
+            result = miss_colour(load_const(&lc->P.bg), accum, strength, sd);
           }
           if (COUNT) total_draws += rng.draws;
           if (COUNT) trd += rng.draws;

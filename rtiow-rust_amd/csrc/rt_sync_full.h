@@ -167,6 +167,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
               lpt_on = ps < cm.lpt_samples && bounces == cm.lpt_deep;
             }
           }
+        } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the miss sees the background (rt_device.h)
+          result = miss_colour(load_const(&lc->P.bg), mk(0.f, 0.f, 0.f), strength, sd);
         }
         if (COUNT) total_draws += rng.draws, tr_draws += rng.draws;
         if (ended) {

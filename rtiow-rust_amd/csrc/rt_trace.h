@@ -55,6 +55,8 @@ struct DevParams {
   float t_near;
   uint32_t seed_lo, seed_hi;
   uint32_t tile_w, tile_h, rank, nranks;
+  Background bg;  // RTG_FLAG_BACKGROUND (rt_device.h); mode BG_NONE without the flag.  Last, and read in the miss branch alone: the
+                  // passes of the pool kernels that load the frame parameters load the words they use
 };
 // derived from DevParams (make_pixmap): tiles per row and the divisors of the work-item <-> pixel maps (rt_pool.h).  Its own
 // struct in the launch constants, read field by field where a map is evaluated: inside DevParams every pass that loads the
@@ -773,6 +775,7 @@ RT_DEV V3 color(const DevScene& sc, V3 o, V3 d, float time, const DevParams& P, 
     rng.set_event(bounces + 1);
   }
   bounces_out = bounces;
+  if (P.bg.mode != BG_NONE) return miss_colour(P.bg, accum, strength, d);  // RTG_FLAG_BACKGROUND: the miss sees the background
   return mk(0.f, 0.f, 0.f);  // lib.rs:100
 }
 

@@ -257,6 +257,9 @@ struct SampleSlice {
   bool denoise = false; // RTG_FLAG_DENOISE: the framebuffer ends with an rtg_denoise block and the output plane; the filter runs before the division
   bool features = false; // RTG_FLAG_FEATURES: the framebuffer ends with an rtg_features block and the albedo / normal / depth planes
   bool error = false;   // RTG_FLAG_DENOISE_ERROR: the framebuffer ends with the error plane; the filter runs before the retire step, which reads it
+  // RTG_FLAG_BACKGROUND: the framebuffer ends with an rtg_background block whose in-fields the call reads from the frame and puts
+  // into its frame parameters (DevParams::bg).  The ranks of rtg_par_cast_multi get them from the host block instead: not set there
+  bool background = false;
   bool sliced() const { return begin != 0u || !divide; }
 };
 static SampleSlice slice_of(const rtg_params* p) {
@@ -269,6 +272,7 @@ static SampleSlice slice_of(const rtg_params* p) {
   if (p->flags & RTG_FLAG_DENOISE) sl.denoise = true;
   if (p->flags & RTG_FLAG_FEATURES) sl.features = true;
   if (p->flags & RTG_FLAG_DENOISE_ERROR) sl.error = true;
+  if (p->flags & RTG_FLAG_BACKGROUND) sl.background = true;
   return sl;
 }
 
@@ -301,12 +305,27 @@ static const char* features_refusal(const rtg_features& r, bool denoise) {
   return nullptr;
 }
 
+// RTG_FLAG_BACKGROUND: why the block's in-fields are refused (nullptr: accepted)
+static const char* background_refusal(const rtg_background& r) {
+  if (r.mode > 1u) return "RTG_FLAG_BACKGROUND: mode > 1";
+  if (r.reserved_in != 0u) return "RTG_FLAG_BACKGROUND: reserved_in != 0";
+  return nullptr;
+}
+// ... and the accepted block as the kernels read it (rt_device.h Background)
+static Background dev_background(const rtg_background& r) {
+  Background b;
+  b.mode = r.mode == 0u ? BG_CONSTANT : BG_GRADIENT;
+  for (int c = 0; c < 3; c++) b.bottom[c] = r.bottom[c], b.top[c] = r.top[c];
+  return b;
+}
+
 // The in-fields of a flagged frame's blocks, in ONE place: read (from the host frame by check_blocks, from the device frame by
 // read_blocks), checked by blocks_refusal, then handed to the launchers as an argument.
 struct FrameBlocks {
   rtg_retire retire{};
   rtg_denoise denoise{};
   rtg_features features{};
+  rtg_background background{};
 };
 // Enqueue on `stream` the read-backs of the in-fields of the blocks the slice's flags name; the caller synchronises
 static hipError_t read_blocks(const FrameLayout& L, const SampleSlice& sl, const float* d_out, hipStream_t stream, FrameBlocks* fb) {
@@ -314,6 +333,7 @@ static hipError_t read_blocks(const FrameLayout& L, const SampleSlice& sl, const
   if (sl.retire) e = hipMemcpyAsync(&fb->retire, d_out + L.retire, offsetof(rtg_retire, active), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess && sl.denoise) e = hipMemcpyAsync(&fb->denoise, d_out + L.denoise, offsetof(rtg_denoise, filtered), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess && sl.features) e = hipMemcpyAsync(&fb->features, d_out + L.features, offsetof(rtg_features, traced), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && sl.background) e = hipMemcpyAsync(&fb->background, d_out + L.background, offsetof(rtg_background, reserved), hipMemcpyDeviceToHost, stream);
   return e;
 }
 // Why a call of `nranks` ranks refuses those in-fields (nullptr: accepted)
@@ -322,6 +342,7 @@ static const char* blocks_refusal(const SampleSlice& sl, const FrameBlocks& fb, 
   if (sl.retire && (why = retire_refusal(fb.retire, nranks))) return why;
   if (sl.denoise && (why = denoise_refusal(fb.denoise, nranks))) return why;
   if (sl.features && (why = features_refusal(fb.features, sl.denoise))) return why;
+  if (sl.background && (why = background_refusal(fb.background))) return why;
   return nullptr;
 }
 
@@ -911,6 +932,7 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   if (d.tile_w % 8u || d.tile_h % 8u) return fail(RTG_ERR_INVALID, "tile_w / tile_h must be multiples of 8");
   d.nranks = p->nranks ? p->nranks : 1u;
   d.rank = p->rank;
+  d.bg = Background{BG_NONE, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // (RTG_FLAG_BACKGROUND: the entry points fill it in once they have read the block)
   if (d.rank >= d.nranks) return fail(RTG_ERR_INVALID, "rank >= nranks");
   if ((p->flags & RTG_FLAG_RESUME) && p->sample_begin > p->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   if ((p->flags & RTG_FLAG_RETIRE) && (~p->flags & (RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES)))
@@ -996,12 +1018,13 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
       return hip_fail(e_, #expr);                       \
     }                                                   \
   } while (0)
-  if ((sl.denoise || sl.features) && !sl.counts) {
-    // RTG_FLAG_DENOISE / RTG_FLAG_FEATURES without a count plane: the blocks' in-fields come back now, in one copy-and-wait, before
+  if ((sl.denoise || sl.features || sl.background) && !sl.counts) {
+    // RTG_FLAG_DENOISE / RTG_FLAG_FEATURES / RTG_FLAG_BACKGROUND without a count plane: the blocks' in-fields come back now, in one copy-and-wait, before
     // anything of the frame is enqueued and outside the timed span (a counts call reads them with its compaction result: launch_counts)
     HIP_TRY(read_blocks(L, sl, d_out, stream, &fb));
     HIP_TRY(hipStreamSynchronize(stream));
     if (const char* why = blocks_refusal(sl, fb, d.nranks)) return fail(RTG_ERR_INVALID, why);
+    if (sl.background) d.bg = dev_background(fb.background);
   }
   if (count) {
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), stream));
@@ -1061,6 +1084,7 @@ static int check_blocks(const FrameLayout& L, const SampleSlice& sl, const float
   if (sl.retire) memcpy(&fb->retire, out_rgb + L.retire, sizeof(rtg_retire));
   if (sl.denoise) memcpy(&fb->denoise, out_rgb + L.denoise, sizeof(rtg_denoise));
   if (sl.features) memcpy(&fb->features, out_rgb + L.features, sizeof(rtg_features));
+  if (sl.background) memcpy(&fb->background, out_rgb + L.background, sizeof(rtg_background));
   if (const char* why = blocks_refusal(sl, *fb, nranks)) return fail(RTG_ERR_INVALID, why);
   return RTG_OK;
 }

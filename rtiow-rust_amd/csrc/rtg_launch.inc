@@ -741,7 +741,8 @@ static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevPara
 // RTG_FLAG_PARTIAL every owned pixel with e_p > 0 ends divided by e_p.
 // The in-fields of the slice's blocks (RTG_FLAG_RETIRE / DENOISE / FEATURES) come back with that read-back (on their own when the
 // call renders nothing; a call that renders nothing and has no block does not synchronise); refused ones end the call before it
-// renders (s->cx->refusal).  The feature pass runs first, before the render.
+// renders (s->cx->refusal).  The feature pass runs first, before the render.  The background of RTG_FLAG_BACKGROUND rides with
+// them and goes into the frame parameters of the render.
 template <bool COUNT>
 static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream,
                                 const SampleSlice& sl, const FrameLayout& L) {
@@ -778,11 +779,13 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, stream);
   }
-  if (renders || sl.retire || sl.denoise || sl.features) {  // the blocks ride with the compaction result: ONE synchronisation
+  DevParams dr = d;  // the render's parameters: d with the background the frame's block names
+  if (renders || sl.retire || sl.denoise || sl.features || sl.background) {  // the blocks ride with the compaction result: ONE synchronisation
     if (e == hipSuccess) e = read_blocks(L, sl, d_out, stream, &fb);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     if ((s->cx->refusal = blocks_refusal(sl, fb, d.nranks))) return hipSuccess;
+    if (sl.background) dr.bg = dev_background(fb.background);
   }
   if (sl.features && (e = launch_features(s, cam, d, d_out, stream, L, fb.features)) != hipSuccess) return e;
   if (renders) {
@@ -791,7 +794,7 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
     if (s->verbose)
       fprintf(stderr, "[rtg] sample counts: samples [%u, %u): %u of %llu owned pixels active (list of %u work items), %llu samples\n",
               sl.begin, d.ns, h.active, (unsigned long long)owned_pixels(d), h.padded, h.samples);
-    if (h.active != 0u && (e = launch_slice<COUNT>(s, cam, d, d_out, stream, ls)) != hipSuccess) return e;
+    if (h.active != 0u && (e = launch_slice<COUNT>(s, cam, dr, d_out, stream, ls)) != hipSuccess) return e;
   }
   return launch_post_steps(s, d, d_out, stream, sl, L, fb);
 }

@@ -251,9 +251,18 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
   const size_t n_floats = (size_t)params->nx * params->ny * 3;
   const size_t bytes = n_floats * sizeof(float);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
-  const SampleSlice sl = slice_of(params);
+  SampleSlice sl = slice_of(params);
   const FrameLayout L(params->nx, params->ny, 0u);  // (the plain frame)
   const FrameBlocks fb;
+  // RTG_FLAG_BACKGROUND: the block stands behind the plain frame in the caller's buffer; every rank gets it in its parameters
+  Background bg{BG_NONE, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+  if (sl.background) {
+    rtg_background b;
+    memcpy(&b, out_rgb + FrameLayout(params->nx, params->ny, RTG_FLAG_BACKGROUND).background, sizeof(b));
+    if (const char* why = background_refusal(b)) return fail(RTG_ERR_INVALID, why);
+    bg = dev_background(b);
+    sl.background = false;
+  }
   // (1) every scene renders ITS tiles (tile % n_scenes == i) into its own zero-filled full frame, on its own stream (resuming a
   // progressive frame: its tiles hold the caller's running sums)
   for (int i = 0; i < n_scenes; i++) {
@@ -270,6 +279,7 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
     }
     DevParams d;
     if (int rc = rank_params(s, camera, params, i, n_scenes, &d)) return rc;
+    d.bg = bg;
     if (sl.begin != 0u) {
       hipLaunchKernelGGL(keep_owned_kernel, dim3((uint32_t)(((size_t)d.nx * d.ny + 255) / 256)), dim3(256), 0, s->own_stream, d, s->d_frame);
       HIP_TRY(hipGetLastError());
@@ -401,7 +411,8 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   const uint32_t compute = sl.features ? fb.features.compute : 0u;
   const PlaneSet ps = make_plane_set(L, compute != 0u);
   rtg_params rp = *params;  // what the ranks render into that frame: the slice, never retired, filtered or resolved
-  rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR | RTG_FLAG_FEATURES)) | RTG_FLAG_PARTIAL;
+  // (nor do they read the background block: they get it in their parameters, from the host copy)
+  rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR | RTG_FLAG_FEATURES | RTG_FLAG_BACKGROUND)) | RTG_FLAG_PARTIAL;
   const SampleSlice rsl = slice_of(&rp);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
   const DevCamera cam = to_dev(camera);
@@ -409,6 +420,7 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   std::vector<DevParams> dps(n_scenes);
   for (int i = 0; i < n_scenes; i++) {
     if (int rc = rank_params(scenes[i], camera, &rp, i, n_scenes, &dps[i])) return rc;
+    if (sl.background) dps[i].bg = dev_background(fb.background);
     // (the pack / unpack kernels index a rank's work items with 32 bits, as launch_resolve and launch_counts do)
     if (rank_pix_work(dps[i]) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: a rank's work items overflow the 32-bit work index");
   }

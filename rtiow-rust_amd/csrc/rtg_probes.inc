@@ -36,6 +36,7 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
   if (params->flags & RTG_FLAG_DENOISE) return fail(RTG_ERR_INVALID, "rtg_debug_samples: RTG_FLAG_DENOISE is not accepted");
   if (params->flags & RTG_FLAG_FEATURES) return fail(RTG_ERR_INVALID, "rtg_debug_samples: RTG_FLAG_FEATURES is not accepted");
   if (params->flags & RTG_FLAG_DENOISE_ERROR) return fail(RTG_ERR_INVALID, "rtg_debug_samples: RTG_FLAG_DENOISE_ERROR is not accepted");
+  if (params->flags & RTG_FLAG_BACKGROUND) return fail(RTG_ERR_INVALID, "rtg_debug_samples: RTG_FLAG_BACKGROUND is not accepted");
   HIP_TRY(hipSetDevice(s->device));
   if (params->flags & RTG_FLAG_TRACE_KERNEL) {
     // Trace the PRODUCTION kernel: render the whole frame with the instrumented variant of whatever kernel par_cast

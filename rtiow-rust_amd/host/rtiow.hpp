@@ -274,6 +274,37 @@ inline Image par_cast(size_t nx, size_t ny, size_t ns, const Camera& camera, con
   return img;
 }
 
+// Not in the reference: par_cast with RTG_FLAG_BACKGROUND -- a ray that leaves the scene sees `background` instead of black
+// (lib.rs:100), so an open scene needs no emitting dome around it.  sky(bottom) is the constant background, sky(bottom, top)
+// the gradient along world +y; book_sky() the book's (white to (0.5, 0.7, 1.0)).  The image has par_cast's layout.
+inline rtg_background sky(const float (&bottom)[3]) {
+  rtg_background g{};
+  for (int c = 0; c < 3; c++) g.bottom[c] = bottom[c];
+  return g;
+}
+inline rtg_background sky(const float (&bottom)[3], const float (&top)[3]) {
+  rtg_background g = sky(bottom);
+  g.mode = 1;
+  for (int c = 0; c < 3; c++) g.top[c] = top[c];
+  return g;
+}
+inline rtg_background book_sky() { return sky({1.f, 1.f, 1.f}, {0.5f, 0.7f, 1.f}); }
+
+inline Image par_cast_background(size_t nx, size_t ny, size_t ns, const Camera& camera, const Scene& world, const rtg_background& background,
+                                 const CastOptions& opt = CastOptions()) {
+  SceneHandle s = make_scene(world, opt);
+  rtg_params p = cast_params(nx, ny, ns, opt);
+  p.flags = RTG_FLAG_BACKGROUND;
+  const size_t n = nx * ny, block_word = (3 * n + 1) & ~size_t(1);  // the plane, padding to 8 bytes, the block
+  std::vector<float> frame(block_word + sizeof(rtg_background) / sizeof(float), 0.f);
+  std::memcpy(frame.data() + block_word, &background, sizeof(background));
+  check(rtg_par_cast(s.get(), &camera.c, &p, frame.data(), nullptr));
+  Image img;
+  img.nx = nx, img.ny = ny;
+  img.rgb.assign(frame.begin(), frame.begin() + 3 * n);
+  return img;
+}
+
 // Not in the reference: the same frame rendered `step` samples at a time (include/rtiow_gpu.h RTG_FLAG_PARTIAL /
 // RTG_FLAG_RESUME).  After each slice `on_preview(n_done, preview)` receives the frame resolved at n_done samples --
 // bit-identical to par_cast(nx, ny, n_done, ...) -- and returns false to stop early (a time budget, a cancel button).  The

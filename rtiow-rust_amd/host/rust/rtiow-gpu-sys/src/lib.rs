@@ -41,6 +41,8 @@ pub const RTG_FLAG_FEATURES: u32 = 256;
 pub const RTG_FEATURES_MAX_GRID: u32 = 4;
 /// Needs `RTG_FLAG_DENOISE`: the framebuffer ends with the error plane, the variance of every filtered pixel (see the header).
 pub const RTG_FLAG_DENOISE_ERROR: u32 = 512;
+/// The framebuffer ends with an `rtg_background` block: what a ray that leaves the scene sees instead of black (see the header).
+pub const RTG_FLAG_BACKGROUND: u32 = 1024;
 
 #[repr(C)]
 pub struct rtg_builder {
@@ -128,6 +130,19 @@ pub struct rtg_features {
     pub reserved_in: u32,
     pub traced: u32,
     pub missed: u32,
+    pub reserved: [u32; 8],
+}
+
+/// 64 bytes, in-only, at the first even word behind everything the other flags put in an `RTG_FLAG_BACKGROUND` frame (without
+/// other flags: word `3 * nx * ny` rounded up to even).  `mode` 0: the constant `bottom`; 1: the gradient from `bottom` to `top`
+/// along world +y.
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default, PartialEq)]
+pub struct rtg_background {
+    pub mode: u32,
+    pub reserved_in: u32,
+    pub bottom: [c_float; 3],
+    pub top: [c_float; 3],
     pub reserved: [u32; 8],
 }
 

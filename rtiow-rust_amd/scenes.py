@@ -170,11 +170,15 @@ def bench_scene(b, nx, ny):
 # ---------------------------------------------------------------------------------------------
 # Book-1 random spheres (BASELINE.json north-star workload)
 # ---------------------------------------------------------------------------------------------
-def random_scene_objects(b, rng):
+DOME_COLOUR = (0.7, 0.8, 1.0)   # the emission of book-1's sky dome
+
+
+def random_scene_objects(b, rng, dome=True):
     """lib.rs:238-319 re-expressed in the live API: each sphere is
     Translate{offset: center, Sphere{radius, material}}; no motion (book 1); constant grey ground;
     the three r=1 spheres follow the book layout (glass / Lambertian / metal); a FlipNormals sky-dome
-    emitter (same idiom as main.rs:150-156) replaces the sky, because a miss is black (lib.rs:100)."""
+    emitter (same idiom as main.rs:150-156) replaces the sky, because a miss is black (lib.rs:100).  dome=False leaves the
+    emitter out: the world for a call with a background (include/rtiow_gpu.h RTG_FLAG_BACKGROUND)."""
     world = [b.translate(v(0.0, -1000.0, 0.0), b.sphere(1000.0, b.lambertian(b.constant(vfrom(0.5)))))]
     for a in range(-11, 11):
         for bb in range(-11, 11):
@@ -194,21 +198,29 @@ def random_scene_objects(b, rng):
     world.append(b.translate(v(0.0, 1.0, 0.0), b.sphere(1.0, b.dielectric(1.5))))
     world.append(b.translate(v(-4.0, 1.0, 0.0), b.sphere(1.0, b.lambertian(b.constant(v(0.4, 0.2, 0.1))))))
     world.append(b.translate(v(4.0, 1.0, 0.0), b.sphere(1.0, b.metal(v(0.7, 0.6, 0.5), 0.0))))
-    world.append(b.flip_normals(b.sphere(10000.0, b.diffuse_light(b.constant(v(0.7, 0.8, 1.0)), 1.0))))
+    if dome:
+        world.append(b.flip_normals(b.sphere(10000.0, b.diffuse_light(b.constant(v(*DOME_COLOUR)), 1.0))))
     return world
 
 
-def random_scene(b, nx, ny, rng=None, use_bvh=True):
+def random_scene(b, nx, ny, rng=None, use_bvh=True, sky="dome"):
     """Book-1 random spheres + the benches/scene.rs:16-30 camera; whole scene under bvh::from_scene
-    (the USE_BVH = true path of main.rs:340-345)."""
+    (the USE_BVH = true path of main.rs:340-345).
+    sky="dome" (default): the world ends with the sky-dome emitter; returns (world, camera, exposure).
+    sky="background": the world without the dome, and a fourth item, the background= of the render calls that gives the same
+    image (capi.Scene.par_cast; a constant background of the dome's emission): (world, camera, exposure, background)."""
+    if sky not in ("dome", "background"):
+        raise ValueError('sky must be "dome" or "background"')
     if rng is None:
         rng = SmallRng(0xDEADBEEF)  # main.rs:333
     exposure = (0.0, 1.0)
-    objs = random_scene_objects(b, rng)
+    objs = random_scene_objects(b, rng, dome=sky == "dome")
     if use_bvh == "sah":      # non-parity option (SURVEY.md 8 f2): same image, ~36 % fewer Aabb tests per ray
         world = [b.bvh_sah(objs, exposure)]
     else:
         world = [b.bvh(objs, exposure)] if use_bvh else objs
     cam = b.be.camera_look(v(13.0, 2.0, 3.0), v(0, 0, 0), v(0.0, 1.0, 0.0), 20.0, float(f32(nx) / f32(ny)),
                            0.1, 10.0, exposure)
+    if sky == "background":
+        return world, cam, exposure, {"bottom": DOME_COLOUR}
     return world, cam, exposure

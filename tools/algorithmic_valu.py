@@ -26,6 +26,8 @@ built from the same assembly:
               not for the helpers above the kernel (lane ranks, work-item maps, the cost-ordered queue) nor for HIP's headers
             - the code only a Dielectric lane runs (its branch + powf(x, 5): 5 % of book-1's spheres; the modal lane is Lambertian)
             - the Philox blocks as the assembly holds them (inlined copies x 10 rounds, 2 v_mad_u64_u32 each)
+            - the miss branch of a background call (RTG_FLAG_BACKGROUND: the block the compiler made of it in the END pass), which no
+              lane of an unflagged call runs
             + the blocks one lane GENERATES per event x the instructions of one block:
               scatter: in_unit_sphere accepts with p = pi / 6, 3 draws per try -> 5.73 draws -> 1.43 blocks (vec3.rs:19-26);
               camera:  2 draws (lib.rs:368-369) + 2 per in_unit_disc try (p = pi / 4) + 1 (camera.rs:55) -> 5.55 draws -> 1.39 blocks.
@@ -163,14 +165,24 @@ def region_cost(instrs, fname, a, b, others=(), detached=None):
 
 
 ARITH_FILES = ("rt_device.h", "rt_trace.h", "rt_sphere_hit.h", "rt_libm.h")
-PHILOX_LINES = ("rt_device.h", 71, 96)   # SampleRng::refill
+# SampleRng::refill, found by its anchors (text above it in rt_device.h may move it): from its first line to its closing brace
+PHILOX_LINES = ("rt_device.h",) + (find_lines(os.path.join(CSRC, "rt_device.h"), "  RT_DEV void refill() {", "  // continue the current event's stream"))
 E_BLOCKS = {"shade": (3.0 / (3.14159265358979 / 6.0)) / 4.0, "cam": (2.0 + 2.0 / (3.14159265358979 / 4.0) + 1.0) / 4.0}
 
 
-def lane_model(instrs, fname, a, b, name, dielectric):
-    """The per-lane cost of the lean kernel's shade / camera region (docstring above)."""
+def lane_model(instrs, fname, a, b, name, dielectric, flagged=None):
+    """The per-lane cost of the lean kernel's shade / camera region (docstring above).  flagged: source lines of a branch that
+    only a flagged call takes (the miss branch of RTG_FLAG_BACKGROUND) -- the block the compiler made of it, from the first to the
+    last instruction of those lines with the helpers inlined between them, is no lane's reference work and is left out
+    (`flagged_only`)."""
     idx = [i for i, (_, (f, ln)) in enumerate(instrs) if f == fname and a <= ln <= b]
     span = instrs[idx[0]:idx[-1] + 1]
+    n_flagged = 0
+    if flagged:
+        fi = [i for i, (_, (f, ln)) in enumerate(span) if f == fname and flagged[0] <= ln <= flagged[1]]
+        if fi:
+            n_flagged = sum(1 for op, _ in span[fi[0]:fi[-1] + 1] if op.startswith("v_"))
+            span = span[:fi[0]] + span[fi[-1] + 1:]
     valu = [(op, loc) for op, loc in span if op.startswith("v_")]
     useful = [(op, (f, ln)) for op, (f, ln) in valu if (f == fname and a <= ln <= b) or f in ARITH_FILES]
     philox = [1 for op, (f, ln) in useful if f == PHILOX_LINES[0] and PHILOX_LINES[1] <= ln <= PHILOX_LINES[2]]
@@ -178,7 +190,7 @@ def lane_model(instrs, fname, a, b, name, dielectric):
     diel = [1 for op, (f, ln) in useful if (f == fname and dielectric and dielectric[0] <= ln <= dielectric[1]) or (dielectric and f == "rt_libm.h")]
     per_block = len(philox) / float(copies)
     cost = len(useful) - len(philox) - len(diel) + E_BLOCKS[name] * per_block
-    return {"useful_static": len(useful), "bookkeeping_excluded": len(valu) - len(useful), "philox_static": len(philox), "philox_copies": copies,
+    return {"useful_static": len(useful), "bookkeeping_excluded": len(valu) - len(useful), "flagged_only": n_flagged, "philox_static": len(philox), "philox_copies": copies,
             "philox_per_block": per_block, "dielectric_only": len(diel), "expected_blocks_per_lane": E_BLOCKS[name], "per_operation": cost}
 
 
@@ -212,7 +224,10 @@ def main():
                     d0 = next(i + 1 for i, l in enumerate(src) if i + 1 >= a and l.startswith("          } else if (kind == MAT_DIELECTRIC) {"))
                     d1 = next(i + 1 for i, l in enumerate(src) if i + 1 > d0 and l.startswith("          } else {  // Isotropic")) - 1
                     diel = (d0, d1)
-                c["lane_model"] = lane_model(instrs, fname, a, b, name, diel)
+                flagged = None
+                if name == "cam":   # the END pass's miss branch of a background call (rt_pool.h)
+                    flagged = find_lines(os.path.join(CSRC, fname), "            } else if (P.bg.mode != BG_NONE) {", "            if (cm.scratch) {  // chunk mode")
+                c["lane_model"] = lane_model(instrs, fname, a, b, name, diel, flagged)
                 c["per_operation"] = c["lane_model"]["per_operation"]
             if key == "render_lean_pool" and name == "prim":
                 sa, sb = find_lines(os.path.join(CSRC, "rt_sphere_hit.h"), "    if (first && !(q >= t1)) {", "  return false;")
