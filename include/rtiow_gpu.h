@@ -412,7 +412,8 @@ int rtg_camera_look(const float look_from[3], const float look_at[3], const floa
 int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, rtg_scene** out);
 void rtg_scene_destroy(rtg_scene* s);
 /* Scheduling / measurement switches of one scene handle -- kernel generation, cost-ordered work queue, pool
- * thresholds, workgroup size (names: DESIGN.md section 4 "Knobs").  None of them changes a bit of the result.  The
+ * thresholds, workgroup size (names: DESIGN.md section 4 "Knobs").  None of them changes a bit of the result, with one
+ * exception: "light_sampling" (below) is another estimator of the same image.  The
  * library reads no environment variable for these.  "box_chains" = 0 stages the full LDS image of a lean
  * program (default 1: the image without box-chain followers; the same framebuffer and counters).  "box_prune" (default 1)
  * leaves out of that image the interior BOX records of the pruning plan too (rtiow_gpu_debug.h rtg_debug_box_plan): the
@@ -420,7 +421,44 @@ void rtg_scene_destroy(rtg_scene* s);
  * what the production walk executes (fewer than the reference's; every other counter unchanged; a measurement switch).
  * "bvh4" = 1 (scenes
  * that are ONE Bvh of spheres; RTG_ERR_INVALID otherwise) traverses the reference's tree (bvh.rs:22-120) as 4-wide
- * nodes: the same framebuffer, other rtg_stats.aabb_tests / prim_tests than the reference's walk. */
+ * nodes: the same framebuffer, other rtg_stats.aabb_tests / prim_tests than the reference's walk.
+ *
+ * "light_sampling" = 1 (default 0): direct light sampling (next-event estimation) of the scene's rect lights.  An explicit
+ * non-parity mode, like rtg_object_bvh_sah: the same expectation for every max_bounces, other samples, other bits.
+ * What it costs (measured): every frame on the one-lane-per-pixel kernels, 25 .. 100 x the kernel time of
+ * the ray-pool kernels; and one light sample per hit without multiple importance sampling is heavy-tailed where a surface comes
+ * close to a light -- the Cornell box's light hangs one unit under its ceiling: at 256 x 256 x 64 the variance is TEN TIMES the
+ * plain estimator's, single pixels spike, and a frame of few samples reads 1-2 % dark; the book-2 final scene's variance is
+ * 1.34 x lower.  More plain samples win on both scenes at equal time.  It adds no flag, no struct field and no frame offset: every flag of
+ * rtg_params works unchanged on its sums.
+ *   Which lights: a DiffuseLight material is SAMPLED when every primitive of the world's graph that uses it is a Rect at the
+ *   world's list level, bare or under any number of FlipNormals (not under Translate, Scale, RotateY, LinearMove, And, a
+ *   medium boundary or a Bvh).  The rects of the sampled materials, in world order, are the light table, N entries (rects
+ *   with an empty range are left out); more than RT_MAX_LIGHTS = 64 entries: setting the option to 1 returns RTG_ERR_INVALID;
+ *   none: accepted, the frames are those without the option, bit for bit.  Every other emitter is found by scattered rays
+ *   as without the option, at full weight.  Scene option "verbose" prints N.
+ *   At a hit (p, n, material) of color()'s loop (lib.rs:60-101), `bounces` the running count:
+ *   1. Emission is added as always -- except when the material is sampled and step 2 ran at the previous hit.  Camera rays and
+ *      rays leaving Metal, Dielectric or the hit at which the bounce cap ends the path still collect it.
+ *   2. When the material is Lambertian or Isotropic, N > 0 and bounces < max_bounces: three gen_f32 draws from the path's
+ *      stream -- light i = min(N - 1, floor(u0 N)), then the point q of its rect from (u1, u2), uniform.  w = q - p,
+ *      r2 = w.w, cos_l = |w[axis]| / sqrt(r2) (DiffuseLight emits from both faces).  `lobe` is the density of the material's
+ *      scattered direction along w.  The reference's Lambertian scatters towards p + n + in_unit_sphere(), a point of the unit
+ *      BALL (material.rs:57-65), so its lobe is not cos / pi: with b = n.w / sqrt(r2), disc = b^2 - (n.n - 1),
+ *      r_hi = b + sqrt(disc), r_lo = max(b - sqrt(disc), 0): lobe = (r_hi^3 - r_lo^3) / (4 pi), 0 when disc <= 0 or r_hi <= 0
+ *      -- 2 cos^3 / pi for |n| = 1, and valid for the unnormalised normals Scale leaves.  Isotropic: lobe = 1 / (4 pi).
+ *      When lobe, r2 and cos_l are > 0 a shadow ray runs from p along w (unnormalised: the light sits at t = 1) at the path's
+ *      time; it is occluded when anything is hit in [t_near, 1 - 1e-3).  A ConstantMedium takes part with its own free-path
+ *      draw, an unbiased estimate of its transmittance.  Unoccluded:
+ *        accum += strength * albedo(p) * Le(q) * (lobe * N * area_i * cos_l / r2),  Le(q) = brightness * texture(q).
+ *      The last 1e-3 of the segment is not tested (the light itself lies there); that bias is accepted.
+ *   3. Scatter as always.  A miss returns accum, plus the background under RTG_FLAG_BACKGROUND (without the option accum is
+ *      always +0 at a miss).  max_bounces = 0 makes no new draw.
+ *   Every frame of the handle renders on the one-lane-per-pixel kernels (rtg_stats / the debug interface report the baseline
+ *   kernel; options "kernel", "bvh4" and the pool thresholds are ignored meanwhile); rtg_debug_samples without
+ *   RTG_FLAG_TRACE_KERNEL returns the option's samples, with it RTG_ERR_UNSUPPORTED as for every baseline frame.
+ *   rtg_par_cast_multi returns RTG_ERR_INVALID when its handles disagree on the option.  rtg_stats counts what runs: `rays`
+ *   includes the shadow rays, `draws` the three light draws and the media draws of shadow rays; `samples` is unchanged. */
 int rtg_scene_set_option(rtg_scene* s, const char* name, int value);
 /* size of the flattened program (for DESIGN.md's byte accounting / tests); n_box_followers: BOX records of a lean program
  * that repeat the BOX before them bit for bit and are no skip target ("box chains") -- the records production

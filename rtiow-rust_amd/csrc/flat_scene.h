@@ -129,6 +129,16 @@ enum MatKind : uint32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2,
 enum TexKind : uint32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_PERLIN = 2 };
 // Texture record, 32 bytes: lo = (r, g, b, scale) hi = (t0, t1, -, kind)
 
+// Light table (scene option light_sampling, rt_light.h): one record per Rect of a SAMPLED DiffuseLight material, in world order.
+// A material is sampled when every primitive of the world's graph that uses it is a Rect at the world's list level, bare or
+// under FlipNormals (scene_builder.cpp light_table).  Not part of the flat program: buffers of their own.
+constexpr uint32_t RT_MAX_LIGHTS = 64;
+struct LightRect {
+  float k, r0s, r0e, r1s, r1e;  // Rect<axis> { k, r0, r1 } (object.rs:185-218)
+  float area;                   // (r0e - r0s) * (r1e - r1s)
+  uint32_t axis, mat;
+};
+
 // Feature bits of a flattened scene: select the kernel instantiation (lean book-1 path vs full path)
 constexpr uint32_t FEAT_XFORM = 1u;    // PUSH/POP present
 constexpr uint32_t FEAT_MEDIUM = 2u;   // MEDIUM present

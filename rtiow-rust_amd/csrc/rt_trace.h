@@ -269,7 +269,9 @@ __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __r
 // same visiting order, same counters as hit_top / boundary_hit_t; one lane per ray, private stacks: the slow, general path.
 // XD = wrapper levels the ray stacks hold, ML = levels of boundary queries below the main walk: chosen per scene by what its graph
 // needs (FEAT_DEEP_FEW_WRAPPERS / FEAT_DEEP_ONE_LEVEL) -- the stacks are private memory and registers of every lane.
-template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING>
+// ANY (LEVEL 0, `rec` == null; rt_light.h occluded): an occlusion query over [t_lo, t_hi) -- returns at the first accepted hit,
+// t_out unset.  Its boundary queries are the ordinary closest-t ones.
+template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING, bool ANY = false>
 __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t first, uint32_t end_pc, V3 o, V3 d, const float time,
                                                     const float t_lo, const float t_hi, SampleRng& rng, HitRec* rec, float& t_out,
                                                     Counts& cnt) {
@@ -322,6 +324,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
           rec->t = t, rec->p = p, rec->n = n, rec->mat = hi.z;
         }
         best = t, any = true, tag = depth, nhits++;
+        if (ANY) return true;
       }
       pc++;
     } else if (op == OP_RECT) {
@@ -335,6 +338,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
           rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = n, rec->mat = hi.z;
         }
         best = t, any = true, tag = depth, nhits++;
+        if (ANY) return true;
       }
       pc++;
     } else if (op == OP_PRISM) {
@@ -345,6 +349,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
       if (nh) {
         if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = prism_normal(face), rec->mat = hi.z;
         best = t, any = true, tag = depth, nhits += nh;
+        if (ANY) return true;
       }
       pc++;
     } else if (op == OP_PUSH) {
@@ -415,6 +420,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
               if (accept) {
                 if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = mk(1.f, 0.f, 0.f), rec->mat = hi.z;
                 best = t, any = true, tag = depth, nhits++;
+                if (ANY) return true;
               }
             }
           }

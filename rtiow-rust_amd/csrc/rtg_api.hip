@@ -31,6 +31,7 @@
 #include "rt_sync_full.h"
 #include "rt_pool2.h"
 #include "rt_trace.h"
+#include "rt_light.h"
 #include "scene_builder.h"
 
 using namespace rtg;
@@ -191,6 +192,16 @@ struct rtg_scene {
   Pool2Tuning pool2_tune{24, 48, 40, 4, 8, 24, 2};  // refill_min, box_leave, park_max, t_sphere, t_prism, t_list, t_push
   int guide_lds = 0;                       // guided filter (rt_denoise.h GUIDED): 1 = the neighbours' feature records from an LDS copy, 0 = through the caches
   int small_frames = 1;                    // rtg_launch.inc pool_geometry: frames smaller than the chip get small workgroups and reservations
+  // Scene option light_sampling (rt_light.h): 1 = every frame on the one-lane-per-pixel kernels over color_ls.  The table is made
+  // when the scene is created (scene_builder.cpp light_table), on the host; it goes to buffers of its own when the option is first
+  // set to 1 (unless it is empty or too long), so a handle that never sets the option holds and reports the bytes it always did.
+  int light_sampling = 0;
+  uint32_t n_lights = 0;                   // the table's length, whatever it is
+  std::vector<LightRect> h_lights;         // the table and the per-material sampled bytes
+  std::vector<uint8_t> h_sampled;
+  LightTable lights{nullptr, nullptr, 0};  // d_lights / d_sampled: .n = 0 until uploaded, and when there is nothing to sample
+  void* d_lights = nullptr;
+  void* d_sampled = nullptr;
   LaunchCtx ctx[RTG_MAX_FRAMES];           // frames in flight
   int n_ctx = 1, next_ctx = 0;
   LaunchCtx* cx = &ctx[0];                 // the context of the call being made (ctx_acquire)
@@ -690,6 +701,8 @@ void rtg_scene_destroy(rtg_scene* s) {
     if (c.done) (void)hipEventDestroy(c.done);
   }
   if (s->d_frame) (void)hipFree(s->d_frame);
+  if (s->d_lights) (void)hipFree(s->d_lights);
+  if (s->d_sampled) (void)hipFree(s->d_sampled);
   if (s->d_pack) (void)hipFree(s->d_pack);
   if (s->d_recv) (void)hipFree(s->d_recv);
   if (s->post0) (void)hipEventDestroy(s->post0);
@@ -793,6 +806,8 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
       s->wide_bytes = (uint32_t)(wide.size() * sizeof(uint32_t));
     }
   }
+  b->sb.light_table(world, n, &s->h_lights, &s->h_sampled);  // (scene option light_sampling uploads it)
+  s->n_lights = (uint32_t)s->h_lights.size();
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->num_cus = prop.multiProcessorCount;
   if (s->num_cus <= 0) s->num_cus = 256;
@@ -807,8 +822,9 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
 
 
 // Scheduling / measurement switches of ONE scene handle (none of them changes a bit of the result; every setting is
-// covered by test_every_kernel_variant_and_schedule_gives_the_same_bits).  The library itself reads no environment
-// variable for these: sweep tools and the test-suite set them through this call (capi.py forwards RTG_* variables).
+// covered by test_every_kernel_variant_and_schedule_gives_the_same_bits) -- and light_sampling, the one option that changes the
+// estimator (include/rtiow_gpu.h).  The library itself reads no environment variable for these: sweep tools and the test-suite
+// set them through this call (capi.py forwards RTG_* variables).
 int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   if (!s || !name) return fail(RTG_ERR_INVALID, "null argument");
   const std::string k(name);
@@ -869,6 +885,27 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "deep_sized") s->deep_sized = value;
   else if (k == "mat_lds") s->mat_lds = value;
   else if (k == "guide_lds") s->guide_lds = value;
+  else if (k == "light_sampling") {                             // 1: direct light sampling of the scene's rect lights (rt_light.h): other samples, the same expectation
+    if (value < 0 || value > 1) return fail(RTG_ERR_INVALID, "light_sampling: 0 or 1");
+    if (value && s->n_lights > RT_MAX_LIGHTS) return fail(RTG_ERR_INVALID, "light_sampling: the scene's light table has " + std::to_string(s->n_lights) + " rects, more than RT_MAX_LIGHTS (64)");
+    if (value && s->n_lights != 0u && !s->d_lights) {  // the first time: the table to the device
+      HIP_TRY(hipSetDevice(s->device));
+      int rc = upload(&s->d_lights, s->h_lights.data(), s->h_lights.size() * sizeof(LightRect), &s->bytes);
+      if (!rc) rc = upload(&s->d_sampled, s->h_sampled.data(), s->h_sampled.size(), &s->bytes);
+      if (rc) return rc;
+      s->lights = LightTable{(const LightRect*)s->d_lights, (const uint8_t*)s->d_sampled, s->n_lights};
+    }
+    if (s->verbose) {
+      fprintf(stderr, "[rtg] light sampling %s: light table of %u rect(s)\n", value ? "on" : "off", s->n_lights);
+      for (const LightRect& l : s->h_lights)
+        fprintf(stderr, "[rtg]   light: axis %u k %.9g r0 %.9g %.9g r1 %.9g %.9g area %.9g material %u\n", l.axis, l.k, l.r0s, l.r0e, l.r1s, l.r1e, l.area, l.mat);
+      std::string ids;
+      for (size_t m = 0; m < s->h_sampled.size(); m++)
+        if (s->h_sampled[m]) ids += " " + std::to_string(m);
+      fprintf(stderr, "[rtg]   sampled materials:%s\n", ids.c_str());
+    }
+    s->light_sampling = value;
+  }
   else if (k == "small_frames") s->small_frames = value;        // 0: one geometry for every frame size (measurement switch)
   else if (k == "verbose") s->verbose = value;                  // print launch geometry / schedule statistics to stderr
   else if (k == "window") s->window = value;                    // full-feature kernel: records staged in LDS, -1 = automatic

@@ -117,6 +117,63 @@ __global__ __launch_bounds__(256) void render_counts_kernel(DevScene sc, DevCame
   if (COUNT) flush_counts(cnt, total_draws, counters);
 }
 
+// Scene option light_sampling (rt_light.h): the kernels above over color_ls, for scenes whose light table is not empty -- the
+// same pixel mapping, the same ordered folds.  One body: a whole frame is s_begin = 0, divide = 1; SQ as render_squares_kernel;
+// CNT as render_counts_kernel (the pixel's samples [s_begin, min(n_p, ns)), never divided).
+template <uint32_t FEAT, bool COUNT, bool SQ, bool CNT>
+__global__ __launch_bounds__(256) void render_light_kernel(DevScene sc, LightTable lt, DevCamera cam, DevParams P, float* out,
+                                                           unsigned long long* counters, uint32_t s_begin, uint32_t divide, const uint32_t* counts) {
+  const uint32_t nbx = (P.nx + 15u) / 16u;
+  const uint32_t bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
+  const uint32_t tiles_x = (P.nx + P.tile_w - 1u) / P.tile_w;
+  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
+  const uint32_t x0 = bx * 16u + (w & 1u) * 8u, row0 = by * 16u + (w >> 1) * 8u;
+  const uint32_t tile = (row0 / P.tile_h) * tiles_x + x0 / P.tile_w;
+  if (tile % P.nranks != P.rank) return;
+  const uint32_t x = x0 + (l & 7u);
+  const uint32_t row = row0 + (l >> 3);
+  if (x >= P.nx || row >= P.ny) return;
+  const uint32_t y = P.ny - 1u - row;
+  uint32_t s_end = P.ns;
+  if (CNT) {
+    const uint32_t n = counts[(size_t)row * P.nx + x];
+    s_end = n < P.ns ? n : P.ns;
+    if (s_end <= s_begin) return;
+  }
+  Counts cnt = {0, 0, 0, 0};
+  uint32_t total_draws = 0;
+  float* o = out + 3ull * ((size_t)row * P.nx + x);
+  float* q = o + 3ull * ((size_t)P.nx * P.ny);
+  V3 col = mk(0.f, 0.f, 0.f), sq = mk(0.f, 0.f, 0.f);
+  if (s_begin != 0u) {
+    col = mk(o[0], o[1], o[2]);
+    if (SQ) sq = mk(q[0], q[1], q[2]);
+  }
+  for (uint32_t s = s_begin; s < s_end; s++) {
+    uint32_t bounces, draws;
+    V3 c = sample_color_ls<FEAT, COUNT>(sc, lt, cam, P, x, y, s, cnt, bounces, draws);
+    col = vadd(col, c);
+    if (SQ) sq = vadd(sq, vmul(c, c));
+    if (COUNT) total_draws += draws;
+  }
+  if (!CNT && divide) col = sdiv(col, (float)P.ns);  // lib.rs:374
+  o[0] = col.x, o[1] = col.y, o[2] = col.z;
+  if (SQ) q[0] = sq.x, q[1] = sq.y, q[2] = sq.z;
+  if (COUNT) flush_counts(cnt, total_draws, counters);
+}
+
+template <uint32_t FEAT>
+__global__ void debug_samples_light_kernel(DevScene sc, LightTable lt, DevCamera cam, DevParams P, uint32_t n, const uint32_t* xs,
+                                           const uint32_t* ys, const uint32_t* ss, float* out_rgb, uint32_t* out_info) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Counts cnt = {0, 0, 0, 0};
+  uint32_t bounces = 0, draws = 0;
+  V3 c = sample_color_ls<FEAT, true>(sc, lt, cam, P, xs[i], ys[i], ss[i], cnt, bounces, draws);
+  out_rgb[3 * i] = c.x, out_rgb[3 * i + 1] = c.y, out_rgb[3 * i + 2] = c.z;
+  out_info[4 * i] = bounces, out_info[4 * i + 1] = draws, out_info[4 * i + 2] = cnt.aabb, out_info[4 * i + 3] = cnt.prim;
+}
+
 template <uint32_t FEAT>
 __global__ void debug_hit_top_kernel(DevScene sc, uint32_t n, const float* rays, uint32_t seed_lo, uint32_t seed_hi,
                                      float t_near, float* out, uint32_t* out_mat) {

@@ -707,7 +707,8 @@ static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevPara
   const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
   const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
   // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
-  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP);
+  // scene option light_sampling: the one-lane-per-pixel family in every case, whatever options kernel, bvh4 and the pool thresholds say
+  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP) && !s->light_sampling;
   if (pool_ok) {  // (launch_full_pool names the kernel it picks)
     s->cx->last_kernel = geom != 0 ? KernelKind::full_pool : KernelKind::lean_pool;
     return geom != 0 ? launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl) : launch_pool<COUNT>(s, cam, d, d_out, stream, sl);
@@ -715,6 +716,18 @@ static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevPara
   // the baseline kernels: counts, squares and slices of a progressive frame have instantiations of their own
   const dim3 grid(((d.nx + 15) / 16) * ((d.ny + 15) / 16)), block(256);
   const uint32_t divide = sl.divide ? 1u : 0u;
+  if (s->light_sampling && s->verbose) fprintf(stderr, "[rtg] light sampling: light table of %u rect(s)%s\n", s->n_lights, s->lights.n ? "" : ": the plain kernels");
+  if (s->light_sampling && s->lights.n != 0u) {  // ... over color_ls (rt_light.h); with an empty table color_ls is color(): the kernels below
+    with_feat<false>(s, [&](auto feat) {
+      constexpr uint32_t F = decltype(feat)::value;
+      if constexpr (F != 0u)  // (a table that is not empty holds a Rect: never a lean program)
+        with_bools([&](auto sq, auto cn) {
+          hipLaunchKernelGGL((render_light_kernel<F, COUNT, decltype(sq)::value, decltype(cn)::value>), grid, block, 0, stream, s->dev, s->lights, cam, d, d_out,
+                             s->cx->d_counters, sl.begin, divide, sl.list.counts);
+        }, sl.squares, sl.counts);
+    });
+    return hipGetLastError();
+  }
   if (sl.counts)
     with_feat<false>(s, [&](auto feat) {
       constexpr uint32_t F = decltype(feat)::value;

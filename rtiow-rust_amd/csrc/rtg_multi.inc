@@ -593,6 +593,8 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
     // one handle = one frame, one work queue, one stream: the same handle twice would wipe its own tiles
     for (int k = 0; k < i; k++)
       if (scenes[k] == scenes[i]) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi: the same scene handle appears twice (one handle per shard)");
+    // ... and one estimator: tiles with light sampling beside tiles without it are no frame
+    if (scenes[i]->light_sampling != scenes[0]->light_sampling) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi: the handles disagree on scene option light_sampling");
   }
   // a call without any of the five flags is the plain frame whatever the option says
   const uint32_t plane_flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_FEATURES;

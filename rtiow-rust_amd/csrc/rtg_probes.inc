@@ -94,7 +94,13 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
   HIP_TRY(hipMemcpy(ds.p, samples, n * 4, hipMemcpyHostToDevice));
   DevCamera cam = to_dev(camera);
   dim3 grid((uint32_t)((n + 63) / 64)), block(64);
-  if (n)
+  if (n && s->light_sampling && s->lights.n != 0u)  // scene option light_sampling: the sample of color_ls (rt_light.h)
+    with_feat<false>(s, [&](auto feat) {
+      constexpr uint32_t F = decltype(feat)::value;
+      if constexpr (F != 0u)
+        hipLaunchKernelGGL((debug_samples_light_kernel<F>), grid, block, 0, 0, s->dev, s->lights, cam, d, (uint32_t)n, dx.p, dy.p, ds.p, drgb.p, dinfo.p);
+    });
+  else if (n)
     with_feat<false>(s, [&](auto feat) {
       hipLaunchKernelGGL((debug_samples_kernel<decltype(feat)::value>), grid, block, 0, 0, s->dev, cam, d, (uint32_t)n, dx.p, dy.p, ds.p, drgb.p, dinfo.p);
     });

@@ -638,6 +638,55 @@ bool SceneBuilder::flatten_pool2(const uint32_t* world, size_t n, FlatScene* out
   return true;
 }
 
+// Which DiffuseLight materials light sampling may sample, and their Rects (flat_scene.h LightRect; rt_light.h).  Every use of a
+// material by a primitive of the world's graph is either "a Rect at list level, bare or under FlipNormals" or "anything else"
+// (a Sphere, a Rect below a Translate / Scale / RotateY / LinearMove / And / Bvh, a medium's boundary or phase material): a
+// material is sampled when it is a DiffuseLight with uses of the first kind only, so that a scattered ray can never reach it
+// on a surface the table does not hold.  The table lists those Rects in world order.
+void SceneBuilder::light_table(const uint32_t* world, size_t n, std::vector<LightRect>* lights, std::vector<uint8_t>* sampled) const {
+  enum : uint8_t { LIST_RECT = 1, OTHER = 2 };
+  std::vector<uint8_t> use(materials.size(), 0);
+  std::vector<uint32_t> todo, rects;
+  auto mark_other = [&](uint32_t root) {  // every material used at or below `root`
+    todo.assign(1, root);
+    while (!todo.empty()) {
+      const HostObject& o = objects[todo.back()];
+      todo.pop_back();
+      switch (o.kind) {
+        case HostObject::SPHERE:
+        case HostObject::RECT: use[o.mat] |= OTHER; break;
+        case HostObject::AND: todo.push_back(o.a), todo.push_back(o.b); break;
+        case HostObject::MEDIUM: use[o.mat] |= OTHER, todo.push_back(o.a); break;
+        case HostObject::BVH: {
+          std::vector<int32_t> nodes(1, (int32_t)o.a);
+          while (!nodes.empty()) {
+            const HostBvhNode& node = bvh_nodes[nodes.back()];
+            nodes.pop_back();
+            if (node.leaf != kNone) todo.push_back(node.leaf);
+            else nodes.push_back(node.left), nodes.push_back(node.right);
+          }
+          break;
+        }
+        default: todo.push_back(o.a);  // wrappers
+      }
+    }
+  };
+  for (size_t i = 0; i < n; i++) {
+    uint32_t id = world[i];
+    while (objects[id].kind == HostObject::FLIP) id = objects[id].a;
+    if (objects[id].kind == HostObject::RECT) use[objects[id].mat] |= LIST_RECT, rects.push_back(id);
+    else mark_other(world[i]);
+  }
+  sampled->assign(materials.size(), 0);
+  for (size_t m = 0; m < materials.size(); m++) (*sampled)[m] = materials[m].kind == MAT_DIFFUSE_LIGHT && use[m] == LIST_RECT;
+  lights->clear();
+  for (uint32_t id : rects) {
+    const HostObject& o = objects[id];
+    if (!(*sampled)[o.mat] || !(o.f[1] < o.f[2] && o.f[3] < o.f[4])) continue;  // (an empty range: no ray ever hits it, object.rs:201)
+    lights->push_back(LightRect{o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], (o.f[2] - o.f[1]) * (o.f[4] - o.f[3]), (uint32_t)o.axis, o.mat});
+  }
+}
+
 void SceneBuilder::finish_materials(FlatScene* out) const {
   // Albedo range of every scattering material -- decides whether the pool kernels' "accum is +0" argument holds
   // (rt_pool.h PoolField): walks the WHOLE texture tree (a checker's children, recursively; texture.rs:12-21), any

@@ -76,6 +76,8 @@ class SceneBuilder {
   uint32_t add_bvh(const uint32_t* objs, size_t n, float e0, float e1, bool sah = false);
   Box3 bounding_box(uint32_t obj, float e0, float e1) const;
   void flatten(const uint32_t* world, size_t n, FlatScene* out) const;
+  // The light table of `world` (flat_scene.h LightRect) and, per material, whether it is sampled (scene option light_sampling)
+  void light_table(const uint32_t* world, size_t n, std::vector<LightRect>* lights, std::vector<uint8_t>* sampled) const;
   bool hoist_segments = true;  // flatten() may put an OP_SEG record in front of a list world's longest run of plain primitives
 
  private:

@@ -239,6 +239,9 @@ struct CastOptions {
 using SceneHandle = std::unique_ptr<rtg_scene, void (*)(rtg_scene*)>;
 
 // flatten `world` once onto opt.device
+// (Not in the reference, and not switched on by anything in this header: rtg_scene_set_option(handle.get(), "light_sampling", 1)
+// renders every frame of the handle with direct light sampling of the world's list-level rect lights -- another estimator of
+// the same image, not the reference's samples; include/rtiow_gpu.h, at rtg_scene_set_option, states it.)
 inline SceneHandle make_scene(const Scene& world, const CastOptions& opt) {
   rtg_builder* b = nullptr;
   check(rtg_builder_create(&b));

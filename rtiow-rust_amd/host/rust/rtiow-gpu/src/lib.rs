@@ -236,7 +236,9 @@ impl GpuScene {
     /// Scheduling / resource switches of this handle (`rtg_scene_set_option`; none changes a bit of the result): e.g.
     /// `("scratch_mb", 4096)` bounds the per-sample colour scratch (larger frames render in sample passes),
     /// `("frames_in_flight", 2)` lets two asynchronous frames of this handle overlap, `("force_rccl", 1)` sends
-    /// `gpu_cast_multi` through the RCCL collective even on one device.
+    /// `gpu_cast_multi` through the RCCL collective even on one device.  The one exception: `("light_sampling", 1)` renders
+    /// with direct light sampling of the world's list-level rect lights -- another estimator of the same image, not the
+    /// reference's samples (`include/rtiow_gpu.h`, at `rtg_scene_set_option`).
     pub fn set_option(&mut self, name: &str, value: i32) -> Result<()> {
         let c = std::ffi::CString::new(name).map_err(|_| last_error(sys::RTG_ERR_INVALID))?;
         check(unsafe { sys::rtg_scene_set_option(self.raw, c.as_ptr(), value) })
