@@ -130,6 +130,10 @@ struct SampleRng {
   }
   RT_DEV uint32_t next_u32() {
     if (left == 0) refill();
+    return next_u32_primed();
+  }
+  // next_u32() for a caller that knows the word is there: refill() ran and fewer than four words were taken since
+  RT_DEV uint32_t next_u32_primed() {
     uint32_t r = b0;
     b0 = b1, b1 = b2, b2 = b3;
     left--;
@@ -138,6 +142,7 @@ struct SampleRng {
   }
   // rand 0.6.5 Standard for f32: (u32 >> 8) * 2^-24
   RT_DEV float gen_f32() { return (float)(next_u32() >> 8) * (1.0f / 16777216.0f); }
+  RT_DEV float gen_f32_primed() { return (float)(next_u32_primed() >> 8) * (1.0f / 16777216.0f); }
   // rand 0.6.5 UniformFloat::sample_single (camera.rs:55)
   RT_DEV float gen_range(float low, float high) {
     float scale = high - low;
@@ -172,6 +177,31 @@ RT_DEV bool in_unit_sphere_tries(SampleRng& rng, uint32_t max_tries, V3& out) {
     }
   }
   return false;
+}
+// in_unit_sphere_tries for a pass some of whose lanes draw no direction (`wanted` false) but take a later draw from the same
+// stream position: the head of the loop is the ONE place where the first block of any lane of the pass is generated.  The
+// lanes that came for the block alone leave behind it with its four words unread (next_u32_primed() hands them out); the others
+// make four attempts per trip on that block and the two behind it (12 draws = 3 whole blocks, so every lane crosses the block
+// boundaries at the same draws), `max_tries` / 4 trips at the most.  The stream stands at a block boundary (left == 0) on
+// entry, and max_tries is a multiple of 4.  Same words, same order and same `draws` as in_unit_sphere_tries.
+RT_DEV bool in_unit_sphere_tries_shared(SampleRng& rng, bool wanted, uint32_t max_tries, V3& out) {
+  for (uint32_t k = 0;;) {
+    rng.refill();
+    if (!wanted) return false;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++) {
+      float a = rng.gen_f32();
+      float b = rng.gen_f32();
+      float c = rng.gen_f32();
+      V3 v = vsub(smul(2.f, mk(a, b, c)), splat(1.f));
+      if (vdot(v, v) < 1.f) {
+        out = v;
+        return true;
+      }
+    }
+    k += 4u;
+    if (k >= max_tries) return false;
+  }
 }
 // vec3.rs:32-39
 RT_DEV V3 in_unit_disc(SampleRng& rng) {

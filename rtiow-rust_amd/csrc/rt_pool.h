@@ -1050,8 +1050,15 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
           // draws); the 5 % of the lanes that are still without a direction leave their slot as it is, note the try in
           // best_pc and go back on the S-list -- a later pass continues their stream where this one stopped (same draws, same
           // order: the stream is counter-based).  The fourth pass of a slot loops to the end.
+          // A Dielectric lane draws no direction, but its one draw (below, if the ray refracts) is word 0 of the block at ITS
+          // stream position, block 0 -- the block the other lanes generate as the first of their attempts.  The lane sets are
+          // disjoint and the instructions the same, so the loop's first generation serves both (in_unit_sphere_tries_shared):
+          // the pass holds three copies of the Philox block, not a fourth one for the few lanes that refract.
           V3 rs = mk(0.f, 0.f, 0.f);
-          if (kind != MAT_DIELECTRIC) deferred = !in_unit_sphere_tries(rng, (RT_SCATTER_TRIES && tries < 3u) ? (uint32_t)RT_SCATTER_TRIES : 0xffffffffu, rs);
+          const uint32_t max_tries = (RT_SCATTER_TRIES && tries < 3u) ? (uint32_t)RT_SCATTER_TRIES : 0xffffffffu;
+          constexpr bool SHARED_BLOCK = RT_SCATTER_TRIES % 4 == 0;  // (attempts in whole blocks: the stream stands at a block boundary here)
+          if (SHARED_BLOCK) deferred = !in_unit_sphere_tries_shared(rng, kind != MAT_DIELECTRIC, max_tries, rs) && kind != MAT_DIELECTRIC;
+          else if (kind != MAT_DIELECTRIC) deferred = !in_unit_sphere_tries(rng, max_tries, rs);
           if (COUNT && !deferred) cnt.shaded++;
           if (kind == MAT_LAMBERTIAN) {  // material.rs:57-65
             V3 target = vadd(vadd(hp, hn), rs);
@@ -1079,7 +1086,7 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
             bool refracted = disc > 0.f;
             if (refracted) {
               nd = vsub(smul(ni_over_nt, vsub(uv, smul(dt, outward))), smul(__builtin_sqrtf(disc), outward));
-              refracted = rng.gen_f32() >= schlick<true>(cosine, param);  // material.rs:97: draw only if Some
+              refracted = (SHARED_BLOCK ? rng.gen_f32_primed() : rng.gen_f32()) >= schlick<true>(cosine, param);  // material.rs:97: draw only if Some
             }
             if (!refracted) nd = reflect(sd, hn);
             att = splat(1.f);
@@ -1172,7 +1179,8 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
               col = vadd(mk(SLOT_F(PF_COL, j), SLOT_F(PF_COL + 1, j), SLOT_F(PF_COL + 2, j)), result);  // vec3.rs:195-203
             }
             s++;
-            if (s == P.ns || (cm.scratch && s % cm.chunk == 0u)) {
+            // (cm.chunk is wave-uniform and 1 in a launch that is not chunked: the division behind it is for chunked launches alone)
+            if (s == P.ns || (cm.scratch && (cm.chunk == 1u || s % cm.chunk == 0u))) {
               if (!cm.scratch) {
                 V3 px = sdiv(col, (float)P.ns);  // lib.rs:374
                 float* op_ = out + 3ull * ((size_t)row * P.nx + x);

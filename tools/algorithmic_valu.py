@@ -28,6 +28,8 @@ built from the same assembly:
             - the Philox blocks as the assembly holds them (inlined copies x 10 rounds, 2 v_mad_u64_u32 each)
             - the miss branch of a background call (RTG_FLAG_BACKGROUND: the block the compiler made of it in the END pass), which no
               lane of an unflagged call runs
+            - three of the four unrolled in_unit_sphere attempts of the SCATTER pass (rt_device.h in_unit_sphere_tries_shared): a loop
+              body counts once here, as it did while the attempts were a rolled loop
             + the blocks one lane GENERATES per event x the instructions of one block:
               scatter: in_unit_sphere accepts with p = pi / 6, 3 draws per try -> 5.73 draws -> 1.43 blocks (vec3.rs:19-26);
               camera:  2 draws (lib.rs:368-369) + 2 per in_unit_disc try (p = pi / 4) + 1 (camera.rs:55) -> 5.55 draws -> 1.39 blocks.
@@ -167,6 +169,10 @@ def region_cost(instrs, fname, a, b, others=(), detached=None):
 ARITH_FILES = ("rt_device.h", "rt_trace.h", "rt_sphere_hit.h", "rt_libm.h")
 # SampleRng::refill, found by its anchors (text above it in rt_device.h may move it): from its first line to its closing brace
 PHILOX_LINES = ("rt_device.h",) + (find_lines(os.path.join(CSRC, "rt_device.h"), "  RT_DEV void refill() {", "  // continue the current event's stream"))
+# in_unit_sphere_tries_shared (rt_device.h): the SCATTER pass's four unrolled attempts.  A loop body counts once in this tool, and
+# these four bodies were one before they were unrolled: the lane model counts a quarter of them (`attempts_static` / 4).
+ATTEMPT_LINES = ("rt_device.h",) + (find_lines(os.path.join(CSRC, "rt_device.h"), "RT_DEV bool in_unit_sphere_tries_shared(", "// vec3.rs:32-39"))
+ATTEMPTS_UNROLLED = 4
 E_BLOCKS = {"shade": (3.0 / (3.14159265358979 / 6.0)) / 4.0, "cam": (2.0 + 2.0 / (3.14159265358979 / 4.0) + 1.0) / 4.0}
 
 
@@ -189,9 +195,17 @@ def lane_model(instrs, fname, a, b, name, dielectric, flagged=None):
     copies = max(1, round(sum(1 for op, (f, ln) in useful if op.startswith("v_mad_u64_u32")) / 20.0))
     diel = [1 for op, (f, ln) in useful if (f == fname and dielectric and dielectric[0] <= ln <= dielectric[1]) or (dielectric and f == "rt_libm.h")]
     per_block = len(philox) / float(copies)
-    cost = len(useful) - len(philox) - len(diel) + E_BLOCKS[name] * per_block
+    # the unrolled attempts: the useful instructions, Philox aside, between the first and the last one emitted for the helper's own lines
+    attempts = 0
+    if name == "shade":
+        hi = [i for i, (op, (f, ln)) in enumerate(span) if f == ATTEMPT_LINES[0] and ATTEMPT_LINES[1] <= ln <= ATTEMPT_LINES[2]]
+        if hi:
+            attempts = sum(1 for op, (f, ln) in span[hi[0]:hi[-1] + 1] if op.startswith("v_") and ((f == fname and a <= ln <= b) or f in ARITH_FILES)
+                           and not (f == PHILOX_LINES[0] and PHILOX_LINES[1] <= ln <= PHILOX_LINES[2]))
+    cost = len(useful) - len(philox) - len(diel) - attempts * (1.0 - 1.0 / ATTEMPTS_UNROLLED) + E_BLOCKS[name] * per_block
     return {"useful_static": len(useful), "bookkeeping_excluded": len(valu) - len(useful), "flagged_only": n_flagged, "philox_static": len(philox), "philox_copies": copies,
-            "philox_per_block": per_block, "dielectric_only": len(diel), "expected_blocks_per_lane": E_BLOCKS[name], "per_operation": cost}
+            "philox_per_block": per_block, "dielectric_only": len(diel), "attempts_static": attempts, "attempts_unrolled": ATTEMPTS_UNROLLED if attempts else 1,
+            "expected_blocks_per_lane": E_BLOCKS[name], "per_operation": cost}
 
 
 def main():

@@ -61,6 +61,8 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #define OP_XOR(k) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(a[k]) : "v"(m));
 #define OP_MULLO(k) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(a[k]) : "v"(m));
 #define OP_MULHI(k) asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(a[k]) : "v"(m));
+// the multiply of a Philox round as rt_device.h SampleRng::refill compiles: 32 x 32 -> 64 (+ a 64-bit addend), carry-out to vcc
+#define OP_MAD64(k) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(a[k]) : "v"((uint32_t)m), "v"((uint32_t)c) : "vcc");
 #define OP_RCP(k) asm volatile("v_rcp_f32 %0, %0" : "+v"(a[k]));
 #define OP_SQRT(k) asm volatile("v_sqrt_f32 %0, %0" : "+v"(a[k]));
 #define OP_MOV(k) asm volatile("v_mov_b32 %0, %1" : "=v"(a[k]) : "v"(m));
@@ -84,6 +86,7 @@ KERNEL(add_u32, uint32_t, UINIT, OP_ADDU, (float)a[i])
 KERNEL(xor, uint32_t, UINIT, OP_XOR, (float)a[i])
 KERNEL(mul_lo, uint32_t, UINIT, OP_MULLO, (float)a[i])
 KERNEL(mul_hi, uint32_t, UINIT, OP_MULHI, (float)a[i])
+KERNEL(mad_u64_u32, uint64_t, (uint64_t)UINIT, OP_MAD64, (float)a[i])
 KERNEL(rcp, float, FINIT, OP_RCP, a[i])
 KERNEL(sqrt, float, FINIT, OP_SQRT, a[i])
 KERNEL(dep_fma, float, FINIT, OP_DEP_FMA, a[i])
@@ -157,7 +160,7 @@ int main() {
   printf("cycles per wave64 instruction per SIMD = s_memtime ticks / (waves per SIMD x instructions per wave)\n");
 #define ROW(name, n) run(#name, k_##name, cus, d_out, d_sink, n, wall_khz * 1e3);
   ROW(fma, 1) ROW(add, 1) ROW(sub, 1) ROW(mul, 1) ROW(max, 1) ROW(max3, 1) ROW(cmp, 1) ROW(cndmask, 1) ROW(mov, 1)
-  ROW(pk_mul, 1) ROW(pk_add, 1) ROW(pk_fma, 1) ROW(add_u32, 1) ROW(xor, 1) ROW(mul_lo, 1) ROW(mul_hi, 1) ROW(rcp, 1) ROW(sqrt, 1)
+  ROW(pk_mul, 1) ROW(pk_add, 1) ROW(pk_fma, 1) ROW(add_u32, 1) ROW(xor, 1) ROW(mul_lo, 1) ROW(mul_hi, 1) ROW(mad_u64_u32, 1) ROW(rcp, 1) ROW(sqrt, 1)
   ROW(dep_fma, 1) ROW(dep_add, 1) ROW(dep_max3, 1)
   ROW(box_mix22, 22)
   return 0;
