@@ -28,6 +28,15 @@ int rtg_debug_box_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint
 int rtg_debug_production_program(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
                                  uint32_t* words_out, uint32_t* origin_out, uint8_t* mask_out, size_t capacity);
 
+/* The camera plan of a lean program (scene option "box_camera"; csrc/rt_box_plan.h BOX_PLAN_COUNTS): the plan the launcher makes
+ * from the pass counts of its probe kernel, here from counts handed in.  The program is given as for rtg_debug_box_plan and
+ * planned as it stands (hand in rtg_debug_production_program's words to plan what production launches stage).  counts: one
+ * word per record, the number of probe walks out of n_rays in which that BOX passed (ignored for other records); any values are
+ * accepted, and every mask that comes back is a sound plan.  mask_out as for rtg_debug_box_plan.  Writes min(record count,
+ * capacity) bytes; returns the record count, or a negative rtg_status.  Works without a GPU. */
+int rtg_debug_camera_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records,
+                          const uint32_t* counts, uint64_t n_rays, uint8_t* mask_out, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -724,6 +724,7 @@ class Backend:
         # include/rtiow_gpu_debug.h (not part of ABI_SYMBOLS: no CPU restatement mirrors it)
         f("debug_box_plan", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u8p, C.c_size_t])
         f("debug_production_program", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u32p, c_u32p, c_u8p, C.c_size_t])
+        f("debug_camera_plan", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u32p, C.c_uint64, c_u8p, C.c_size_t])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -999,6 +1000,21 @@ class Builder:
             self.be.check(n)
         return out, origin, mask
 
+    def camera_plan(self, words, counts, n_rays):
+        """Host-only (product library): the camera plan (scene option box_camera; csrc/rt_box_plan.h BOX_PLAN_COUNTS) of the lean
+        program `words` ([n, 8] uint32, as flatten / production_program return them) from pass counts: counts[i] walks out of
+        n_rays passed BOX record i.  One uint8 per record as box_plan returns them; any counts are accepted."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if len(counts) != len(words):
+            raise ValueError("camera_plan: one count per record")
+        mask = np.zeros(len(words), dtype=np.uint8)
+        n = self.be._debug_camera_plan(None, None, 0, words.ctypes.data_as(c_u32p), len(words), counts.ctypes.data_as(c_u32p), int(n_rays),
+                                       mask.ctypes.data_as(c_u8p), len(mask))
+        if n < 0:
+            self.be.check(n)
+        return mask
+
     def bvh_sah(self, objs, exposure=(0.0, 1.0)):
         """Not in the reference: SAH-built Bvh; same results up to exact-t ties, fewer box tests."""
         arr = (C.c_uint32 * max(1, len(objs)))(*objs)
@@ -1034,7 +1050,7 @@ class Scene:
     # measurement / test hook: RTG_<OPTION>=<int> in the environment of the PYTHON process becomes
     # rtg_scene_set_option(scene, "<option>", <int>) -- the library itself reads no environment variable
     ENV_OPTIONS = ("kernel", "chunks", "lpt", "lpt_phase1", "lpt_deep", "lpt_shift", "ray_lds", "sync", "block", "wg_per_cu", "window",
-                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling")
+                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "box_camera", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling")
 
     def set_option(self, name, value):
         self.be.check(self.be._scene_set_option(self.h, name.encode(), int(value)))

@@ -29,7 +29,9 @@ constexpr uint32_t BOX_PLAN_PROBES = RT_BOX_PLAN_PROBES;
 constexpr bool BOX_PLAN_FULL = RT_BOX_PLAN_FULL != 0;
 // Which plan: the sure-pass subset, the tree DP on the probes' pass counts, or the same DP on a pass probability that needs no
 // ray -- a box's surface area over the area of the box around everything that is not a sky dome (at `box_plan`, "Choice").
-enum BoxPlanKind : int { BOX_PLAN_SURE = 0, BOX_PLAN_PROBE_DP = 1, BOX_PLAN_AREA = 2 };
+// BOX_PLAN_COUNTS: the DP on pass counts handed in from outside -- the camera plan, whose probe paths the GPU walks for the camera
+// a launch renders with (rt_camera_probe.h; option box_camera).
+enum BoxPlanKind : int { BOX_PLAN_SURE = 0, BOX_PLAN_PROBE_DP = 1, BOX_PLAN_AREA = 2, BOX_PLAN_COUNTS = 3 };
 constexpr BoxPlanKind BOX_PLAN_DEFAULT = BOX_PLAN_FULL ? BOX_PLAN_PROBE_DP : BOX_PLAN_SURE;
 // The plan of the rebuilt program (box_tree_rebuild below; option box_tree) and its probes.  The area model ships: no probe
 // walk at all.  0 / 1 keep the other two plans buildable for measurements (HISTORY.md "Box tree").
@@ -144,6 +146,37 @@ inline bool program_shape(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size
   }
   return true;
 }
+// A SPHERE record's centre, and the spheres that hold the box around all centres (a sky dome): no probe starts or bounces
+// there.  `starts` (optional): the other spheres with finite geometry, where the host probes begin.
+inline void sphere_centre(const uint32_t (*lo)[4], const uint32_t (*hi)[4], uint32_t j, float* c) {
+  for (int a = 0; a < 3; a++) c[a] = (hi[j][3] & F_TRANSLATE) ? as_f(lo[j][a]) : 0.f;
+}
+inline void enclosing_spheres(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size_t n, std::vector<uint8_t>* enclosing,
+                              std::vector<uint32_t>* starts = nullptr) {
+  std::vector<uint32_t> spheres;
+  for (size_t j = 0; j < n; j++)
+    if ((hi[j][3] & 0xffu) == OP_SPHERE) spheres.push_back((uint32_t)j);
+  float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t j : spheres) {
+    float c[3];
+    sphere_centre(lo, hi, j, c);
+    for (int a = 0; a < 3; a++) cmin[a] = fminf(cmin[a], c[a]), cmax[a] = fmaxf(cmax[a], c[a]);
+  }
+  enclosing->assign(n, 0);
+  for (uint32_t j : spheres) {
+    float cj[3];
+    sphere_centre(lo, hi, j, cj);
+    const float r = as_f(lo[j][3]);
+    float far2 = 0.f;  // squared distance to the farthest corner of that box
+    for (int a = 0; a < 3; a++) {
+      const float d = fmaxf(cmax[a] - cj[a], cj[a] - cmin[a]);
+      far2 += d * d;
+    }
+    const bool all = spheres.size() > 1 && far2 < r * r;
+    (*enclosing)[j] = all;
+    if (starts && !all && std::isfinite(r) && std::isfinite(cj[0]) && std::isfinite(cj[1]) && std::isfinite(cj[2])) starts->push_back(j);
+  }
+}
 }  // namespace box_plan_detail
 
 // Box pruning.  Statement: in the production walk an interior BOX j may be left out (its test taken as passed) without
@@ -178,12 +211,18 @@ inline bool program_shape(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size
 // random sphere that does not enclose the others, leaves along normal + in_unit_sphere, and bounces on like that one to three
 // times while it hits such a sphere.  BOX_PLAN_AREA is the same DP without a ray: n_pass(B) / rays is replaced by
 // min(1, SA(B) / SA_ref), the chance that a line through the scene's box also meets B (below, where n_pass is filled).
+// BOX_PLAN_COUNTS is the same DP once more, on n_pass handed in from outside: counts[j] walks out of count_rays passed BOX j
+// (the camera plan: paths from the camera a launch renders with, walked on the GPU -- rt_camera_probe.h).  The proof above
+// never asks where n_pass comes from: every subset of the choosable records is a sound plan, and the counts only decide which
+// subset is taken to be the cheapest.  So any counts are accepted -- zeros, counts above the ray count (clamped to it), counts
+// that rise from a parent to its child, which no walk produces -- and the mask is sound for all of them.
 //
 // mask[j] = BOX_FOLLOWER where follower[j] (the box-chains rule wins), BOX_PRUNED for the plan's records, else BOX_KEPT.
 // sure[j] (optional) = 1 for the pruned records that every probe passed.  A malformed program (a skip pointer that does
 // not nest) gets no pruned record.
 inline BoxPlan box_plan(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size_t n, const uint8_t* follower, uint8_t* mask,
-                        uint8_t* sure = nullptr, uint32_t n_probes = BOX_PLAN_PROBES, BoxPlanKind kind = BOX_PLAN_DEFAULT) {
+                        uint8_t* sure = nullptr, uint32_t n_probes = BOX_PLAN_PROBES, BoxPlanKind kind = BOX_PLAN_DEFAULT,
+                        const uint32_t* counts = nullptr, uint64_t count_rays = 0) {
   using namespace box_plan_detail;
   BoxPlan out;
   for (size_t j = 0; j < n; j++) {
@@ -211,35 +250,17 @@ inline BoxPlan box_plan(const uint32_t (*lo)[4], const uint32_t (*hi)[4], size_t
 
   // ---- probe walks: n_pass ----
   std::vector<uint64_t> n_pass(n, 0);
-  std::vector<uint32_t> spheres, starts;
-  for (size_t j = 0; j < n; j++)
-    if (op(j) == OP_SPHERE) spheres.push_back((uint32_t)j);
-  auto centre = [&](uint32_t j, float* c) {
-    for (int a = 0; a < 3; a++) c[a] = (hi[j][3] & F_TRANSLATE) ? as_f(lo[j][a]) : 0.f;
-  };
-  // a sphere that holds the box around all centres (a sky dome): no probe starts or bounces there
-  float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (uint32_t j : spheres) {
-    float c[3];
-    centre(j, c);
-    for (int a = 0; a < 3; a++) cmin[a] = fminf(cmin[a], c[a]), cmax[a] = fmaxf(cmax[a], c[a]);
-  }
-  std::vector<uint8_t> enclosing(n, 0);
-  for (uint32_t j : spheres) {
-    float cj[3];
-    centre(j, cj);
-    const float r = as_f(lo[j][3]);
-    float far2 = 0.f;  // squared distance to the farthest corner of that box
-    for (int a = 0; a < 3; a++) {
-      const float d = fmaxf(cmax[a] - cj[a], cj[a] - cmin[a]);
-      far2 += d * d;
-    }
-    const bool all = spheres.size() > 1 && far2 < r * r;
-    enclosing[j] = all;
-    if (!all && std::isfinite(r) && std::isfinite(cj[0]) && std::isfinite(cj[1]) && std::isfinite(cj[2])) starts.push_back(j);
-  }
+  std::vector<uint32_t> starts;
+  std::vector<uint8_t> enclosing;
+  enclosing_spheres(lo, hi, n, &enclosing, &starts);
+  auto centre = [&](uint32_t j, float* c) { sphere_centre(lo, hi, j, c); };
   uint64_t n_rays = 0;
-  if (!starts.empty() && kind != BOX_PLAN_AREA) {
+  if (kind == BOX_PLAN_COUNTS) {
+    if (!counts) return out;
+    for (size_t j = 0; j < n; j++)
+      if (op(j) == OP_BOX) n_pass[j] = counts[j] < count_rays ? counts[j] : count_rays;
+    n_rays = count_rays;
+  } else if (!starts.empty() && kind != BOX_PLAN_AREA) {
     Rng rng{0x626f78706c616e31ull ^ (uint64_t)n};
     const float t_near = 0.001f;
     while (n_rays < n_probes) {

@@ -23,6 +23,7 @@
 #include "../../include/rtiow_gpu_debug.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
+#include "rt_camera_probe.h"
 #include "rt_retire.h"
 #include "rt_denoise.h"
 #include "rt_features.h"
@@ -99,6 +100,25 @@ struct LaunchCtx {
   size_t features_bytes = 0;
 };
 
+// The camera plan of ONE (program, camera) pair (rt_camera_probe.h, rtg_launch.inc camera_plan): the probe's counts on their way
+// to the host, then the record offsets of the image that leaves out what the tree DP picks from those counts.  A scene keeps
+// CAMERA_PLANS of them, least recently used evicted; the buffers stay with the entry (every program of a scene has n_prog records).
+constexpr int CAMERA_PLANS = 4;
+constexpr size_t CAMERA_KEY_BYTES = sizeof(DevCamera) + 2;
+struct CameraPlan {
+  enum State { FREE, PROBING, PLANNED } state = FREE;
+  unsigned char key[CAMERA_KEY_BYTES] = {};  // the DevCamera bytes, then which program is staged: box_tree, box_chains
+  uint64_t stamp = 0;            // last use (rtg_scene::cam_clock)
+  hipEvent_t ev = nullptr;       // behind the copy of the counts, then behind the upload of the table
+  hipStream_t up_stream = nullptr;  // ... the stream that upload went to (a launch on another stream waits for ev)
+  uint32_t* d_counts = nullptr;  // n + 1 words: the probe's n_pass and its ray count
+  uint32_t* h_words = nullptr;   // pinned, 2 n + 1 words: the counts, then the offsets on their way up
+  uint32_t* d_off = nullptr;     // n words: the record offsets of the camera's image
+  uint32_t bytes = 0;            // ... and its size
+  uint32_t n_pruned = 0, n_rays = 0;
+  float plan_ms = 0.f;           // host time of the DP and the table (option verbose, tools/camera_plan_cost.py)
+};
+
 // The LDS images of ONE lean program (rt_pool.h): the full one, the one without box-chain followers and the ones without the
 // records of the pruning plan.  A scene has two: the reference program's and the rebuilt one's (rt_box_plan.h box_tree_rebuild).
 struct LeanImages {
@@ -120,6 +140,12 @@ struct LeanImages {
   std::vector<uint8_t> plan_mask;
   std::vector<uint8_t> follower;
   int slot = 12;               // first of this program's three offset tables in rtg_scene::buffers
+  // camera plan: the host copy of the program, whether program_shape accepts it (-1: not asked yet; 0: no probe, no camera plan)
+  // and which of its spheres end a probe path (rt_camera_probe.h camera_probe_stops), on the device from the first probe on
+  const std::vector<Packet>* h_lo = nullptr;
+  const std::vector<Packet>* h_hi = nullptr;
+  int probe_ok = -1;
+  uint8_t* d_stop = nullptr;
 };
 
 struct rtg_scene {
@@ -158,6 +184,14 @@ struct rtg_scene {
   // box tree (rt_box_plan.h box_tree_rebuild): 1 = production launches of the staged lean pool kernel (and, with box_prune = 2,
   // its counting launches) walk the program whose Bvh regions are rebuilt over the same leaf order; 0 = the reference program
   int box_tree = 1;
+  // camera plan (rtg_launch.inc camera_plan): 1 = launches that stage a pruned image probe the camera they render with once, when
+  // they are large enough, and every later launch with that camera stages the image planned from the probe's counts; 2 = every
+  // such launch, planned before it runs (tests and measurements); 0 = off
+  int box_camera = 1;
+  int cam_paths = (int)CAMERA_PROBE_PATHS, cam_bounces = (int)CAMERA_PROBE_BOUNCES, cam_trips = (int)CAMERA_PROBE_TRIPS;  // options box_camera_paths / _bounces / _trips (the sweeps of profiles/r24_camera_plan/)
+  CameraPlan cam_plans[CAMERA_PLANS];
+  uint64_t cam_clock = 0;
+  std::vector<Packet> t_lo, t_hi;  // host copy of the rebuilt program (the reference program's: h_lo / h_hi below)
   LeanImages ref;              // the reference program (dev.lo / dev.hi; offset tables in buffers[6], [12], [13], [14])
   LeanImages tree;             // the rebuilt one (buffers[15], [16]; tables in [17] .. [20]); tree.lo = nullptr: no region was rebuilt
   bool tree_tried = false;     // ... and whether the rebuild has run
@@ -684,6 +718,8 @@ static int tree_program(rtg_scene* s) {
   if ((rc = lean_images(s, &s->tree, lo, hi, 17)) || (rc = lean_plan(s, &s->tree, lo, hi, BOX_TREE_PLAN))) return rc;
   if (!s->box_chains && (rc = prune_table(s, &s->tree, 0))) return rc;
   s->tree.lo = (const uint4*)s->buffers[15], s->tree.hi = (const uint4*)s->buffers[16];
+  s->t_lo.swap(lo), s->t_hi.swap(hi);
+  s->tree.h_lo = &s->t_lo, s->tree.h_hi = &s->t_hi;
   return RTG_OK;
 }
 
@@ -700,6 +736,14 @@ void rtg_scene_destroy(rtg_scene* s) {
     if (c.ev1) (void)hipEventDestroy(c.ev1);
     if (c.done) (void)hipEventDestroy(c.done);
   }
+  for (CameraPlan& c : s->cam_plans) {
+    if (c.ev) (void)hipEventDestroy(c.ev);
+    if (c.d_counts) (void)hipFree(c.d_counts);
+    if (c.d_off) (void)hipFree(c.d_off);
+    if (c.h_words) (void)hipHostFree(c.h_words);
+  }
+  for (LeanImages* im : {&s->ref, &s->tree})
+    if (im->d_stop) (void)hipFree(im->d_stop);
   if (s->d_frame) (void)hipFree(s->d_frame);
   if (s->d_lights) (void)hipFree(s->d_lights);
   if (s->d_sampled) (void)hipFree(s->d_sampled);
@@ -792,6 +836,7 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
     s->plannable = s->dev.lds_image_bytes - LDS_BOX_BYTES * (s->n_box / 2u) <= 160u * 1024u;
     if (s->plannable) {
       s->h_lo = fs.lo, s->h_hi = fs.hi;
+      s->ref.h_lo = &s->h_lo, s->ref.h_hi = &s->h_hi;
       if ((s->box_tree && (rc = tree_program(s))) || (!s->tree.lo && (rc = ref_plan(s)))) {
         rtg_scene_destroy(s);
         return rc;
@@ -857,6 +902,20 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "box_prune") {                                  // 0: no interior box pruned; 1: production launches; 2: counting launches too (rtg_scene above)
     if (value < 0 || value > 2) return fail(RTG_ERR_INVALID, "box_prune: 0 .. 2");
     s->box_prune = value;
+  }
+  else if (k == "box_camera") {                                 // camera plan: 0 off, 1 launches that are large enough (default), 2 every launch, planned before it runs
+    if (value < 0 || value > 2) return fail(RTG_ERR_INVALID, "box_camera: 0 .. 2");
+    s->box_camera = value;
+  }
+  else if (k == "box_camera_paths" || k == "box_camera_bounces" || k == "box_camera_trips") {
+    // measurement switches of the probe (profiles/r24_camera_plan/ sweep.txt, sweep_trips.txt): paths per camera, bounces per path,
+    // records a path may visit.  They are not part of a plan's key, so the handle's plans are dropped and made again with the new values.
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // (kernels in flight may read a plan's table)
+    for (CameraPlan& c : s->cam_plans) c.state = CameraPlan::FREE;
+    if (k == "box_camera_paths") s->cam_paths = std::min(1 << 20, std::max(1, value));
+    else if (k == "box_camera_bounces") s->cam_bounces = std::min(16, std::max(0, value));
+    else s->cam_trips = std::max(1, value);
   }
   else if (k == "bvh4") {
     if (value && !s->wide_bytes) return fail(RTG_ERR_INVALID, "bvh4: the scene is not one Bvh of spheres (no 4-wide image)");

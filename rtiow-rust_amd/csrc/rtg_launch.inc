@@ -206,6 +206,108 @@ static hipError_t sample_passes(rtg_scene* s, const DevParams& d, float* d_out, 
   return hipSuccess;
 }
 
+// ---- camera plan (option box_camera; rt_camera_probe.h, rt_box_plan.h BOX_PLAN_COUNTS) ----------------------------------------
+// The scene's plan (lean_plan) is made from box areas and knows nothing about where the rays go.  The pair (scene, camera)
+// stays the same from call to call -- the slices of a progressive frame, the sample passes of a large one, repeated frames -- so
+// the launcher keeps a plan per camera: the first launch that sees a camera enqueues the probe kernel in front of itself, with
+// an asynchronous copy of the counts to pinned memory and an event behind it, and stages the scene's image; the next launch
+// with that camera (the next sample pass of the same call included) waits for the event, runs the tree DP on the counts,
+// uploads the offsets table on its stream and stages the camera's image, as does every launch after it.
+//
+// A launch probes when the probe costs it at most 1 %.  CAMERA_PLAN_MIN_SAMPLES = probe time / 1 % / time per sample:
+//   probe kernel, book-1's rebuilt program (1 455 records), 4 108 paths x 2 bounces, at most 64 records per path, one MI355X
+//     (rocprofv3 --kernel-trace --stats over tools/camera_plan_cost.py, 5 launches): 41 us, rounded up to 42 below (profiles/
+//     r24_camera_plan/probe_kernel_stats.csv; the earlier versions of the kernel, 73 .. 126 us: README.txt there)
+//   time per sample of the launches that gain, book-1 1200x800x50 on the parent commit: 6.01 ms / 48 M samples = 0.1252 ns
+//   42 us / 1 % / 0.1252 ns = 33.5 M samples (book-1 1200x800x50 is 48 M)
+constexpr uint64_t CAMERA_PLAN_MIN_SAMPLES = 33500000ull;
+
+static hipError_t camera_plan_make(rtg_scene* s, const LeanImages& im, CameraPlan* e, bool chains, hipStream_t stream) {
+  hipError_t err = hipEventSynchronize(e->ev);  // (recorded in front of the launch that probed: long past)
+  if (err != hipSuccess) return err;
+  const size_t n = im.h_hi->size();
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> mask(n), drop(n);
+  e->n_rays = e->h_words[n];
+  e->n_pruned = box_plan(reinterpret_cast<const uint32_t (*)[4]>(im.h_lo->data()), reinterpret_cast<const uint32_t (*)[4]>(im.h_hi->data()), n, im.follower.data(),
+                         mask.data(), nullptr, 0u, BOX_PLAN_COUNTS, e->h_words, e->n_rays).n_pruned;
+  for (size_t i = 0; i < n; i++) drop[i] = mask[i] == BOX_PRUNED || (chains && mask[i] == BOX_FOLLOWER);
+  uint32_t* off = e->h_words + n + 1u;
+  e->bytes = lds_image_offsets(im.plan_ops.data(), n, off, drop.data());
+  e->plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if ((err = hipMemcpyAsync(e->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream)) != hipSuccess) return err;
+  if ((err = hipEventRecord(e->ev, stream)) != hipSuccess) return err;
+  e->up_stream = stream, e->state = CameraPlan::PLANNED;
+  if (s->verbose)
+    fprintf(stderr, "[rtg] camera plan: %u rays probed, %u interior record(s) left out (the scene's plan: %u), image %u B, DP + table %.3f ms\n", e->n_rays, e->n_pruned,
+            im.n_pruned, e->bytes, e->plan_ms);
+  return hipSuccess;
+}
+
+// The camera's plan for a launch of `samples` samples that would stage the pruned image of `im` (`tree`: the rebuilt program):
+// *out = the entry whose table the launch stages, nullptr = the scene's own.
+static hipError_t camera_plan(rtg_scene* s, LeanImages& im, bool tree, const DevCamera& cam, hipStream_t stream, uint64_t samples, const CameraPlan** out) {
+  *out = nullptr;
+  if (!s->box_camera || !im.h_lo || !im.h_hi) return hipSuccess;
+  const size_t n = im.h_hi->size();
+  if (im.probe_ok < 0) {  // skip pointers point forward and nest: the probe's walk is bounded (rt_camera_probe.h)
+    box_plan_detail::Shape shape;
+    im.probe_ok = n == s->n_prog && n <= CAMERA_PROBE_MAX_RECORDS && box_plan_detail::program_shape(reinterpret_cast<const uint32_t (*)[4]>(im.h_lo->data()), reinterpret_cast<const uint32_t (*)[4]>(im.h_hi->data()), n, &shape) &&
+                  shape.n_prunable != 0u;
+  }
+  if (!im.probe_ok) return hipSuccess;
+  const bool chains = s->box_chains != 0;
+  unsigned char key[CAMERA_KEY_BYTES];
+  memcpy(key, &cam, sizeof(DevCamera));
+  key[sizeof(DevCamera)] = tree ? 1 : 0, key[sizeof(DevCamera) + 1] = chains ? 1 : 0;
+  CameraPlan* e = nullptr;
+  for (CameraPlan& c : s->cam_plans)
+    if (c.state != CameraPlan::FREE && !memcmp(c.key, key, CAMERA_KEY_BYTES)) e = &c;
+  hipError_t err;
+  if (!e) {
+    if (s->box_camera == 1 && samples < CAMERA_PLAN_MIN_SAMPLES) return hipSuccess;
+    for (CameraPlan& c : s->cam_plans)  // a free entry, else the least recently used
+      if (c.state == CameraPlan::FREE && (!e || e->state != CameraPlan::FREE)) e = &c;
+      else if (!e || (e->state != CameraPlan::FREE && c.stamp < e->stamp)) e = &c;
+    if (e->state != CameraPlan::FREE) {  // evicted: kernels in flight, on whichever stream, may still read its table -- a fifth camera on a
+                                         // handle waits for the whole device once (DESIGN.md "Camera plan", costs)
+      if ((err = hipDeviceSynchronize()) != hipSuccess) return err;
+      e->state = CameraPlan::FREE;
+    }
+    if (!e->ev && (err = hipEventCreateWithFlags(&e->ev, hipEventDisableTiming)) != hipSuccess) return err;
+    if (!e->d_counts && (err = hipMalloc((void**)&e->d_counts, (n + 1u) * sizeof(uint32_t))) != hipSuccess) return err;
+    if (!e->d_off) {
+      if ((err = hipMalloc((void**)&e->d_off, n * sizeof(uint32_t))) != hipSuccess) return err;
+      s->bytes += (2u * n + 1u) * sizeof(uint32_t);
+    }
+    if (!e->h_words && (err = hipHostMalloc((void**)&e->h_words, (2u * n + 1u) * sizeof(uint32_t))) != hipSuccess) return err;
+    if (!im.d_stop) {
+      std::vector<uint8_t> stop;
+      camera_probe_stops(reinterpret_cast<const uint32_t (*)[4]>(im.h_lo->data()), reinterpret_cast<const uint32_t (*)[4]>(im.h_hi->data()), n, &stop);
+      if ((err = hipMalloc((void**)&im.d_stop, n)) != hipSuccess) return err;
+      if ((err = hipMemcpy(im.d_stop, stop.data(), n, hipMemcpyHostToDevice)) != hipSuccess) return err;
+      s->bytes += n;
+    }
+    CameraProbe p{im.lo, im.hi, im.d_stop, e->d_counts, (uint32_t)n, 0u, 0u, (uint32_t)s->cam_bounces, (uint32_t)s->cam_trips, 0.001f};
+    camera_probe_grid(cam, (uint32_t)s->cam_paths, &p.grid_w, &p.grid_h);
+    if ((err = hipMemsetAsync(e->d_counts, 0, (n + 1u) * sizeof(uint32_t), stream)) != hipSuccess) return err;
+    int probe_per_cu = 0;  // (raises the kernel's dynamic-LDS limit when the program needs more than the default 64 KB)
+    if ((err = kernel_setup(s, (const void*)camera_probe_kernel, (int)CAMERA_PROBE_BLOCK, camera_probe_lds_bytes(n), &probe_per_cu)) != hipSuccess) return err;
+    hipLaunchKernelGGL(camera_probe_kernel, dim3((p.grid_w * p.grid_h + CAMERA_PROBE_WALKERS - 1u) / CAMERA_PROBE_WALKERS), dim3(CAMERA_PROBE_BLOCK), camera_probe_lds_bytes(n), stream, p, cam);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = hipMemcpyAsync(e->h_words, e->d_counts, (n + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
+    if ((err = hipEventRecord(e->ev, stream)) != hipSuccess) return err;
+    memcpy(e->key, key, CAMERA_KEY_BYTES);
+    e->state = CameraPlan::PROBING, e->stamp = ++s->cam_clock;
+    if (s->box_camera != 2) return hipSuccess;  // this launch stages the scene's image; the next one makes the plan
+  }
+  e->stamp = ++s->cam_clock;
+  if (e->state == CameraPlan::PROBING && (err = camera_plan_make(s, im, e, chains, stream)) != hipSuccess) return err;
+  if (e->up_stream != stream && (err = hipStreamWaitEvent(stream, e->ev, 0)) != hipSuccess) return err;
+  *out = e;
+  return hipSuccess;
+}
+
 // Lean scenes, ray-pool kernel (rt_pool.h): one persistent 1024-thread workgroup per CU.
 // `sl`: the samples [sl.begin, d.ns) of a progressive frame's slice -- pass sizing, chunking and launch geometry follow this
 // call's samples, not the frame's.  A counts call (sl.counts) runs over its list of active pixels: `pix_work` is the list's
@@ -270,9 +372,37 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     if (pool_lds_bytes(dev.lds_image_bytes, s->n_mat, waves, true, false) > lds_limit) tree = false;  // (the global-memory walk keeps the reference program)
   }
   if (!tree && s->ref.lo != nullptr) choose(s->ref);
-  const LeanImages& im = tree ? s->tree : s->ref;
+  LeanImages& im = tree ? s->tree : s->ref;
+  // Option box_camera: a launch that stages the pruned image takes the table planned for the camera it renders with, once there
+  // is one (camera_plan above).  The camera's image may be LARGER than the scene's: the area model leaves out a box that covers
+  // half of its parent, the counts keep it when few of the probe's rays pass it (tests/test_camera_plan.py has such a program).
+  // So the table is taken only where that is safe.  Before the launch is sized: when the image is no larger than the scene's, or
+  // picks the same kernel (program staged, hot slot fields in LDS) -- a plan never moves a scene to a slower kernel.  In a later
+  // pass of the call, whose dynamic LDS was sized below from the image of its first pass and which lays LDS out from the image
+  // size it is given: only when the camera's image is no larger than that one; else the call keeps its table, and the next call
+  // is sized for the camera's.
+  const bool camera_ok = prune && pool_lds_bytes(dev.lds_image_bytes, s->n_mat, waves, true, false) <= lds_limit;
+  const CameraPlan* cplan = nullptr;
+  uint32_t sized_for = 0;  // the image the launch was sized for, 0 = not sized yet
+  auto kernel_for = [&](uint32_t bytes) {  // bit 0: the program is staged, bit 1: the hot slot fields live in LDS
+    const bool u = bytes != 0 && pool_lds_bytes(bytes, s->n_mat, waves, true, false) <= lds_limit;
+    const bool r = s->ray_lds && pool_lds_bytes(bytes, s->n_mat, waves, u, true) <= lds_limit && (!u || bytes < (1u << 17));
+    return (u ? 1u : 0u) | (r ? 2u : 0u);
+  };
+  auto camera_image = [&]() {
+    if (!camera_ok || cplan) return hipSuccess;
+    const CameraPlan* cp = nullptr;
+    hipError_t ec = camera_plan(s, im, tree, cam, stream, pix_work * ns_call, &cp);
+    if (ec != hipSuccess || !cp) return ec;
+    const bool take = sized_for ? cp->bytes <= sized_for : (cp->bytes <= dev.lds_image_bytes || kernel_for(cp->bytes) == kernel_for(dev.lds_image_bytes));
+    if (take) cplan = cp, dev.lds_off = cp->d_off, dev.lds_image_bytes = cp->bytes;
+    else if (s->verbose) fprintf(stderr, "[rtg] camera plan: image %u B against %u B: not staged by this %s\n", cp->bytes, sized_for ? sized_for : dev.lds_image_bytes, sized_for ? "call" : "launch");
+    return hipSuccess;
+  };
+  if (hipError_t ec = camera_image(); ec != hipSuccess) return ec;
   if (wide) dev.lds_off = (const uint32_t*)s->buffers[7], dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
   const uint32_t image = dev.lds_image_bytes;
+  sized_for = image;
   bool use_lds = image != 0 && pool_lds_bytes(image, s->n_mat, waves, true, false) <= lds_limit;
   if (wide && !use_lds) return hipErrorNotSupported;  // (rtg_scene_set_option refuses bvh4 for images that do not fit)
   // (hot slot fields in LDS keep best_pc as 16 bits = 14 bits of image offset / 8 + 2 bits of scatter tries: images < 128 KB)
@@ -290,9 +420,10 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
   if (s->verbose && (chains || prune) && use_lds)
-    fprintf(stderr, "[rtg] pool: %s program (%u region(s) rebuilt in %.2f ms), box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
-            tree ? "rebuilt" : "reference", s->n_regions, s->tree_ms, im.n_followers, chains || (prune && s->box_chains) ? " dropped" : " kept", im.n_pruned, prune ? " dropped" : " kept", im.plan_ms, image,
-            s->n_prog - (chains || (prune && s->box_chains) ? im.n_followers : 0u) - (prune ? im.n_pruned : 0u), s->n_prog, im.chain_bytes ? im.chain_bytes : im.bytes, im.bytes);
+    fprintf(stderr, "[rtg] pool: %s program (%u region(s) rebuilt in %.2f ms), box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (%s plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
+            tree ? "rebuilt" : "reference", s->n_regions, s->tree_ms, im.n_followers, chains || (prune && s->box_chains) ? " dropped" : " kept", cplan ? cplan->n_pruned : im.n_pruned, prune ? " dropped" : " kept",
+            cplan ? "the camera's" : "the scene's", cplan ? cplan->plan_ms : im.plan_ms, image,
+            s->n_prog - (chains || (prune && s->box_chains) ? im.n_followers : 0u) - (prune ? (cplan ? cplan->n_pruned : im.n_pruned) : 0u), s->n_prog, im.chain_bytes ? im.chain_bytes : im.bytes, im.bytes);
   PoolLaunch L{KernelKind::lean_pool, bt, 0, lds, geo, POOL};
   hipError_t e = kernel_setup(s, (const void*)kernel, bt, lds, &L.per_cu);
   if (e != hipSuccess) return e;
@@ -312,6 +443,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
               s0, dp.ns, d.ns, grid, bt, L.per_cu, lds, (int)use_lds, (int)ray_lds, cm.n_chunks, cm.chunk, (cm.lpt_samples - (cm.lpt_samples ? s0 : 0u)) / (cm.chunk ? cm.chunk : 1u));
     hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
     if (eg != hipSuccess) return eg;
+    if (s0 != sl.begin && (eg = camera_image()) != hipSuccess) return eg;  // (a later pass: the plan its first pass probed for)
     launch_pass_setup(s, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, queue, stream);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                        s->cx->d_counters, s->pool_tune, s->cx->d_slots);

@@ -251,6 +251,27 @@ int rtg_debug_production_program(rtg_builder* b, const rtg_id* world, size_t n, 
   return (int)m;
 }
 
+// Host-only (include/rtiow_gpu_debug.h): the camera plan of a lean program from pass counts handed in -- the tree DP the launcher
+// runs on the counts of the probe kernel (rt_box_plan.h BOX_PLAN_COUNTS), over the program as given (no rebuild: hand in the
+// production program to plan what launches stage).  counts[i]: walks out of n_rays in which BOX i passed; any values are accepted.
+// Returns the record count, or a negative error code.
+int rtg_debug_camera_plan(rtg_builder* b, const rtg_id* world, size_t n, const uint32_t* words, size_t n_records, const uint32_t* counts,
+                          uint64_t n_rays, uint8_t* mask_out, size_t capacity) {
+  if (!counts) return fail(RTG_ERR_INVALID, "null argument");
+  std::vector<Packet> lo, hi;
+  bool lean = true;
+  int rc = debug_lean_program("rtg_debug_camera_plan", b, world, n, words, n_records, &lo, &hi, &lean);
+  if (rc) return rc;
+  std::vector<uint8_t> follower(hi.size(), 0), mask(hi.size(), 0);
+  if (lean && !hi.empty()) {
+    box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), follower.data());
+    box_plan(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), follower.data(), mask.data(), nullptr, 0u,
+             BOX_PLAN_COUNTS, counts, n_rays);
+  }
+  if (mask_out) std::memcpy(mask_out, mask.data(), std::min(mask.size(), capacity));
+  return (int)hi.size();
+}
+
 int rtg_debug_math(int device, int op, size_t n, const float* in, const float* in2, float* out) {
   if (!in || !out || op < 0 || op > 5 || (op == 5 && !in2)) return fail(RTG_ERR_INVALID, "bad argument");
   int ndev = 0;
