@@ -51,6 +51,16 @@ class Params(C.Structure):
                 ("nranks", C.c_uint32), ("flags", C.c_uint32), ("sample_begin", C.c_uint32)]
 
 
+class QueryParams(C.Structure):
+    """include/rtiow_gpu_query.h rtg_query_params (32 bytes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("first_index", C.c_uint64),
+                ("t_min", C.c_float), ("reserved2", C.c_uint32)]
+
+
+def make_query_params(seed=1, t_min=0.001, first_index=0):
+    return QueryParams(struct_size=C.sizeof(QueryParams), seed=seed, first_index=first_index, t_min=t_min)
+
+
 class Retire(C.Structure):
     """include/rtiow_gpu.h rtg_retire: the block behind the count plane of an RTG_FLAG_RETIRE frame (64 bytes).  The caller
     sets target_se / min_samples / radius; every accepted call writes the out-fields active .. samples_held."""
@@ -659,6 +669,8 @@ ABI_SYMBOLS = [
     "object_constant_medium", "object_bvh", "object_bvh_sah", "camera_look", "scene_create", "scene_destroy",
     "scene_set_option", "scene_info", "par_cast", "par_cast_device", "par_cast_multi", "multi_reset", "debug_hit_top", "debug_samples", "debug_math", "debug_flatten", "debug_flatten_pool2", "tonemap", "tonemap_device",
 ]
+# every symbol include/rtiow_gpu_query.h declares: beside the ABI above, not part of it (no CPU restatement mirrors ray queries)
+QUERY_SYMBOLS = ["query_closest", "query_closest_device", "query_occluded", "query_occluded_device"]
 
 
 class Backend:
@@ -725,6 +737,12 @@ class Backend:
         f("debug_box_plan", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u8p, C.c_size_t])
         f("debug_production_program", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u32p, c_u32p, c_u8p, C.c_size_t])
         f("debug_camera_plan", C.c_int, [C.c_void_p, c_u32p, C.c_size_t, c_u32p, C.c_size_t, c_u32p, C.c_uint64, c_u8p, C.c_size_t])
+        # include/rtiow_gpu_query.h (QUERY_SYMBOLS): pointers as void*, so that host arrays and device addresses both pass
+        qp, st = C.POINTER(QueryParams), C.POINTER(Stats)
+        f("query_closest", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, C.c_void_p, st])
+        f("query_closest_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, C.c_void_p, C.c_void_p, st])
+        f("query_occluded", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, st])
+        f("query_occluded_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, C.c_void_p, st])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -1050,7 +1068,7 @@ class Scene:
     # measurement / test hook: RTG_<OPTION>=<int> in the environment of the PYTHON process becomes
     # rtg_scene_set_option(scene, "<option>", <int>) -- the library itself reads no environment variable
     ENV_OPTIONS = ("kernel", "chunks", "lpt", "lpt_phase1", "lpt_deep", "lpt_shift", "ray_lds", "sync", "block", "wg_per_cu", "window",
-                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "box_camera", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling")
+                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "box_camera", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling", "query_lds", "query_refill")
 
     def set_option(self, name, value):
         self.be.check(self.be._scene_set_option(self.h, name.encode(), int(value)))
@@ -1454,6 +1472,51 @@ class Scene:
         self.be.check(self.be._debug_hit_top(self.h, n, rays.ctypes.data_as(c_f32p), seed, t_near,
                                              out.ctypes.data_as(c_f32p), mat.ctypes.data_as(c_u32p)))
         return out, mat
+
+    # ---- ray queries (include/rtiow_gpu_query.h) ---------------------------------------------------------------------
+    def _query(self, what, width, rays, seed, t_min, first_index, stream, stats, outputs):
+        """One query call.  `rays`: a numpy array -> the host entry point, numpy results; a torch tensor on the scene's
+        device -> the device entry point on `stream` (default: the current torch stream), torch results, no host round
+        trip.  `outputs`: ((columns or None, numpy dtype, torch dtype name), ...)."""
+        p = make_query_params(seed, t_min, first_index)
+        st = Stats.new() if stats else None
+        st_arg = C.byref(st) if stats else None
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if not rays.is_cuda:
+                raise ValueError("%s: a torch tensor must live on the scene's device (pass a numpy array for host rays)" % what)
+            if rays.dtype != torch.float32 or not rays.is_contiguous():   # (no temporary copy: the call returns before the kernel reads it)
+                raise ValueError("%s: the rays must be a contiguous float32 tensor" % what)
+            rays = rays.reshape(-1, width)
+            n = rays.shape[0]
+            outs = [torch.empty((n, c) if c else (n,), dtype=getattr(torch, t), device=rays.device) for c, _, t in outputs]
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device)
+            if isinstance(stream, torch.cuda.Stream):   # the results are written on `stream`, whatever stream allocated them
+                for o in outs:
+                    o.record_stream(stream)
+            hs = _stream(stream)
+            fn = getattr(self.be, "_query_%s_device" % what)
+            self.be.check(fn(self.h, n, _device_ptr(rays), C.byref(p), *[_device_ptr(o) for o in outs], hs, st_arg))
+        else:
+            rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, width)
+            n = rays.shape[0]
+            outs = [np.zeros((n, c) if c else (n,), dtype=d) for c, d, _ in outputs]
+            fn = getattr(self.be, "_query_%s" % what)
+            self.be.check(fn(self.h, n, rays.ctypes.data, C.byref(p), *[o.ctypes.data for o in outs], st_arg))
+        res = outs[0] if len(outs) == 1 else tuple(outs)
+        return (res, st.as_dict()) if stats else res
+
+    def closest_hit(self, rays, seed=1, t_min=0.001, first_index=0, stream=None, stats=False):
+        """Closest hit of the caller's rays, [n, 7] (origin, direction, time): (out [n, 8] float32 = (hit, t, p, normal),
+        material [n] -- uint32 in numpy, int32 in torch, 0xffffffff / -1 on a miss).  One World::hit_top per ray over
+        [t_min, f32::MAX); media draw from the stream (seed, first_index + i).  stats=True: ((out, material), stats)."""
+        return self._query("closest", 7, rays, seed, t_min, first_index, stream, stats, ((8, np.float32, "float32"), (None, np.uint32, "int32")))
+
+    def occluded(self, rays, seed=1, t_min=0.001, first_index=0, stream=None, stats=False):
+        """Is anything hit in [t_min, t_max)?  rays [n, 8]: (origin, direction, time, t_max); uint8 [n].  A ConstantMedium
+        blocks with probability 1 - transmittance.  stats=True: (out, stats)."""
+        return self._query("occluded", 8, rays, seed, t_min, first_index, stream, stats, ((None, np.uint8, "uint8"),))
 
     def debug_samples(self, camera, nx, ny, ns, xs, ys, samples, seed=0xDEADBEEF, trace_kernel=False, **kw):
         """trace_kernel=True: read the keys out of the production ray-pool kernel's per-sample trace (whole frame rendered)."""

@@ -21,6 +21,7 @@
 
 #include "../../include/rtiow_gpu.h"
 #include "../../include/rtiow_gpu_debug.h"
+#include "../../include/rtiow_gpu_query.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -33,6 +34,7 @@
 #include "rt_pool2.h"
 #include "rt_trace.h"
 #include "rt_light.h"
+#include "rt_query.h"
 #include "scene_builder.h"
 
 using namespace rtg;
@@ -236,6 +238,10 @@ struct rtg_scene {
   LightTable lights{nullptr, nullptr, 0};  // d_lights / d_sampled: .n = 0 until uploaded, and when there is nothing to sample
   void* d_lights = nullptr;
   void* d_sampled = nullptr;
+  // Scene option query_lds (include/rtiow_gpu_query.h): which kernel answers ray queries -- 0 = always the general one, 2 = the
+  // lean kernel whenever the program is lean and fits LDS, 1 = that kernel from QUERY_LDS_MIN_RAYS rays upward (rtg_query.inc)
+  int query_lds = 1;
+  int query_refill = 16;  // ... and the finished lanes of a wave at which the lean kernel runs its refill arm (rt_query.h; measurement switch)
   LaunchCtx ctx[RTG_MAX_FRAMES];           // frames in flight
   int n_ctx = 1, next_ctx = 0;
   LaunchCtx* cx = &ctx[0];                 // the context of the call being made (ctx_acquire)
@@ -965,6 +971,11 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
     }
     s->light_sampling = value;
   }
+  else if (k == "query_lds") {                                  // ray queries: 0 the general kernel, 1 automatic (default), 2 the lean kernel whenever the program fits
+    if (value < 0 || value > 2) return fail(RTG_ERR_INVALID, "query_lds: 0 .. 2");
+    s->query_lds = value;
+  }
+  else if (k == "query_refill") s->query_refill = std::min(64, std::max(1, value));
   else if (k == "small_frames") s->small_frames = value;        // 0: one geometry for every frame size (measurement switch)
   else if (k == "verbose") s->verbose = value;                  // print launch geometry / schedule statistics to stderr
   else if (k == "window") s->window = value;                    // full-feature kernel: records staged in LDS, -1 = automatic
@@ -1221,3 +1232,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 #include "rtg_probes.inc"
 
 }  // extern "C"
+
+#include "rtg_query.inc"
