@@ -159,7 +159,7 @@ inline
 
 namespace rtg {
 
-// Work item w of the rank P.rank -> its pixel (rt_pool.h work_to_pixel, as pack_tiles_kernel): every word of every travelling
+// Work item w of the rank P.rank -> its pixel (rt_pool.h work_to_pixel; items beyond the image are padding): every word of every travelling
 // plane of that pixel, frame -> packed.  On the frame side the lanes of a wave follow the 8-pixel row segments of an 8x8 block
 // (96 contiguous bytes per segment of a 3-word plane); on the packed side they are consecutive dwords.  Padding items (beyond the
 // image) pack +0.  The loops are fully unrolled over the at most 5 x 3 words, so the PlaneSet stays in the kernel arguments.

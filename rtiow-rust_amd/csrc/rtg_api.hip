@@ -72,34 +72,45 @@ struct rtg_builder {
 constexpr int RTG_MAX_FRAMES = 4;
 // The kernel that rendered a frame (rtg_launch.inc launch_render)
 enum class KernelKind { baseline, lean_pool, full_pool, lock_step, pool2 };
+// A device allocation that a handle owns and grows on demand: it never shrinks; when it is too small it is freed and allocated
+// anew (nothing is held when that fails).  The device it lives on is current when grow / release are called.
+struct DevMem {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipError_t grow(size_t need) {
+    if (need <= bytes) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&p, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr, bytes = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
 struct LaunchCtx {
   unsigned long long* d_counters = nullptr;  // [0..4] N/P/H/rays/draws, [7] = work-queue head (persistent kernel), [8..] schedule statistics
   hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
   bool busy = false;            // `done` was recorded and not waited for yet
-  float* d_stack = nullptr;     // full-feature pool kernel: per-wave transform stacks
-  size_t stack_bytes = 0;
-  uint32_t* d_slots = nullptr;  // ray-pool path slots when they live in global memory
-  size_t slots_bytes = 0;
-  float* d_scratch = nullptr;   // per-sample colours (sample passes: rtg_launch.inc)
-  size_t scratch_bytes = 0;
+  DevMem stack;                 // float: full-feature pool kernel: per-wave transform stacks
+  DevMem slots;                 // uint32_t: ray-pool path slots when they live in global memory
+  DevMem scratch;               // float: per-sample colours (sample passes: rtg_launch.inc)
   LaunchConsts* d_consts = nullptr;  // camera / frame parameters / chunk description of the launch (rt_pool.h), written on the launch stream
-  uint32_t* d_lpt = nullptr;    // cost-ordered work queue (rt_pool.h LptQueue)
-  size_t lpt_bytes = 0;
+  DevMem lpt;                   // uint32_t: cost-ordered work queue (rt_pool.h LptQueue)
   LptQueue lpt_desc{};          // descriptor of the last launch (RTG_VERBOSE histogram)
   KernelKind last_kernel = KernelKind::baseline;  // what launch_render chose last
   uint32_t last_pix_work = 0;   // pixel work items of that launch (tiles x tile area), 0 when it kept no per-sample scratch
-  uint32_t* d_list = nullptr;   // RTG_FLAG_SAMPLE_COUNTS: the active-pixel list and its inverse (rt_pool.h ListConsts), 2 x the rank's work items
-  size_t list_bytes = 0;
-  uint32_t* d_compact = nullptr;  // ... the compaction's per-block counts, offsets and samples, and its CompactResult
-  size_t compact_bytes = 0;
+  DevMem list;                  // uint32_t: RTG_FLAG_SAMPLE_COUNTS: the active-pixel list and its inverse (rt_pool.h ListConsts), 2 x the rank's work items
+  DevMem compact;               // ... the compaction's per-block counts, offsets and samples, and its CompactResult
   unsigned long long counts_samples = 0;  // ... rtg_stats.samples of the last counts call
-  void* d_retire = nullptr;     // RTG_FLAG_RETIRE: the OK bit plane and the retire kernels' per-block partials (rt_retire.h)
-  size_t retire_bytes = 0;
+  DevMem retire;                // RTG_FLAG_RETIRE: the OK bit plane and the retire kernels' per-block partials (rt_retire.h)
   const char* refusal = nullptr;  // ... set by launch_counts when a block's in-fields are refused (RTG_ERR_INVALID, nothing written)
-  void* d_denoise = nullptr;    // RTG_FLAG_DENOISE: the per-pixel (m, v, valid) records and the prepare kernel's per-block counts (rt_denoise.h)
-  size_t denoise_bytes = 0;
-  uint32_t* d_features = nullptr;  // RTG_FLAG_FEATURES: the feature kernel's per-block counts (rt_features.h)
-  size_t features_bytes = 0;
+  DevMem denoise;               // RTG_FLAG_DENOISE: the per-pixel (m, v, valid) records and the prepare kernel's per-block counts (rt_denoise.h)
+  DevMem features;              // uint32_t: RTG_FLAG_FEATURES: the feature kernel's per-block counts (rt_features.h)
 };
 
 // The camera plan of ONE (program, camera) pair (rt_camera_probe.h, rtg_launch.inc camera_plan): the probe's counts on their way
@@ -129,19 +140,18 @@ struct LeanImages {
   const uint32_t* d_off = nullptr;  // record offsets of the full image, and its size
   uint32_t bytes = 0;
   uint32_t n_followers = 0;    // records the production image drops (0: it is the full image, and no table is allocated)
-  const uint32_t* d_chain_off = nullptr;  // buffers[slot]: the record offsets of that image
+  const uint32_t* d_chain_off = nullptr;  // the record offsets of that image
   uint32_t chain_bytes = 0;    // ... and its size
   bool planned = false;        // the pruning plan is made (at creation for the program that production launches stage, else on demand)
   uint32_t n_pruned = 0;       // records the plan leaves out beyond the followers
   float plan_ms = 0.f;         // host time of the plan (option verbose)
-  // buffers[slot + 1 + chains]: record offsets of the pruned image, [1] without the followers too (the default), [0] with them
+  // record offsets of the pruned image, [1] without the followers too (the default), [0] with them
   // (option box_chains = 0: a measurement switch, so that table is made when the option is first set -- prune_table below)
   const uint32_t* d_prune_off[2] = {nullptr, nullptr};
   uint32_t prune_bytes[2] = {0, 0};
   std::vector<uint32_t> plan_ops;  // ... from these: every record's flag word and its mask (BOX_KEPT / BOX_FOLLOWER / BOX_PRUNED)
   std::vector<uint8_t> plan_mask;
   std::vector<uint8_t> follower;
-  int slot = 12;               // first of this program's three offset tables in rtg_scene::buffers
   // camera plan: the host copy of the program, whether program_shape accepts it (-1: not asked yet; 0: no probe, no camera plan)
   // and which of its spheres end a probe path (rt_camera_probe.h camera_probe_stops), on the device from the first probe on
   const std::vector<Packet>* h_lo = nullptr;
@@ -156,12 +166,11 @@ struct rtg_scene {
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   uint64_t bytes = 0;
-  void* buffers[21] = {};
-  const uint32_t* d_parent = nullptr;  // buffers[8]: the wrapper around every program record (rt_pool_full.h rebuild_hit)
+  std::vector<void*> owned;    // what `upload` allocated: freed when the scene is destroyed
+  const uint32_t* d_parent = nullptr;  // the wrapper around every program record (rt_pool_full.h rebuild_hit)
   hipStream_t own_stream = nullptr;  // rtg_par_cast_multi: this scene's launch stream (created on first use)
   int num_cus = 0;
-  float* d_frame = nullptr;     // rtg_par_cast: device staging frame for host framebuffers
-  size_t frame_bytes = 0;
+  DevMem frame;                // rtg_par_cast: device staging frame for host framebuffers
   int force_chunks = 0;        // RTG_CHUNKS: 0 = automatic
   uint64_t scratch_limit = 0;  // option scratch_mb: budget of the per-sample colour scratch in bytes, 0 = half of the free HBM
   bool whole_scratch = false;  // the kernel trace reads every sample colour back: one pass regardless of the budget
@@ -170,15 +179,14 @@ struct rtg_scene {
   int ray_lds = 1;             // 0: all slot fields in global memory
   int force_rccl = 0;          // rtg_par_cast_multi: run the RCCL reduce even over ONE distinct device (a clique of one)
   int multi_gather = 0;        // rtg_par_cast_multi: 1 = the packed collective (every scene ships its own tiles only; rtg_multi.inc) instead of the full-frame reduce
-  float* d_pack = nullptr;     // ... this scene's tiles, packed in work-item order (on its device)
-  size_t pack_bytes = 0;
-  float* d_recv = nullptr;     // ... and where they arrive on the first device
-  size_t recv_bytes = 0;
-  int multi_planes = 0;        // rtg_par_cast_multi: 1 = accept the flagged frames (SUM_SQUARES .. FEATURES): every plane gathered on the first device, which retires, filters and divides (rtg_multi.inc par_cast_multi_planes_body)
+  DevMem pack;                 // ... this scene's planes, packed in work-item order (on its device)
+  DevMem recv;                 // ... and where they arrive on the first device
+  int multi_planes = 0;        // rtg_par_cast_multi: 1 = accept the flagged frames (SUM_SQUARES .. FEATURES): every plane gathered on the first device, which retires, filters and divides (rtg_multi.inc)
   hipEvent_t post0 = nullptr, post1 = nullptr;  // ... the first device's span for that step (rtg_stats.kernel_ms), created on first use
   hipEvent_t pack0 = nullptr, pack1 = nullptr, unpack0 = nullptr;  // ... option verbose: this scene's pack kernel, and where the first device's unpack kernels begin (they end at post0)
   int bvh4 = 0;                // 1: traverse the 4-wide collapse of the Bvh (same image, other counters; needs wide_bytes)
-  uint32_t wide_bytes = 0;     // size of the 4-wide image in buffers[7], 0 = the scene has none
+  const uint32_t* d_wide = nullptr;  // the 4-wide image
+  uint32_t wide_bytes = 0;     // ... and its size, 0 = the scene has none
   int box_chains = 1;          // production launches of the lean pool kernel stage the image without box-chain followers (rt_pool.h); 0 = off
   // box pruning (rt_box_plan.h): 1 = production launches stage the image without the plan's interior boxes, 2 = counting launches
   // too (their aabb_tests then report what the production walk executes), 0 = off
@@ -194,8 +202,8 @@ struct rtg_scene {
   CameraPlan cam_plans[CAMERA_PLANS];
   uint64_t cam_clock = 0;
   std::vector<Packet> t_lo, t_hi;  // host copy of the rebuilt program (the reference program's: h_lo / h_hi below)
-  LeanImages ref;              // the reference program (dev.lo / dev.hi; offset tables in buffers[6], [12], [13], [14])
-  LeanImages tree;             // the rebuilt one (buffers[15], [16]; tables in [17] .. [20]); tree.lo = nullptr: no region was rebuilt
+  LeanImages ref;              // the reference program (dev.lo / dev.hi)
+  LeanImages tree;             // the rebuilt one; tree.lo = nullptr: no region was rebuilt
   bool tree_tried = false;     // ... and whether the rebuild has run
   float tree_ms = 0.f;         // host time of the rebuild (option verbose)
   uint32_t n_regions = 0;      // regions rebuilt
@@ -223,8 +231,8 @@ struct rtg_scene {
   // The second program and its kernel (rt_pool2.h; flat_scene.h "the list level, hoisted"): n_prog2 = 0 when the world has another shape
   int pool2 = 1;                            // 1 (default): programs with a second program run on the pool-2 kernel; 0: on the first full-feature kernel
   uint32_t n_prog2 = 0, n_box2 = 0;
-  DevScene dev2{};                          // lo / hi = the second program (buffers[9], [10]); materials, textures, Perlin tables shared
-  const P2Table* d_p2 = nullptr;            // buffers[11]
+  DevScene dev2{};                          // lo / hi = the second program; materials, textures, Perlin tables shared
+  const P2Table* d_p2 = nullptr;            // ... and its table
   Pool2Tuning pool2_tune{24, 48, 40, 4, 8, 24, 2};  // refill_min, box_leave, park_max, t_sphere, t_prism, t_list, t_push
   int guide_lds = 0;                       // guided filter (rt_denoise.h GUIDED): 1 = the neighbours' feature records from an LDS copy, 0 = through the caches
   int small_frames = 1;                    // rtg_launch.inc pool_geometry: frames smaller than the chip get small workgroups and reservations
@@ -235,9 +243,7 @@ struct rtg_scene {
   uint32_t n_lights = 0;                   // the table's length, whatever it is
   std::vector<LightRect> h_lights;         // the table and the per-material sampled bytes
   std::vector<uint8_t> h_sampled;
-  LightTable lights{nullptr, nullptr, 0};  // d_lights / d_sampled: .n = 0 until uploaded, and when there is nothing to sample
-  void* d_lights = nullptr;
-  void* d_sampled = nullptr;
+  LightTable lights{nullptr, nullptr, 0};  // on the device: .n = 0 until uploaded, and when there is nothing to sample
   // Scene option query_lds (include/rtiow_gpu_query.h): which kernel answers ray queries -- 0 = always the general one, 2 = the
   // lean kernel whenever the program is lean and fits LDS, 1 = that kernel from QUERY_LDS_MIN_RAYS rays upward (rtg_query.inc)
   int query_lds = 1;
@@ -252,21 +258,7 @@ struct rtg_scene {
 static void ctx_free_buffers(LaunchCtx* c) {
   if (c->busy) (void)hipEventSynchronize(c->done);
   c->busy = false;
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
-  if (c->d_slots) (void)hipFree(c->d_slots);
-  if (c->d_stack) (void)hipFree(c->d_stack);
-  if (c->d_lpt) (void)hipFree(c->d_lpt);
-  if (c->d_list) (void)hipFree(c->d_list);
-  if (c->d_compact) (void)hipFree(c->d_compact);
-  if (c->d_retire) (void)hipFree(c->d_retire);
-  if (c->d_denoise) (void)hipFree(c->d_denoise);
-  if (c->d_features) (void)hipFree(c->d_features);
-  c->d_scratch = nullptr, c->scratch_bytes = 0, c->d_slots = nullptr, c->slots_bytes = 0;
-  c->d_stack = nullptr, c->stack_bytes = 0, c->d_lpt = nullptr, c->lpt_bytes = 0;
-  c->d_list = nullptr, c->list_bytes = 0, c->d_compact = nullptr, c->compact_bytes = 0;
-  c->d_retire = nullptr, c->retire_bytes = 0;
-  c->d_denoise = nullptr, c->denoise_bytes = 0;
-  c->d_features = nullptr, c->features_bytes = 0;
+  for (DevMem* m : {&c->scratch, &c->slots, &c->stack, &c->lpt, &c->list, &c->compact, &c->retire, &c->denoise, &c->features}) m->release();
 }
 
 // Take the next launch context of the ring: create its small buffers on first use, wait for the frame that used it last.
@@ -286,6 +278,12 @@ static int ctx_acquire(rtg_scene* s) {
   }
   s->cx = c;
   return RTG_OK;
+}
+// A counting launch starts from cleared counters and schedule statistics ([7], the work-queue head, is the kernels' own)
+static hipError_t clear_counters(LaunchCtx* c, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(c->d_counters, 0, 7 * sizeof(unsigned long long), stream);
+  if (e == hipSuccess) e = hipMemsetAsync(c->d_counters + 8, 0, 24 * sizeof(unsigned long long), stream);
+  return e;
 }
 // ... and mark it in flight on `stream` once its work is enqueued
 static int ctx_release(rtg_scene* s, hipStream_t stream) {
@@ -407,6 +405,20 @@ struct DevBuf {
   }
   hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
 };
+
+// `bytes` of `src` in a device allocation of their own, which the scene owns until it is destroyed and counts in rtg_scene::bytes
+// (an empty upload still takes 16 bytes); *dst = the typed pointer
+template <typename T>
+static int upload(rtg_scene* s, const T** dst, const void* src, size_t bytes) {
+  const size_t alloc = bytes ? bytes : 16;
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, alloc));
+  s->owned.push_back(p);
+  if (bytes) HIP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+  s->bytes += alloc;
+  *dst = static_cast<const T*>(p);
+  return RTG_OK;
+}
 
 extern "C" {
 
@@ -649,14 +661,6 @@ int rtg_camera_look(const float from[3], const float at[3], const float up[3], f
 }
 
 // ---- scene ---------------------------------------------------------------------------------------
-static int upload(void** dst, const void* src, size_t bytes, uint64_t* total) {
-  size_t alloc = bytes ? bytes : 16;
-  HIP_TRY(hipMalloc(dst, alloc));
-  if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  *total += alloc;
-  return RTG_OK;
-}
-
 // The record offsets of the pruned image of a lean program (rt_box_plan.h): the plan's records 0 bytes, and the box-chain
 // followers too (chains = 1) or not; made once per scene, program and kind.
 static int prune_table(rtg_scene* s, LeanImages* im, int chains) {
@@ -666,28 +670,22 @@ static int prune_table(rtg_scene* s, LeanImages* im, int chains) {
   std::vector<uint32_t> off(n);
   for (size_t i = 0; i < n; i++) drop[i] = im->plan_mask[i] == BOX_PRUNED || (chains && im->plan_mask[i] == BOX_FOLLOWER);
   im->prune_bytes[chains] = lds_image_offsets(im->plan_ops.data(), n, off.data(), drop.data());
-  int rc = upload(&s->buffers[im->slot + 1 + chains], off.data(), n * sizeof(uint32_t), &s->bytes);
-  if (rc) return rc;
-  im->d_prune_off[chains] = (const uint32_t*)s->buffers[im->slot + 1 + chains];
-  return RTG_OK;
+  return upload(s, &im->d_prune_off[chains], off.data(), n * sizeof(uint32_t));
 }
 
-// The full image's offsets (buffers[off_slot]), the followers and the image without them (buffers[im->slot]) of the program
-// (lo, hi), which is on the device already (im->lo, im->hi).
-static int lean_images(rtg_scene* s, LeanImages* im, const std::vector<Packet>& lo, const std::vector<Packet>& hi, int off_slot) {
+// The full image's offsets, the followers and the image without them of the program (lo, hi), which is on the device already.
+static int lean_images(rtg_scene* s, LeanImages* im, const std::vector<Packet>& lo, const std::vector<Packet>& hi) {
   std::vector<uint32_t> off(hi.size());
   im->plan_ops.resize(hi.size());
   for (size_t i = 0; i < hi.size(); i++) im->plan_ops[i] = hi[i].w[3];
   im->bytes = lds_image_offsets(im->plan_ops.data(), hi.size(), off.data());
-  int rc = upload(&s->buffers[off_slot], off.data(), off.size() * sizeof(uint32_t), &s->bytes);
+  int rc = upload(s, &im->d_off, off.data(), off.size() * sizeof(uint32_t));
   if (rc) return rc;
-  im->d_off = (const uint32_t*)s->buffers[off_slot];
   im->follower.resize(hi.size());
   im->n_followers = box_chain_followers(reinterpret_cast<const uint32_t (*)[4]>(lo.data()), reinterpret_cast<const uint32_t (*)[4]>(hi.data()), hi.size(), im->follower.data());
   if (im->n_followers) {  // the production image: every follower 0 bytes (the counting launches keep the full one)
     im->chain_bytes = lds_image_offsets(im->plan_ops.data(), hi.size(), off.data(), im->follower.data());
-    if ((rc = upload(&s->buffers[im->slot], off.data(), off.size() * sizeof(uint32_t), &s->bytes))) return rc;
-    im->d_chain_off = (const uint32_t*)s->buffers[im->slot];
+    if ((rc = upload(s, &im->d_chain_off, off.data(), off.size() * sizeof(uint32_t)))) return rc;
   }
   return RTG_OK;
 }
@@ -719,11 +717,11 @@ static int tree_program(rtg_scene* s) {
   s->tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!s->n_regions) return RTG_OK;
   int rc;
-  if ((rc = upload(&s->buffers[15], lo.data(), n * 16, &s->bytes)) || (rc = upload(&s->buffers[16], hi.data(), n * 16, &s->bytes))) return rc;
-  s->tree.slot = 18;
-  if ((rc = lean_images(s, &s->tree, lo, hi, 17)) || (rc = lean_plan(s, &s->tree, lo, hi, BOX_TREE_PLAN))) return rc;
+  const uint4 *d_lo = nullptr, *d_hi = nullptr;
+  if ((rc = upload(s, &d_lo, lo.data(), n * 16)) || (rc = upload(s, &d_hi, hi.data(), n * 16))) return rc;
+  if ((rc = lean_images(s, &s->tree, lo, hi)) || (rc = lean_plan(s, &s->tree, lo, hi, BOX_TREE_PLAN))) return rc;
   if (!s->box_chains && (rc = prune_table(s, &s->tree, 0))) return rc;
-  s->tree.lo = (const uint4*)s->buffers[15], s->tree.hi = (const uint4*)s->buffers[16];
+  s->tree.lo = d_lo, s->tree.hi = d_hi;
   s->t_lo.swap(lo), s->t_hi.swap(hi);
   s->tree.h_lo = &s->t_lo, s->tree.h_hi = &s->t_hi;
   return RTG_OK;
@@ -732,8 +730,7 @@ static int tree_program(rtg_scene* s) {
 void rtg_scene_destroy(rtg_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  for (void* p : s->buffers)
-    if (p) (void)hipFree(p);
+  for (void* p : s->owned) (void)hipFree(p);
   for (LaunchCtx& c : s->ctx) {
     ctx_free_buffers(&c);
     if (c.d_counters) (void)hipFree(c.d_counters);
@@ -750,11 +747,7 @@ void rtg_scene_destroy(rtg_scene* s) {
   }
   for (LeanImages* im : {&s->ref, &s->tree})
     if (im->d_stop) (void)hipFree(im->d_stop);
-  if (s->d_frame) (void)hipFree(s->d_frame);
-  if (s->d_lights) (void)hipFree(s->d_lights);
-  if (s->d_sampled) (void)hipFree(s->d_sampled);
-  if (s->d_pack) (void)hipFree(s->d_pack);
-  if (s->d_recv) (void)hipFree(s->d_recv);
+  for (DevMem* m : {&s->frame, &s->pack, &s->recv}) m->release();
   if (s->post0) (void)hipEventDestroy(s->post0);
   if (s->post1) (void)hipEventDestroy(s->post1);
   for (hipEvent_t ev : {s->pack0, s->pack1, s->unpack0})
@@ -783,21 +776,15 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
   s->n_mat = (uint32_t)fs.mat.size() / 2;
   s->n_tex = (uint32_t)fs.tex.size() / 2;
   int rc;
-  if ((rc = upload(&s->buffers[0], fs.lo.data(), fs.lo.size() * 16, &s->bytes)) ||
-      (rc = upload(&s->buffers[1], fs.hi.data(), fs.hi.size() * 16, &s->bytes)) ||
-      (rc = upload(&s->buffers[2], fs.mat.data(), fs.mat.size() * 16, &s->bytes)) ||
-      (rc = upload(&s->buffers[3], fs.tex.data(), fs.tex.size() * 16, &s->bytes)) ||
-      (rc = upload(&s->buffers[4], fs.perlin_vecs.data(), sizeof(float) * 1024, &s->bytes)) ||
-      (rc = upload(&s->buffers[5], fs.perlin_perm.data(), 768, &s->bytes))) {
+  if ((rc = upload(s, &s->dev.lo, fs.lo.data(), fs.lo.size() * 16)) ||
+      (rc = upload(s, &s->dev.hi, fs.hi.data(), fs.hi.size() * 16)) ||
+      (rc = upload(s, &s->dev.mat, fs.mat.data(), fs.mat.size() * 16)) ||
+      (rc = upload(s, &s->dev.tex, fs.tex.data(), fs.tex.size() * 16)) ||
+      (rc = upload(s, &s->dev.perlin_vecs, fs.perlin_vecs.data(), sizeof(float) * 1024)) ||
+      (rc = upload(s, &s->dev.perlin_perm, fs.perlin_perm.data(), 768))) {
     rtg_scene_destroy(s);
     return rc;
   }
-  s->dev.lo = (const uint4*)s->buffers[0];
-  s->dev.hi = (const uint4*)s->buffers[1];
-  s->dev.mat = (const uint4*)s->buffers[2];
-  s->dev.tex = (const uint4*)s->buffers[3];
-  s->dev.perlin_vecs = (const float4*)s->buffers[4];
-  s->dev.perlin_perm = (const uint8_t*)s->buffers[5];
   s->dev.n_prog = s->n_prog;
   s->dev.n_mat = s->n_mat;
   for (const Packet& h : fs.hi) s->n_box += (h.w[3] & 0xffu) == OP_BOX ? 1u : 0u;
@@ -809,31 +796,28 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
       parent[i] = open.empty() ? 0xffffffffu : open.back();
       if (op == OP_PUSH) open.push_back((uint32_t)i);
     }
-    if ((rc = upload(&s->buffers[8], parent.data(), parent.size() * sizeof(uint32_t), &s->bytes))) {
+    if ((rc = upload(s, &s->d_parent, parent.data(), parent.size() * sizeof(uint32_t)))) {
       rtg_scene_destroy(s);
       return rc;
     }
-    s->d_parent = (const uint32_t*)s->buffers[8];
   }
   for (size_t i = 0; i < fs.hi.size(); i++)
     if ((fs.hi[i].w[3] & 0xffu) == OP_SEG) s->seg_first = (uint32_t)i + 1u, s->seg_end = fs.hi[i].w[2];
   if (!fs.hi2.empty()) {  // the second program (pool-2 kernel)
-    if ((rc = upload(&s->buffers[9], fs.lo2.data(), fs.lo2.size() * 16, &s->bytes)) ||
-        (rc = upload(&s->buffers[10], fs.hi2.data(), fs.hi2.size() * 16, &s->bytes)) ||
-        (rc = upload(&s->buffers[11], &fs.p2, sizeof(P2Table), &s->bytes))) {
+    s->dev2 = s->dev;
+    if ((rc = upload(s, &s->dev2.lo, fs.lo2.data(), fs.lo2.size() * 16)) ||
+        (rc = upload(s, &s->dev2.hi, fs.hi2.data(), fs.hi2.size() * 16)) ||
+        (rc = upload(s, &s->d_p2, &fs.p2, sizeof(P2Table)))) {
       rtg_scene_destroy(s);
       return rc;
     }
-    s->dev2 = s->dev;
-    s->dev2.lo = (const uint4*)s->buffers[9], s->dev2.hi = (const uint4*)s->buffers[10];
     s->dev2.n_prog = s->n_prog2 = (uint32_t)fs.hi2.size();
     s->dev2.lds_off = nullptr, s->dev2.lds_image_bytes = 0;
-    s->d_p2 = (const P2Table*)s->buffers[11];
     for (const Packet& h : fs.hi2) s->n_box2 += (h.w[3] & 0xffu) == OP_BOX ? 1u : 0u;
   }
   if ((fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0) {  // lean program (BOX / SPHERE / END): layout of its LDS image (rt_pool.h)
-    s->ref.lo = s->dev.lo, s->ref.hi = s->dev.hi, s->ref.slot = 12;
-    if ((rc = lean_images(s, &s->ref, fs.lo, fs.hi, 6))) {
+    s->ref.lo = s->dev.lo, s->ref.hi = s->dev.hi;
+    if ((rc = lean_images(s, &s->ref, fs.lo, fs.hi))) {
       rtg_scene_destroy(s);
       return rc;
     }
@@ -850,7 +834,7 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
     }
     std::vector<uint32_t> wide;
     if (build_wide_image(fs.lo.data(), fs.hi.data(), fs.hi.size(), wide)) {
-      if ((rc = upload(&s->buffers[7], wide.data(), wide.size() * sizeof(uint32_t), &s->bytes))) {
+      if ((rc = upload(s, &s->d_wide, wide.data(), wide.size() * sizeof(uint32_t)))) {
         rtg_scene_destroy(s);
         return rc;
       }
@@ -953,12 +937,12 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
   else if (k == "light_sampling") {                             // 1: direct light sampling of the scene's rect lights (rt_light.h): other samples, the same expectation
     if (value < 0 || value > 1) return fail(RTG_ERR_INVALID, "light_sampling: 0 or 1");
     if (value && s->n_lights > RT_MAX_LIGHTS) return fail(RTG_ERR_INVALID, "light_sampling: the scene's light table has " + std::to_string(s->n_lights) + " rects, more than RT_MAX_LIGHTS (64)");
-    if (value && s->n_lights != 0u && !s->d_lights) {  // the first time: the table to the device
+    if (value && s->n_lights != 0u && !s->lights.n) {  // the first time: the table to the device
       HIP_TRY(hipSetDevice(s->device));
-      int rc = upload(&s->d_lights, s->h_lights.data(), s->h_lights.size() * sizeof(LightRect), &s->bytes);
-      if (!rc) rc = upload(&s->d_sampled, s->h_sampled.data(), s->h_sampled.size(), &s->bytes);
+      int rc = upload(s, &s->lights.lights, s->h_lights.data(), s->h_lights.size() * sizeof(LightRect));
+      if (!rc) rc = upload(s, &s->lights.sampled, s->h_sampled.data(), s->h_sampled.size());
       if (rc) return rc;
-      s->lights = LightTable{(const LightRect*)s->d_lights, (const uint8_t*)s->d_sampled, s->n_lights};
+      s->lights.n = s->n_lights;
     }
     if (s->verbose) {
       fprintf(stderr, "[rtg] light sampling %s: light table of %u rect(s)\n", value ? "on" : "off", s->n_lights);
@@ -1053,7 +1037,7 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
 
 // Option verbose, counting builds: the schedule statistics of the frame just rendered (`ms`: its kernel time)
 static int print_schedule_stats(rtg_scene* s, float ms) {
-  if (s->cx->lpt_desc.n_blocks && s->cx->d_lpt) {  // cost classes of the last frame (class 0 = deepest)
+  if (s->cx->lpt_desc.n_blocks && s->cx->lpt.p) {  // cost classes of the last frame (class 0 = deepest)
     std::vector<uint32_t> ctl(LPT_CTL);
     HIP_TRY(hipMemcpy(ctl.data(), s->cx->lpt_desc.ctl, LPT_CTL * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::string line;
@@ -1134,8 +1118,7 @@ int rtg_par_cast_device(rtg_scene* s, const rtg_camera* camera, const rtg_params
     if (sl.background) d.bg = dev_background(fb.background);
   }
   if (count) {
-    HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), stream));
-    HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), stream));
+    HIP_TRY_CTX(clear_counters(s->cx, stream));
     HIP_TRY_CTX(hipMemsetAsync(s->cx->d_counters + 32, 0, 32 * sizeof(unsigned long long), stream));  // (RT_CENSUS builds)
   }
 #ifdef RT_TIMELINE  // diagnostic build (rt_pool.h RT_TL_*): one 16-dword drain record per wave, dumped to $RTG_TIMELINE_OUT
@@ -1210,9 +1193,9 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
   if (int rc0 = check_blocks(L, sl, out_rgb, params->nranks ? params->nranks : 1u, &fb)) return rc0;
   HIP_TRY(hipSetDevice(s->device));
   // the staging frame lives with the scene handle (no hipMalloc / hipFree per call)
-  hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.words ? L.words * sizeof(float) : 16);
+  hipError_t e = s->frame.grow(L.words ? L.words * sizeof(float) : 16);
   if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
-  float* d_out = s->d_frame;
+  float* d_out = s->frame.as<float>();
   char* dev = reinterpret_cast<char*>(d_out);
   char* host = reinterpret_cast<char*>(out_rgb);
   const Extents up = upload_extents(L, params->nranks > 1, sl.begin, fb.features.compute);

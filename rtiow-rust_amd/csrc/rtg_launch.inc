@@ -15,7 +15,7 @@ static uint64_t scratch_cap(int n_ctx) {
 // same left fold, bit for bit, with O(budget) instead of O(spp) memory.  Returns the samples per pass (>= 1).
 static uint32_t samples_per_pass(const rtg_scene* s, uint64_t pix_work, uint32_t ns) {
   const uint64_t per_sample = pix_work * 3 * sizeof(float);
-  uint64_t budget = s->scratch_limit ? s->scratch_limit : std::max<uint64_t>(scratch_cap(s->n_ctx), s->cx->scratch_bytes);
+  uint64_t budget = s->scratch_limit ? s->scratch_limit : std::max<uint64_t>(scratch_cap(s->n_ctx), s->cx->scratch.bytes);
   if (s->whole_scratch) budget = ~0ull;
   uint64_t k = std::max<uint64_t>(1, budget / std::max<uint64_t>(per_sample, 1));
   k = std::min<uint64_t>(k, 0xfffffffeull / std::max<uint64_t>(pix_work, 1));  // work items of a pass: one 32-bit counter
@@ -44,15 +44,6 @@ static uint64_t owned_pixels(const DevParams& d) {
       px += (uint64_t)w * h;
     }
   return px;
-}
-
-static hipError_t grow(void** buf, size_t* have, size_t need) {
-  if (need <= *have) return hipSuccess;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr, *have = 0;
-  hipError_t e = hipMalloc(buf, need);
-  if (e == hipSuccess) *have = need;
-  return e;
 }
 
 // ---- one pick per kernel family ------------------------------------------------------------------------------------------------
@@ -338,7 +329,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     // several passes: one sample per work item; the same when the slice does not begin on a chunk boundary (the kernel ends a
     // work item where s % chunk == 0)
     if (per_pass < ns_call || sl.begin % chunk != 0u || sl.squares || sl.counts) chunk = 1u;
-    hipError_t ea = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
+    hipError_t ea = s->cx->scratch.grow(pix_work * per_pass * 3 * sizeof(float));
     if (ea != hipSuccess) return ea;
   }
   s->cx->last_pix_work = use_scratch && per_pass == d.ns ? (uint32_t)pix_work : 0u;
@@ -400,7 +391,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     return hipSuccess;
   };
   if (hipError_t ec = camera_image(); ec != hipSuccess) return ec;
-  if (wide) dev.lds_off = (const uint32_t*)s->buffers[7], dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
+  if (wide) dev.lds_off = s->d_wide, dev.lds_image_bytes = s->wide_bytes;  // the WIDE kernel's reading of these two
   const uint32_t image = dev.lds_image_bytes;
   sized_for = image;
   bool use_lds = image != 0 && pool_lds_bytes(image, s->n_mat, waves, true, false) <= lds_limit;
@@ -433,7 +424,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     if (use_scratch) {
       cm.chunk = chunk;
       cm.n_chunks = (end - s0 + chunk - 1) / chunk;
-      cm.scratch = s->cx->d_scratch - 3ull * s0 * pix_work;  // biased: sample s of work index w at scratch[3 * (s * pix_work + w)]
+      cm.scratch = s->cx->scratch.as<float>() - 3ull * s0 * pix_work;  // biased: sample s of work index w at scratch[3 * (s * pix_work + w)]
     }
     return cm;
   };
@@ -441,12 +432,12 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     if (s->verbose)
       fprintf(stderr, "[rtg] pool: samples [%u, %u) of %u: grid %u x %d threads, %d WG/CU, lds %zu B (program staged: %d, hot slot fields in LDS: %d), %u chunk(s) of %u samples, cost-ordered queue after %u chunk(s)\n",
               s0, dp.ns, d.ns, grid, bt, L.per_cu, lds, (int)use_lds, (int)ray_lds, cm.n_chunks, cm.chunk, (cm.lpt_samples - (cm.lpt_samples ? s0 : 0u)) / (cm.chunk ? cm.chunk : 1u));
-    hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
+    hipError_t eg = s->cx->slots.grow((size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
     if (eg != hipSuccess) return eg;
     if (s0 != sl.begin && (eg = camera_image()) != hipSuccess) return eg;  // (a later pass: the plan its first pass probed for)
     launch_pass_setup(s, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, queue, stream);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
-                       s->cx->d_counters, s->pool_tune, s->cx->d_slots);
+                       s->cx->d_counters, s->pool_tune, s->cx->slots.as<uint32_t>());
     return hipSuccess;
   };
   return sample_passes(s, d, d_out, stream, sl, L, per_pass, chunks, issue);
@@ -535,18 +526,18 @@ static hipError_t setup_lpt(rtg_scene* s, ChunkMode& cm, uint64_t capacity) {
   if (phase1 < 1 || phase1 > cm.n_chunks / 3) return hipSuccess;
   // layout: [descriptor, 64 B] [cost n] [ctl LPT_CTL] [list LPT_CLASSES x n]
   const size_t words = 16 + (size_t)n_blocks * (1 + LPT_CLASSES) + LPT_CTL;
-  hipError_t e = grow((void**)&s->cx->d_lpt, &s->cx->lpt_bytes, words * sizeof(uint32_t));
+  hipError_t e = s->cx->lpt.grow(words * sizeof(uint32_t));
   if (e != hipSuccess) return e;
   LptQueue q;
   memset(&q, 0, sizeof(q));
   static_assert(sizeof(LptQueue) <= 64, "descriptor slot");
-  q.cost = s->cx->d_lpt + 16, q.ctl = q.cost + n_blocks, q.list = q.ctl + LPT_CTL;
+  q.cost = s->cx->lpt.as<uint32_t>() + 16, q.ctl = q.cost + n_blocks, q.list = q.ctl + LPT_CTL;
   q.n_blocks = n_blocks, q.phase1 = phase1;
   q.phase2_base = phase1 * cm.pix_work;
   q.span = LPT_BLOCK * (cm.n_chunks - phase1);
   q.mode = (uint32_t)s->lpt, q.shift = (uint32_t)s->lpt_shift;
   s->cx->lpt_desc = q;
-  cm.lpt = reinterpret_cast<const LptQueue*>(s->cx->d_lpt);
+  cm.lpt = reinterpret_cast<const LptQueue*>(s->cx->lpt.as<uint32_t>());
   cm.lpt_samples = cm.s_begin + phase1 * cm.chunk;  // samples [s_begin, lpt_samples) of every pixel: phase 1 of this pass
   cm.lpt_deep = (uint32_t)s->lpt_deep;
   return hipSuccess;
@@ -559,7 +550,7 @@ static void launch_pass_setup(rtg_scene* s, const LaunchConsts& c, uint32_t* que
   const bool lpt = c.cm.lpt != nullptr;
   const LptQueue q = lpt ? s->cx->lpt_desc : LptQueue{};
   hipLaunchKernelGGL(write_pass_setup, dim3(1), dim3(256), 0, stream, s->cx->d_consts, c, (unsigned long long*)queue,
-                     lpt ? reinterpret_cast<LptQueue*>(s->cx->d_lpt) : (LptQueue*)nullptr, q, lpt ? q.n_blocks + LPT_CTL : 0u);
+                     lpt ? reinterpret_cast<LptQueue*>(s->cx->lpt.as<uint32_t>()) : (LptQueue*)nullptr, q, lpt ? q.n_blocks + LPT_CTL : 0u);
 }
 
 // Full-feature scenes, ray-pool kernel (rt_pool_full.h) or, for list worlds without a Bvh, the lock-step kernel
@@ -579,7 +570,7 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   const PoolGeometry geo = pool_geometry(s, pix_work * std::min(ns_call, per_pass), bt_max, s->full_threads, FPOOL, false);
   const int bt = geo.bt;
   const uint32_t waves = (uint32_t)bt / 64;
-  hipError_t e = grow((void**)&s->cx->d_scratch, &s->cx->scratch_bytes, pix_work * per_pass * 3 * sizeof(float));
+  hipError_t e = s->cx->scratch.grow(pix_work * per_pass * 3 * sizeof(float));
   if (e != hipSuccess) return e;
   s->cx->last_pix_work = per_pass == d.ns ? (uint32_t)pix_work : 0u;
   uint32_t* queue = (uint32_t*)(s->cx->d_counters + 7);
@@ -658,14 +649,14 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   s->cx->last_kernel = L.kind;
   auto chunks = [&](uint32_t s0, uint32_t end) {
     ChunkMode cm{};
-    cm.scratch = s->cx->d_scratch - 3ull * s0 * pix_work, cm.chunk = 1u, cm.n_chunks = end - s0, cm.pix_work = (uint32_t)pix_work, cm.s_begin = s0;
+    cm.scratch = s->cx->scratch.as<float>() - 3ull * s0 * pix_work, cm.chunk = 1u, cm.n_chunks = end - s0, cm.pix_work = (uint32_t)pix_work, cm.s_begin = s0;
     cm.drain_share = (uint32_t)std::max(0, s->drain_share);
     return cm;
   };
   auto issue = [&](uint32_t s0, const DevParams& dp, const ChunkMode& cm, uint32_t grid, uint32_t total_work) {
-    hipError_t eg = grow((void**)&s->cx->d_slots, &s->cx->slots_bytes, (size_t)grid * std::max(full_pool_wg_words(waves), pool2_slot_words(waves)) * sizeof(uint32_t));
+    hipError_t eg = s->cx->slots.grow((size_t)grid * std::max(full_pool_wg_words(waves), pool2_slot_words(waves)) * sizeof(uint32_t));
     if (eg != hipSuccess) return eg;
-    eg = grow((void**)&s->cx->d_stack, &s->cx->stack_bytes, (size_t)grid * waves * (genb ? 2 : 1) * MAX_XFORM_DEPTH * 6 * 64 * sizeof(float));
+    eg = s->cx->stack.grow((size_t)grid * waves * (genb ? 2 : 1) * MAX_XFORM_DEPTH * 6 * 64 * sizeof(float));
     if (eg != hipSuccess) return eg;
     // (the lock-step kernel reports as the first kernel, with that kernel's LDS figure)
     const bool p2 = L.kind == KernelKind::pool2;
@@ -678,13 +669,13 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
     launch_pass_setup(s, c, queue, stream);
     if (L.kind == KernelKind::lock_step)
       hipLaunchKernelGGL(sync_kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
-                         s->cx->d_counters, s->sync_tune, s->cx->d_stack, window);
+                         s->cx->d_counters, s->sync_tune, s->cx->stack.as<float>(), window);
     else if (p2)
       hipLaunchKernelGGL(pool2_kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev2, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
-                         s->cx->d_counters, s->pool2_tune, s->cx->d_slots, s->d_p2);
+                         s->cx->d_counters, s->pool2_tune, s->cx->slots.as<uint32_t>(), s->d_p2);
     else
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), L.lds, stream, s->dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
-                         s->cx->d_counters, s->full_tune, s->cx->d_slots, s->cx->d_stack, window);
+                         s->cx->d_counters, s->full_tune, s->cx->slots.as<uint32_t>(), s->cx->stack.as<float>(), window);
     return hipSuccess;
   };
   return sample_passes(s, d, d_out, stream, sl, L, per_pass, chunks, issue);
@@ -723,9 +714,9 @@ static hipError_t launch_retire(rtg_scene* s, const DevParams& d, float* d_out, 
   RetireBufs b;
   b.pitch = (d.nx + 31u) / 32u + 1u;
   // [blk_se2: f64 x n_blk] [blk_held: u64 x n_blk] [blk_u32: 3 x n_blk] [okbits: ny x pitch words]
-  hipError_t e = grow(&s->cx->d_retire, &s->cx->retire_bytes, (size_t)n_blk * 28u + (size_t)d.ny * b.pitch * 4u);
+  hipError_t e = s->cx->retire.grow((size_t)n_blk * 28u + (size_t)d.ny * b.pitch * 4u);
   if (e != hipSuccess) return e;
-  b.blk_se2 = reinterpret_cast<double*>(s->cx->d_retire);
+  b.blk_se2 = s->cx->retire.as<double>();
   b.blk_held = reinterpret_cast<unsigned long long*>(b.blk_se2 + n_blk);
   b.blk_u32 = reinterpret_cast<uint32_t*>(b.blk_held + n_blk);
   b.okbits = b.blk_u32 + 3ull * n_blk;
@@ -758,13 +749,13 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   const uint32_t n_blk = (uint32_t)((n_pix + 255u) / 256u);
   // [records: 32 B x n_pix] [blk_u32: 2 x n_blk, padded to 16 B] [guided: feature records: 32 B x n_pix]
   const size_t frec_at = (size_t)n_pix * 32u + (((size_t)n_blk * 8u + 15u) & ~(size_t)15u);
-  hipError_t e = grow(&s->cx->d_denoise, &s->cx->denoise_bytes, frec_at + (guide ? (size_t)n_pix * 32u : 0u));
+  hipError_t e = s->cx->denoise.grow(frec_at + (guide ? (size_t)n_pix * 32u : 0u));
   if (e != hipSuccess) return e;
   uint32_t* words = reinterpret_cast<uint32_t*>(d_out);
   DenoiseBufs b;
   b.planes = d_out;
   b.counts = L.at(words, L.counts);
-  b.rec = reinterpret_cast<float4*>(s->cx->d_denoise);
+  b.rec = s->cx->denoise.as<float4>();
   b.blk_u32 = reinterpret_cast<uint32_t*>(b.rec + 2ull * n_pix);
   b.block = words + L.denoise;
   b.outp = d_out + L.denoised;
@@ -783,7 +774,7 @@ static hipError_t launch_denoise(rtg_scene* s, const DevParams& d, float* d_out,
   if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
   DenoiseGuide gd{nullptr, 1.f, 1.f, 1.f};
   if (guide) {
-    float4* frec = reinterpret_cast<float4*>(reinterpret_cast<char*>(s->cx->d_denoise) + frec_at);
+    float4* frec = reinterpret_cast<float4*>(s->cx->denoise.as<char>() + frec_at);
     gd = DenoiseGuide{frec, guide->sigma_normal, guide->sigma_albedo, guide->sigma_depth};
     hipLaunchKernelGGL(denoise_guide_kernel, dim3(n_blk), dim3(256), 0, stream, (uint32_t)n_pix, (const float*)d_out + L.albedo, (const float*)d_out + L.normal,
                        (const float*)d_out + L.depth, frec);
@@ -803,12 +794,12 @@ static hipError_t launch_features(rtg_scene* s, const DevCamera& cam, const DevP
   const uint64_t blocks = (uint64_t)((d.nx + 15u) / 16u) * ((d.ny + 15u) / 16u);
   if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
   const uint32_t n_blk = in.compute ? (uint32_t)blocks : 0u;
-  hipError_t e = grow((void**)&s->cx->d_features, &s->cx->features_bytes, (size_t)std::max<uint64_t>(blocks, 1) * 8u);
+  hipError_t e = s->cx->features.grow((size_t)std::max<uint64_t>(blocks, 1) * 8u);
   if (e != hipSuccess) return e;
   FeatureBufs b;
   b.block = reinterpret_cast<uint32_t*>(d_out) + L.features;
   b.albedo = d_out + L.albedo, b.normal = d_out + L.normal, b.depth = d_out + L.depth;
-  b.blk_u32 = s->cx->d_features;
+  b.blk_u32 = s->cx->features.as<uint32_t>();
   if (n_blk != 0u)
     with_feat<false>(s, [&](auto feat) { hipLaunchKernelGGL((features_kernel<decltype(feat)::value>), dim3(n_blk), dim3(256), 0, stream, s->dev, cam, d, in.grid, b); });
   hipLaunchKernelGGL(features_finish_kernel, dim3(1), dim3(256), 0, stream, n_blk, b);
@@ -904,16 +895,16 @@ static hipError_t launch_counts(rtg_scene* s, const DevCamera& cam, const DevPar
   if (renders) {
     const PixMap pm = make_pixmap(d);
     const uint32_t n_blk = (uint32_t)(pix_work / 256u);
-    e = grow((void**)&s->cx->d_list, &s->cx->list_bytes, 2 * pix_work * sizeof(uint32_t));
+    e = s->cx->list.grow(2 * pix_work * sizeof(uint32_t));
     if (e != hipSuccess) return e;
     // [blk_samples: u64 x n_blk] [CompactResult] [blk_active: n_blk] [blk_offset: n_blk]
-    e = grow((void**)&s->cx->d_compact, &s->cx->compact_bytes, (size_t)n_blk * 16u + sizeof(CompactResult));
+    e = s->cx->compact.grow((size_t)n_blk * 16u + sizeof(CompactResult));
     if (e != hipSuccess) return e;
-    unsigned long long* blk_samples = reinterpret_cast<unsigned long long*>(s->cx->d_compact);
+    unsigned long long* blk_samples = s->cx->compact.as<unsigned long long>();
     CompactResult* res = reinterpret_cast<CompactResult*>(blk_samples + n_blk);
     uint32_t* blk_active = reinterpret_cast<uint32_t*>(res + 1);
     uint32_t* blk_offset = blk_active + n_blk;
-    uint32_t* list = s->cx->d_list;
+    uint32_t* list = s->cx->list.as<uint32_t>();
     uint32_t* inv = list + pix_work;
     ls.list.list = list, ls.list.inv = inv;
     hipLaunchKernelGGL(compact_count_kernel, dim3(n_blk), dim3(256), 0, stream, d, pm, (uint32_t)pix_work, ls.list.counts, sl.begin, blk_active, blk_samples);

@@ -96,7 +96,7 @@ int rccl_group(const std::vector<int>& devs, const std::function<void(const std:
   return fail(RTG_ERR_DEVICE, err);
 }
 
-// ONE collective over the distinct devices: reduce(sum) of the float3 framebuffers heads[k]->d_frame (device devs[k],
+// ONE collective over the distinct devices: reduce(sum) of the float3 framebuffers heads[k]->frame (device devs[k],
 // stream heads[k]->own_stream) to heads[0]'s.
 int rccl_reduce_frames(const std::vector<int>& devs, const std::vector<rtg_scene*>& heads, size_t n_floats) {
   std::lock_guard<std::mutex> lock(g_rccl.mu);
@@ -108,24 +108,25 @@ int rccl_reduce_frames(const std::vector<int>& devs, const std::vector<rtg_scene
         err = std::string("hipSetDevice: ") + hipGetErrorString(he);
         break;
       }
-      ncclResult_t r = g_rccl.Reduce(heads[k]->d_frame, heads[k]->d_frame, n_floats, ncclFloat, ncclSum, 0, comms[k], heads[k]->own_stream);
+      ncclResult_t r = g_rccl.Reduce(heads[k]->frame.p, heads[k]->frame.p, n_floats, ncclFloat, ncclSum, 0, comms[k], heads[k]->own_stream);
       if (r != ncclSuccess) err = std::string("ncclReduce: ") + g_rccl.GetErrorString(r);
       else g_rccl.n_reduces++;
     }
   });
 }
 
-// The PACKED collective (scene option multi_gather): every scene ships only the pixels it owns -- its tiles in work-item order
-// (rt_pool.h work_to_pixel: pix_work x float3, 1 / n_scenes of the frame) -- to the first device, which scatters them into the frame.
-// Grouped ncclSend / ncclRecv: scene i's packed tiles (sends[k]: buffer, floats, clique rank of its device) arrive in recvs[k] on
-// device 0.  Copies only: bit-identical by construction.
+// The PACKED collective (plain frames under scene option multi_gather, and every flagged frame): a scene ships only the pixels it
+// owns -- the planes of its tiles in work-item order (rt_multi_planes.h: pix_work x words_per_pixel, 1 / n_scenes of the frame) --
+// to the first device, which scatters them into the frame.  Grouped ncclSend / ncclRecv: scene i's packed planes (moves[k]:
+// buffer, words, clique rank of its device) arrive in moves[k].dst on device 0, on `head_stream`.  Copies only: bit-identical
+// by construction.
 struct PackedMove { const float* src; float* dst; size_t n_floats; int from; hipStream_t src_stream; };
-int rccl_gather_tiles(const std::vector<int>& devs, const std::vector<rtg_scene*>& heads, const std::vector<PackedMove>& moves) {
+int rccl_gather_tiles(const std::vector<int>& devs, hipStream_t head_stream, const std::vector<PackedMove>& moves) {
   std::lock_guard<std::mutex> lock(g_rccl.mu);
   if (int rc = rccl_load()) return rc;
   if (!g_rccl.Send || !g_rccl.Recv) return fail(RTG_ERR_DEVICE, "librccl lacks ncclSend / ncclRecv (the packed collective needs them)");
   // every move is checked before the group opens: an argument error must not leave a half-issued group behind
-  if (devs.empty() || heads.size() != devs.size() || !heads[0] || !heads[0]->own_stream) return fail(RTG_ERR_INVALID, "packed collective: no first device");
+  if (devs.empty() || !head_stream) return fail(RTG_ERR_INVALID, "packed collective: no first device");
   for (const PackedMove& m : moves) {
     if (!m.src || !m.dst) return fail(RTG_ERR_INVALID, "packed collective: a move without a buffer");
     if (m.n_floats == 0) return fail(RTG_ERR_INVALID, "packed collective: an empty move");
@@ -146,33 +147,12 @@ int rccl_gather_tiles(const std::vector<int>& devs, const std::vector<rtg_scene*
         break;
       }
       if (err.empty()) {
-        ncclResult_t r = g_rccl.Recv(m.dst, m.n_floats, ncclFloat, m.from, comms[0], heads[0]->own_stream);
+        ncclResult_t r = g_rccl.Recv(m.dst, m.n_floats, ncclFloat, m.from, comms[0], head_stream);
         if (r != ncclSuccess) err = std::string("ncclRecv: ") + g_rccl.GetErrorString(r);
         else g_rccl.n_reduces++;
       }
     }
   });
-}
-
-// work item w of the rank P.rank -> its pixel (rt_pool.h work_to_pixel); items beyond the image are padding
-__global__ void pack_tiles_kernel(DevParams P, PixMap pm, uint32_t pix_work, const float* __restrict__ fb, float* __restrict__ packed) {
-  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= pix_work) return;
-  uint32_t x, row;
-  float r = 0.f, g = 0.f, b = 0.f;
-  if (work_to_pixel(P, pm, w, x, row)) {
-    const float* p = fb + 3ull * ((size_t)row * P.nx + x);
-    r = p[0], g = p[1], b = p[2];
-  }
-  packed[3ull * w] = r, packed[3ull * w + 1] = g, packed[3ull * w + 2] = b;
-}
-__global__ void unpack_tiles_kernel(DevParams P, PixMap pm, uint32_t pix_work, const float* __restrict__ packed, float* __restrict__ fb) {
-  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= pix_work) return;
-  uint32_t x, row;
-  if (!work_to_pixel(P, pm, w, x, row)) return;
-  float* p = fb + 3ull * ((size_t)row * P.nx + x);
-  p[0] = packed[3ull * w], p[1] = packed[3ull * w + 1], p[2] = packed[3ull * w + 2];
 }
 
 // RTG_FLAG_RESUME: scene i's full frame starts as the caller's running sums on the pixels it owns and +0 on every other pixel, so
@@ -222,19 +202,18 @@ static DeviceGroups group_by_device(rtg_scene* const* scenes, int n_scenes) {
   return g;
 }
 
-static int multi_stats(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params, rtg_stats* stats, bool count) {
+// rtg_stats of a call whose streams are drained: the slowest shard's kernel time, `samples`, the counters summed over the ranks
+static int multi_stats(rtg_scene* const* scenes, int n_scenes, uint64_t samples, rtg_stats* stats, bool count) {
   if (stats) {
     rtg_stats total{};
     total.struct_size = sizeof(rtg_stats);
+    total.samples = samples;
     for (int i = 0; i < n_scenes; i++) {
       rtg_scene* s = scenes[i];
       HIP_TRY(hipSetDevice(s->device));
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, s->cx->ev0, s->cx->ev1));
       total.kernel_ms = std::max(total.kernel_ms, ms);
-      DevParams d;
-      (void)rank_params(s, camera, params, i, n_scenes, &d);
-      total.samples += owned_pixels(d) * (d.ns - slice_of(params).begin);
       if (count) {
         unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIP_TRY(hipMemcpy(h, s->cx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
@@ -246,146 +225,182 @@ static int multi_stats(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   return RTG_OK;
 }
 
+// (1) The rank stage of both kinds of call: every scene renders ITS tiles (tile % n_scenes == i) of the frame L into its own device
+// frame, on its own stream.  `rp`: the caller's params with the flags the ranks render with -- never RTG_FLAG_BACKGROUND: a rank
+// gets the block in its parameters, from the checked host copy in `fb`.  `packed`: the packed collective will carry the ranks'
+// pixels (its kernels index a rank's work items with 32 bits, as launch_resolve and launch_counts do).  `fill(i, s, d)` enqueues
+// on s->own_stream what rank i's frame holds before it renders.  `features`: the feature pass follows the render (the planes do
+// not depend on each other): a counts call's compaction wait, a rank's one host wait, then covers no feature kernel, and the next
+// rank is launched while this one traces.  Every rank's parameters are checked before anything is enqueued; they come back in
+// `dps` with the samples of the call.
+using RankFill = std::function<int(int, rtg_scene*, const DevParams&)>;
+static int enqueue_ranks(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params& rp, const FrameLayout& L, const FrameBlocks& fb,
+                         bool packed, bool features, bool count, const RankFill& fill, std::vector<DevParams>* dps, uint64_t* samples) {
+  const SampleSlice rsl = slice_of(&rp);
+  const DevCamera cam = to_dev(camera);
+  dps->resize(n_scenes);
+  for (int i = 0; i < n_scenes; i++) {
+    DevParams& d = (*dps)[i];
+    if (int rc = rank_params(scenes[i], camera, &rp, i, n_scenes, &d)) return rc;
+    if (L.has(L.background)) d.bg = dev_background(fb.background);
+    if (packed && rank_pix_work(d) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: a rank's work items overflow the 32-bit work index");
+  }
+  *samples = 0;
+  for (int i = 0; i < n_scenes; i++) {
+    rtg_scene* s = scenes[i];
+    const DevParams& d = (*dps)[i];
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+    hipError_t e = s->frame.grow(L.words ? L.words * sizeof(float) : 16);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
+    if (int rc = fill(i, s, d)) return rc;
+    if (int rc = ctx_acquire(s)) return rc;
+    if (count) HIP_TRY(clear_counters(s->cx, s->own_stream));
+    HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
+    float* frame = s->frame.as<float>();
+    HIP_TRY(count ? launch_render<true>(s, cam, d, frame, s->own_stream, rsl, L, fb) : launch_render<false>(s, cam, d, frame, s->own_stream, rsl, L, fb));
+    if (features) HIP_TRY(launch_features(s, cam, d, frame, s->own_stream, L, fb.features));
+    HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
+    *samples += rsl.counts ? s->cx->counts_samples : owned_pixels(d) * (d.ns - rsl.begin);
+    if (int rc = ctx_release(s, s->own_stream)) return rc;
+  }
+  return RTG_OK;
+}
+
+// (2) The packed gather of both kinds of call, over the planes `ps` the ranks wrote (rt_multi_planes.h PlaneSet: one pack kernel,
+// one ncclSend / ncclRecv pair and one unpack kernel per handle that travels).  A handle without a work item is skipped; the first
+// handle's own pixels already stand in the frame unless it travels (a clique of one under force_rccl: its planes take the send /
+// recv path too, to itself); another handle on the first device is unpacked from its own pack buffer once its stream is drained.
+// The unpack kernels are left on the first handle's stream: the caller waits.  `verbose`: events around the pack kernels and in
+// front of the unpack kernels (s->pack0 / pack1, head->unpack0).  at_head[i]: where scene i's packed planes stand on the first
+// device (nullptr: nothing was packed); `through_rccl`: how many travelled.
+static int gather_planes(rtg_scene* const* scenes, int n_scenes, const DeviceGroups& g, const std::vector<DevParams>& dps, const PlaneSet& ps, bool force_rccl,
+                         bool verbose, std::vector<const uint32_t*>* at_head, size_t* through_rccl) {
+  rtg_scene* head = g.heads[0];  // (= scenes[0])
+  std::vector<PackedMove> moves;
+  at_head->assign(n_scenes, nullptr);
+  for (int i = 0; i < n_scenes; i++) {
+    rtg_scene* s = scenes[i];
+    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
+    const bool travels = g.of[i] != 0 || (force_rccl && g.devs.size() == 1 && i == 0);
+    if (pw == 0 || (s == head && !travels)) continue;
+    const size_t words = (size_t)pw * ps.words_per_pixel;
+    HIP_TRY(hipSetDevice(s->device));
+    hipError_t e = s->pack.grow(words * sizeof(uint32_t));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(packed planes)");
+    if (verbose) {
+      if (!s->pack0) HIP_TRY(hipEventCreate(&s->pack0));
+      if (!s->pack1) HIP_TRY(hipEventCreate(&s->pack1));
+      HIP_TRY(hipEventRecord(s->pack0, s->own_stream));
+    }
+    hipLaunchKernelGGL(pack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, s->own_stream, dps[i], make_pixmap(dps[i]), pw, ps, s->frame.as<const uint32_t>(),
+                       s->pack.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    if (verbose) HIP_TRY(hipEventRecord(s->pack1, s->own_stream));
+    if (travels) {
+      HIP_TRY(hipSetDevice(g.devs[0]));
+      e = s->recv.grow(words * sizeof(uint32_t));
+      if (e != hipSuccess) return hip_fail(e, "hipMalloc(received planes)");
+      moves.push_back(PackedMove{s->pack.as<float>(), s->recv.as<float>(), words, g.of[i], s->own_stream});
+      (*at_head)[i] = s->recv.as<uint32_t>();
+    } else {
+      (*at_head)[i] = s->pack.as<uint32_t>();
+      HIP_TRY(hipStreamSynchronize(s->own_stream));  // (another handle on the first device: its own stream)
+    }
+  }
+  *through_rccl = moves.size();
+  if (!moves.empty()) {
+    int rc = rccl_gather_tiles(g.devs, head->own_stream, moves);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipSetDevice(head->device));
+  if (verbose) {
+    if (!head->unpack0) HIP_TRY(hipEventCreate(&head->unpack0));
+    HIP_TRY(hipEventRecord(head->unpack0, head->own_stream));
+  }
+  for (int i = 0; i < n_scenes; i++) {
+    if (!(*at_head)[i]) continue;
+    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
+    hipLaunchKernelGGL(unpack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, head->own_stream, dps[i], make_pixmap(dps[i]), pw, ps, head->frame.as<uint32_t>(),
+                       (*at_head)[i]);
+    HIP_TRY(hipGetLastError());
+  }
+  return RTG_OK;
+}
+
+// ... and the wait behind either route: every handle's stream; the first device is current afterwards
+static int drain_streams(rtg_scene* const* scenes, int n_scenes) {
+  for (int i = n_scenes - 1; i >= 0; i--) {
+    HIP_TRY(hipSetDevice(scenes[i]->device));
+    HIP_TRY(hipStreamSynchronize(scenes[i]->own_stream));
+  }
+  return RTG_OK;
+}
+
+// The flags of a flagged frame, which needs scene option multi_planes on a handle (include/rtiow_gpu.h, at rtg_par_cast_multi)
+const struct { uint32_t flag; const char* name; } PLANE_FLAGS[5] = {{RTG_FLAG_SUM_SQUARES, "RTG_FLAG_SUM_SQUARES"}, {RTG_FLAG_SAMPLE_COUNTS, "RTG_FLAG_SAMPLE_COUNTS"}, {RTG_FLAG_RETIRE, "RTG_FLAG_RETIRE"},
+                                                                   {RTG_FLAG_DENOISE, "RTG_FLAG_DENOISE"}, {RTG_FLAG_FEATURES, "RTG_FLAG_FEATURES"}};
+
+// The plain frame: float3 sums, assembled on the first device by the full-frame reduce or, under scene option multi_gather, by
+// the packed gather of the one plane.
 int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera* camera, const rtg_params* params, float* out_rgb,
                         rtg_stats* stats) {
   const size_t n_floats = (size_t)params->nx * params->ny * 3;
   const size_t bytes = n_floats * sizeof(float);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
-  SampleSlice sl = slice_of(params);
-  const FrameLayout L(params->nx, params->ny, 0u);  // (the plain frame)
-  const FrameBlocks fb;
-  // RTG_FLAG_BACKGROUND: the block stands behind the plain frame in the caller's buffer; every rank gets it in its parameters
-  Background bg{BG_NONE, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-  if (sl.background) {
-    rtg_background b;
-    memcpy(&b, out_rgb + FrameLayout(params->nx, params->ny, RTG_FLAG_BACKGROUND).background, sizeof(b));
-    if (const char* why = background_refusal(b)) return fail(RTG_ERR_INVALID, why);
-    bg = dev_background(b);
-    sl.background = false;
-  }
-  // (1) every scene renders ITS tiles (tile % n_scenes == i) into its own zero-filled full frame, on its own stream (resuming a
-  // progressive frame: its tiles hold the caller's running sums)
-  for (int i = 0; i < n_scenes; i++) {
-    rtg_scene* s = scenes[i];
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, bytes ? bytes : 16);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
-    if (sl.begin != 0u) HIP_TRY(hipMemcpyAsync(s->d_frame, out_rgb, bytes, hipMemcpyHostToDevice, s->own_stream));
-    else HIP_TRY(hipMemsetAsync(s->d_frame, 0, bytes, s->own_stream));
-    {
-      const int rc_ctx = ctx_acquire(s);
-      if (rc_ctx) return rc_ctx;
-    }
-    DevParams d;
-    if (int rc = rank_params(s, camera, params, i, n_scenes, &d)) return rc;
-    d.bg = bg;
-    if (sl.begin != 0u) {
-      hipLaunchKernelGGL(keep_owned_kernel, dim3((uint32_t)(((size_t)d.nx * d.ny + 255) / 256)), dim3(256), 0, s->own_stream, d, s->d_frame);
-      HIP_TRY(hipGetLastError());
-    }
-    if (count) {
-      HIP_TRY(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), s->own_stream));
-      HIP_TRY(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), s->own_stream));
-    }
-    HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
-    const DevCamera cam = to_dev(camera);
-    HIP_TRY(count ? launch_render<true>(s, cam, d, s->d_frame, s->own_stream, sl, L, fb) : launch_render<false>(s, cam, d, s->d_frame, s->own_stream, sl, L, fb));
-    HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
-    {
-      const int rc_ctx = ctx_release(s, s->own_stream);
-      if (rc_ctx) return rc_ctx;
-    }
-  }
+  const SampleSlice sl = slice_of(params);
+  const FrameLayout L(params->nx, params->ny, params->flags);  // (the plain frame and, under RTG_FLAG_BACKGROUND, the block behind it)
+  FrameBlocks fb;
+  if (int rc = check_blocks(L, sl, out_rgb, 1u, &fb)) return rc;
+  rtg_params rp = *params;
+  rp.flags &= ~RTG_FLAG_BACKGROUND;
   bool gather = false, force_rccl = false;
   for (int i = 0; i < n_scenes; i++) {
     gather = gather || scenes[i]->multi_gather != 0;
     force_rccl = force_rccl || scenes[i]->force_rccl != 0;
   }
-  const DeviceGroups g = group_by_device(scenes, n_scenes);
-  const std::vector<int>& devs = g.devs;
-  const std::vector<rtg_scene*>& heads = g.heads;
-  if (gather) {
-    // (2') the packed collective: every scene packs ITS tiles (work-item order); the ones on other devices travel to the first
-    // device by grouped ncclSend / ncclRecv, and the first device scatters all of them into its frame
-    std::vector<PackedMove> moves;
-    std::vector<DevParams> dps(n_scenes);
-    std::vector<const float*> at_head(n_scenes, nullptr);  // where scene i's packed tiles stand on the first device
-    for (int i = 0; i < n_scenes; i++) {
-      rtg_scene* s = scenes[i];
-      if (int rc = rank_params(s, camera, params, i, n_scenes, &dps[i])) return rc;
-      const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
-      if (pw == 0) continue;
-      HIP_TRY(hipSetDevice(s->device));
-      hipError_t e = grow((void**)&s->d_pack, &s->pack_bytes, (size_t)pw * 3 * sizeof(float));
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc(packed tiles)");
-      hipLaunchKernelGGL(pack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, s->own_stream, dps[i], make_pixmap(dps[i]), pw, (const float*)s->d_frame, s->d_pack);
-      HIP_TRY(hipGetLastError());
-      // (a clique of one under force_rccl: the first scene's tiles take the send / recv path too, to itself)
-      const bool travels = g.of[i] != 0 || (force_rccl && devs.size() == 1 && i == 0);
-      if (travels) {
-        HIP_TRY(hipSetDevice(devs[0]));
-        e = grow((void**)&s->d_recv, &s->recv_bytes, (size_t)pw * 3 * sizeof(float));
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(received tiles)");
-        moves.push_back(PackedMove{s->d_pack, s->d_recv, (size_t)pw * 3, g.of[i], s->own_stream});
-        at_head[i] = s->d_recv;
-      } else {
-        at_head[i] = s->d_pack;
-        if (s != heads[0]) HIP_TRY(hipStreamSynchronize(s->own_stream));  // (another handle on the first device: its own stream)
-      }
+  // (1) into a zero-filled full frame (resuming a progressive frame: its tiles hold the caller's running sums)
+  const RankFill fill = [&](int, rtg_scene* s, const DevParams& d) -> int {
+    if (sl.begin == 0u) {
+      HIP_TRY(hipMemsetAsync(s->frame.p, 0, bytes, s->own_stream));
+      return RTG_OK;
     }
-    if (!moves.empty()) {
-      int rc = rccl_gather_tiles(devs, heads, moves);
+    HIP_TRY(hipMemcpyAsync(s->frame.p, out_rgb, bytes, hipMemcpyHostToDevice, s->own_stream));
+    hipLaunchKernelGGL(keep_owned_kernel, dim3((uint32_t)(((size_t)d.nx * d.ny + 255) / 256)), dim3(256), 0, s->own_stream, d, s->frame.as<float>());
+    HIP_TRY(hipGetLastError());
+    return RTG_OK;
+  };
+  std::vector<DevParams> dps;
+  uint64_t samples = 0;
+  if (int rc = enqueue_ranks(scenes, n_scenes, camera, rp, L, fb, gather, false, count, fill, &dps, &samples)) return rc;
+  const DeviceGroups g = group_by_device(scenes, n_scenes);
+  const std::vector<rtg_scene*>& heads = g.heads;
+  if (gather) {  // (2') the packed gather
+    std::vector<const uint32_t*> at_head;
+    size_t through_rccl = 0;
+    if (int rc = gather_planes(scenes, n_scenes, g, dps, make_plane_set(L, false), force_rccl, false, &at_head, &through_rccl)) return rc;
+  } else {
+    // (2) scenes that share a device with an earlier one are summed there; one frame per DISTINCT device remains
+    for (int i = 0; i < n_scenes; i++) {
+      rtg_scene *s = scenes[i], *h = heads[g.of[i]];
+      if (s == h) continue;
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(hipStreamSynchronize(s->own_stream));
+      hipLaunchKernelGGL(add_frames_kernel, dim3((uint32_t)((n_floats + 255) / 256)), dim3(256), 0, h->own_stream, n_floats, h->frame.as<float>(), s->frame.as<const float>());
+      HIP_TRY(hipGetLastError());
+    }
+    // (3) ONE collective over the distinct devices: reduce(sum) of the float3 framebuffer to the first device (xGMI).
+    // `force_rccl`: also with ONE distinct device (a clique of one) -- the same dlopen / ncclCommInitAll / grouped in-place
+    // ncclReduce code as on a node, which one-GPU test boxes could otherwise never execute.
+    if (g.devs.size() > 1 || force_rccl) {
+      int rc = rccl_reduce_frames(g.devs, heads, n_floats);
       if (rc) return rc;
     }
-    HIP_TRY(hipSetDevice(devs[0]));
-    for (int i = 0; i < n_scenes; i++) {
-      if (!at_head[i] || scenes[i] == heads[0]) continue;  // (the first scene's own tiles already stand in its frame)
-      const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
-      hipLaunchKernelGGL(unpack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, heads[0]->own_stream, dps[i], make_pixmap(dps[i]), pw, at_head[i], heads[0]->d_frame);
-      HIP_TRY(hipGetLastError());
-    }
-    if (at_head[0] == scenes[0]->d_recv && at_head[0]) {  // clique of one: what came back through RCCL replaces the first scene's tiles
-      const uint32_t pw = (uint32_t)rank_pix_work(dps[0]);
-      hipLaunchKernelGGL(unpack_tiles_kernel, dim3((pw + 255) / 256), dim3(256), 0, heads[0]->own_stream, dps[0], make_pixmap(dps[0]), pw, at_head[0], heads[0]->d_frame);
-      HIP_TRY(hipGetLastError());
-    }
-    for (rtg_scene* h : heads) {
-      HIP_TRY(hipSetDevice(h->device));
-      HIP_TRY(hipStreamSynchronize(h->own_stream));
-    }
-    for (int i = 0; i < n_scenes; i++) {
-      HIP_TRY(hipSetDevice(scenes[i]->device));
-      HIP_TRY(hipStreamSynchronize(scenes[i]->own_stream));
-    }
-    HIP_TRY(hipSetDevice(heads[0]->device));
-    HIP_TRY(hipMemcpy(out_rgb, heads[0]->d_frame, bytes, hipMemcpyDeviceToHost));
-    return multi_stats(scenes, n_scenes, camera, params, stats, count);
-  }
-  // (2) scenes that share a device with an earlier one are summed there; one frame per DISTINCT device remains
-  for (int i = 0; i < n_scenes; i++) {
-    rtg_scene *s = scenes[i], *h = heads[g.of[i]];
-    if (s == h) continue;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->own_stream));
-    hipLaunchKernelGGL(add_frames_kernel, dim3((uint32_t)((n_floats + 255) / 256)), dim3(256), 0, h->own_stream, n_floats, h->d_frame, s->d_frame);
-    HIP_TRY(hipGetLastError());
-  }
-  // (3) ONE collective over the distinct devices: reduce(sum) of the float3 framebuffer to the first device (xGMI).
-  // `force_rccl`: also with ONE distinct device (a clique of one) -- the same dlopen / ncclCommInitAll / grouped in-place
-  // ncclReduce code as on a node, which one-GPU test boxes could otherwise never execute.
-  if (devs.size() > 1 || force_rccl) {
-    int rc = rccl_reduce_frames(devs, heads, n_floats);
-    if (rc) return rc;
   }
   // (4) wait, copy the assembled frame out, gather stats (kernel time = the slowest shard)
-  for (rtg_scene* h : heads) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->own_stream));
-  }
-  HIP_TRY(hipSetDevice(heads[0]->device));
-  HIP_TRY(hipMemcpy(out_rgb, heads[0]->d_frame, bytes, hipMemcpyDeviceToHost));
-  return multi_stats(scenes, n_scenes, camera, params, stats, count);
+  if (int rc = drain_streams(scenes, n_scenes)) return rc;
+  HIP_TRY(hipMemcpy(out_rgb, heads[0]->frame.p, bytes, hipMemcpyDeviceToHost));
+  return multi_stats(scenes, n_scenes, samples, stats, count);
 }
 
 // The flagged frames (scene option multi_planes; include/rtiow_gpu.h at rtg_par_cast_multi): RTG_FLAG_SUM_SQUARES, SAMPLE_COUNTS,
@@ -394,9 +409,7 @@ int par_cast_multi_body(rtg_scene* const* scenes, int n_scenes, const rtg_camera
 // (1) every scene renders ITS tiles as a PARTIAL slice (squares / counts as given) into its own frame of the full layout, and
 //     traces the feature pass for the pixels it owns -- no retire rule, no filter, no division.  A rank's launch holds at most
 //     one host wait (a counts call's compaction), so launching the ranks in turn keeps the devices busy;
-// (2) the packed collective over EVERY plane the ranks wrote (rt_multi_planes.h PlaneSet: one pack kernel, one ncclSend /
-//     ncclRecv pair and one unpack kernel per handle that travels; handles on the first device are unpacked from their own
-//     buffer) assembles the frame on the first device.  Copies only;
+// (2) the packed gather over EVERY plane the ranks wrote assembles the frame on the first device.  Copies only;
 // (3) the first device runs what a one-handle call with sample_begin == ns runs on that frame: launch_post_steps (the retire
 //     step with any radius: the window sees the whole frame; the filter guided over the gathered feature planes; the division);
 // (4) copy back what rtg_par_cast copies back; traced / missed of the features block are the sums over the ranks.
@@ -408,140 +421,58 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
   const FrameLayout L(params->nx, params->ny, params->flags);
   FrameBlocks fb;
   if (int rc = check_blocks(L, sl, out_rgb, 1u, &fb)) return rc;
+  if (rank_pix_work(d1) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: the frame's work items overflow the 32-bit work index");
   const uint32_t compute = sl.features ? fb.features.compute : 0u;
   const PlaneSet ps = make_plane_set(L, compute != 0u);
   rtg_params rp = *params;  // what the ranks render into that frame: the slice, never retired, filtered or resolved
-  // (nor do they read the background block: they get it in their parameters, from the host copy)
   rp.flags = (rp.flags & ~(RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_DENOISE_ERROR | RTG_FLAG_FEATURES | RTG_FLAG_BACKGROUND)) | RTG_FLAG_PARTIAL;
-  const SampleSlice rsl = slice_of(&rp);
   const bool count = stats && (params->flags & RTG_FLAG_COUNTERS);
-  const DevCamera cam = to_dev(camera);
   char* host = reinterpret_cast<char*>(out_rgb);
-  std::vector<DevParams> dps(n_scenes);
-  for (int i = 0; i < n_scenes; i++) {
-    if (int rc = rank_params(scenes[i], camera, &rp, i, n_scenes, &dps[i])) return rc;
-    if (sl.background) dps[i].bg = dev_background(fb.background);
-    // (the pack / unpack kernels index a rank's work items with 32 bits, as launch_resolve and launch_counts do)
-    if (rank_pix_work(dps[i]) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: a rank's work items overflow the 32-bit work index");
-  }
-  if (rank_pix_work(d1) > 0xfffffffeull) return fail(RTG_ERR_RANGE, "rtg_par_cast_multi: the frame's work items overflow the 32-bit work index");
-  uint64_t samples = 0;
   // (1) the first scene's frame is the call's frame: uploaded as rtg_par_cast uploads it (untouched pixels and an untouched
   // output plane survive); the others get what their slice reads -- the float planes when it resumes or renders counts (pixels
   // with n_p = 0 must travel back as they came), and the count plane.  The feature pass takes its in-fields from the host copy.
   Extents rank_up;
   if (sl.begin != 0u || sl.counts) rank_up.add(0, sl.counts ? L.counts + L.n : L.planes());
-  for (int i = 0; i < n_scenes; i++) {
-    rtg_scene* s = scenes[i];
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    hipError_t e = grow((void**)&s->d_frame, &s->frame_bytes, L.words * sizeof(float));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(framebuffer)");
-    char* dev = reinterpret_cast<char*>(s->d_frame);
+  const RankFill fill = [&](int i, rtg_scene* s, const DevParams&) -> int {
     const Extents up = i == 0 ? upload_extents(L, false, sl.begin, compute) : rank_up;
-    for (int k = 0; k < up.n; k++) HIP_TRY(hipMemcpyAsync(dev + up.e[k].lo, host + up.e[k].lo, up.e[k].hi - up.e[k].lo, hipMemcpyHostToDevice, s->own_stream));
-    {
-      const int rc_ctx = ctx_acquire(s);
-      if (rc_ctx) return rc_ctx;
-    }
-    if (count) {
-      HIP_TRY(hipMemsetAsync(s->cx->d_counters, 0, 7 * sizeof(unsigned long long), s->own_stream));
-      HIP_TRY(hipMemsetAsync(s->cx->d_counters + 8, 0, 24 * sizeof(unsigned long long), s->own_stream));
-    }
-    HIP_TRY(hipEventRecord(s->cx->ev0, s->own_stream));
-    HIP_TRY(count ? launch_render<true>(s, cam, dps[i], s->d_frame, s->own_stream, rsl, L, fb) : launch_render<false>(s, cam, dps[i], s->d_frame, s->own_stream, rsl, L, fb));
-    // the feature pass BEHIND the render (the planes do not depend on each other): a counts call's compaction wait, the rank's
-    // one host wait, then covers no feature kernel, and the next rank is launched while this one traces
-    if (sl.features) HIP_TRY(launch_features(s, cam, dps[i], s->d_frame, s->own_stream, L, fb.features));
-    HIP_TRY(hipEventRecord(s->cx->ev1, s->own_stream));
-    samples += rsl.counts ? s->cx->counts_samples : owned_pixels(dps[i]) * (dps[i].ns - rsl.begin);
-    {
-      const int rc_ctx = ctx_release(s, s->own_stream);
-      if (rc_ctx) return rc_ctx;
-    }
-  }
+    for (int k = 0; k < up.n; k++) HIP_TRY(hipMemcpyAsync(s->frame.as<char>() + up.e[k].lo, host + up.e[k].lo, up.e[k].hi - up.e[k].lo, hipMemcpyHostToDevice, s->own_stream));
+    return RTG_OK;
+  };
+  std::vector<DevParams> dps;
+  uint64_t samples = 0;
+  if (int rc = enqueue_ranks(scenes, n_scenes, camera, rp, L, fb, true, sl.features, count, fill, &dps, &samples)) return rc;
   bool force_rccl = false, verbose = false;
   for (int i = 0; i < n_scenes; i++) force_rccl = force_rccl || scenes[i]->force_rccl != 0, verbose = verbose || scenes[i]->verbose != 0;
   const DeviceGroups g = group_by_device(scenes, n_scenes);
   rtg_scene* head = g.heads[0];  // (= scenes[0])
-  // (2) pack, travel, unpack
-  std::vector<PackedMove> moves;
-  std::vector<const uint32_t*> at_head(n_scenes, nullptr);  // where scene i's packed planes stand on the first device
-  for (int i = 0; i < n_scenes; i++) {
-    rtg_scene* s = scenes[i];
-    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
-    // (a clique of one under force_rccl: the first scene's planes take the send / recv path too, to itself)
-    const bool travels = g.of[i] != 0 || (force_rccl && g.devs.size() == 1 && i == 0);
-    if (pw == 0 || (s == head && !travels)) continue;  // (the first scene's own pixels already stand in the frame)
-    const size_t words = (size_t)pw * ps.words_per_pixel;
-    HIP_TRY(hipSetDevice(s->device));
-    hipError_t e = grow((void**)&s->d_pack, &s->pack_bytes, words * sizeof(uint32_t));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(packed planes)");
-    if (verbose) {
-      if (!s->pack0) HIP_TRY(hipEventCreate(&s->pack0));
-      if (!s->pack1) HIP_TRY(hipEventCreate(&s->pack1));
-      HIP_TRY(hipEventRecord(s->pack0, s->own_stream));
-    }
-    hipLaunchKernelGGL(pack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, s->own_stream, dps[i], make_pixmap(dps[i]), pw, ps,
-                       reinterpret_cast<const uint32_t*>(s->d_frame), reinterpret_cast<uint32_t*>(s->d_pack));
-    HIP_TRY(hipGetLastError());
-    if (verbose) HIP_TRY(hipEventRecord(s->pack1, s->own_stream));
-    if (travels) {
-      HIP_TRY(hipSetDevice(g.devs[0]));
-      e = grow((void**)&s->d_recv, &s->recv_bytes, words * sizeof(uint32_t));
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc(received planes)");
-      moves.push_back(PackedMove{s->d_pack, s->d_recv, words, g.of[i], s->own_stream});
-      at_head[i] = reinterpret_cast<const uint32_t*>(s->d_recv);
-    } else {
-      at_head[i] = reinterpret_cast<const uint32_t*>(s->d_pack);
-      HIP_TRY(hipStreamSynchronize(s->own_stream));  // (another handle on the first device: its own stream)
-    }
-  }
-  if (!moves.empty()) {
-    int rc = rccl_gather_tiles(g.devs, g.heads, moves);
-    if (rc) return rc;
-  }
-  HIP_TRY(hipSetDevice(head->device));
   const hipStream_t hs = head->own_stream;
-  if (verbose) {
-    if (!head->unpack0) HIP_TRY(hipEventCreate(&head->unpack0));
-    HIP_TRY(hipEventRecord(head->unpack0, hs));
-  }
-  for (int i = 0; i < n_scenes; i++) {
-    if (!at_head[i]) continue;
-    const uint32_t pw = (uint32_t)rank_pix_work(dps[i]);
-    hipLaunchKernelGGL(unpack_planes_kernel, dim3((pw + 255) / 256), dim3(256), 0, hs, dps[i], make_pixmap(dps[i]), pw, ps,
-                       reinterpret_cast<uint32_t*>(head->d_frame), at_head[i]);
-    HIP_TRY(hipGetLastError());
-  }
+  // (2) pack, travel, unpack
+  std::vector<const uint32_t*> at_head;
+  size_t through_rccl = 0;
+  if (int rc = gather_planes(scenes, n_scenes, g, dps, ps, force_rccl, verbose, &at_head, &through_rccl)) return rc;
   // (3) the first device's step over the assembled frame, through the launch functions of the one-handle call
   if (!head->post0) HIP_TRY(hipEventCreate(&head->post0));
   if (!head->post1) HIP_TRY(hipEventCreate(&head->post1));
   HIP_TRY(hipEventRecord(head->post0, hs));
-  HIP_TRY(launch_post_steps(head, d1, head->d_frame, hs, sl, L, fb));
+  HIP_TRY(launch_post_steps(head, d1, head->frame.as<float>(), hs, sl, L, fb));
   HIP_TRY(hipEventRecord(head->post1, hs));
   // (4) wait, copy out
   HIP_TRY(hipStreamSynchronize(hs));
-  for (int i = 0; i < n_scenes; i++) {
-    HIP_TRY(hipSetDevice(scenes[i]->device));
-    HIP_TRY(hipStreamSynchronize(scenes[i]->own_stream));
-  }
+  if (int rc = drain_streams(scenes, n_scenes)) return rc;
   if (sl.features) {  // traced / missed: the sums over the ranks' blocks, into the first scene's before it is copied out
     uint32_t sum[2] = {0u, 0u};
     const size_t at = L.features * sizeof(uint32_t) + offsetof(rtg_features, traced);
     for (int i = 0; i < n_scenes; i++) {
       uint32_t tm[2] = {0u, 0u};
       HIP_TRY(hipSetDevice(scenes[i]->device));
-      HIP_TRY(hipMemcpy(tm, reinterpret_cast<const char*>(scenes[i]->d_frame) + at, sizeof(tm), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(tm, scenes[i]->frame.as<const char>() + at, sizeof(tm), hipMemcpyDeviceToHost));
       sum[0] += tm[0], sum[1] += tm[1];
     }
     HIP_TRY(hipSetDevice(head->device));
-    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(head->d_frame) + at, sum, sizeof(sum), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(head->frame.as<char>() + at, sum, sizeof(sum), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipSetDevice(head->device));
   const Extents back = copy_back_extents(L, compute);
-  for (int k = 0; k < back.n; k++)
-    HIP_TRY(hipMemcpy(host + back.e[k].lo, reinterpret_cast<const char*>(head->d_frame) + back.e[k].lo, back.e[k].hi - back.e[k].lo, hipMemcpyDeviceToHost));
+  for (int k = 0; k < back.n; k++) HIP_TRY(hipMemcpy(host + back.e[k].lo, head->frame.as<const char>() + back.e[k].lo, back.e[k].hi - back.e[k].lo, hipMemcpyDeviceToHost));
   if (verbose) {  // the pack kernels (summed over the handles) and the first device's unpack kernels, by their events
     float pack_ms = 0.f, unpack_ms = 0.f;
     uint64_t items = 0;
@@ -556,15 +487,14 @@ int par_cast_multi_planes_body(rtg_scene* const* scenes, int n_scenes, const rtg
     HIP_TRY(hipEventElapsedTime(&unpack_ms, head->unpack0, head->post0));
     // (tools/multi_planes_cost.py parses this line -- VERBOSE_LINE there: change both together)
     fprintf(stderr, "[rtg] multi planes: %d handle(s) on %zu device(s), %u words per pixel, %llu work items packed (%llu bytes), %zu through RCCL; pack %.4f ms, unpack %.4f ms\n",
-            n_scenes, g.devs.size(), ps.words_per_pixel, (unsigned long long)items, (unsigned long long)(items * ps.words_per_pixel * 4u), moves.size(), pack_ms, unpack_ms);
+            n_scenes, g.devs.size(), ps.words_per_pixel, (unsigned long long)items, (unsigned long long)(items * ps.words_per_pixel * 4u), through_rccl, pack_ms, unpack_ms);
   }
-  if (int rc = multi_stats(scenes, n_scenes, camera, &rp, stats, count)) return rc;
+  if (int rc = multi_stats(scenes, n_scenes, samples, stats, count)) return rc;
   if (stats) {  // the slowest shard's render span + the first device's span for retire / filter / division
     float ms = 0.f;
     HIP_TRY(hipSetDevice(head->device));
     HIP_TRY(hipEventElapsedTime(&ms, head->post0, head->post1));
     stats->kernel_ms += ms;
-    stats->samples = samples;
   }
   return RTG_OK;
 }
@@ -581,12 +511,10 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
   // the flagged frames need scene option multi_planes on a handle (include/rtiow_gpu.h, at rtg_par_cast_multi)
   bool planes = false;
   for (int i = 0; i < n_scenes; i++) planes = planes || (scenes[i] && scenes[i]->multi_planes != 0);
-  if (!planes) {
-    if (params->flags & RTG_FLAG_SUM_SQUARES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SUM_SQUARES is not supported without scene option multi_planes");
-    if (params->flags & RTG_FLAG_SAMPLE_COUNTS) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_SAMPLE_COUNTS is not supported without scene option multi_planes");
-    if (params->flags & RTG_FLAG_RETIRE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_RETIRE is not supported without scene option multi_planes");
-    if (params->flags & RTG_FLAG_DENOISE) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_DENOISE is not supported without scene option multi_planes");
-    if (params->flags & RTG_FLAG_FEATURES) return fail(RTG_ERR_UNSUPPORTED, "rtg_par_cast_multi: RTG_FLAG_FEATURES is not supported without scene option multi_planes");
+  uint32_t plane_flags = 0;
+  for (const auto& f : PLANE_FLAGS) {
+    if (!planes && (params->flags & f.flag)) return fail(RTG_ERR_UNSUPPORTED, std::string("rtg_par_cast_multi: ") + f.name + " is not supported without scene option multi_planes");
+    plane_flags |= f.flag;
   }
   for (int i = 0; i < n_scenes; i++) {
     if (!scenes[i]) return fail(RTG_ERR_INVALID, "null scene handle");
@@ -597,7 +525,6 @@ int rtg_par_cast_multi(rtg_scene* const* scenes, int n_scenes, const rtg_camera*
     if (scenes[i]->light_sampling != scenes[0]->light_sampling) return fail(RTG_ERR_INVALID, "rtg_par_cast_multi: the handles disagree on scene option light_sampling");
   }
   // a call without any of the five flags is the plain frame whatever the option says
-  const uint32_t plane_flags = RTG_FLAG_SUM_SQUARES | RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_RETIRE | RTG_FLAG_DENOISE | RTG_FLAG_FEATURES;
   const int rc = (params->flags & plane_flags) ? par_cast_multi_planes_body(scenes, n_scenes, camera, params, out_rgb, stats)
                                                : par_cast_multi_body(scenes, n_scenes, camera, params, out_rgb, stats);
   if (rc != RTG_OK) {

@@ -52,13 +52,13 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
     HIP_TRY(d_trace.alloc(table + slots));
     HIP_TRY(hipMemset(d_trace.p, 0, (table + slots) * sizeof(uint32_t)));
     if ((rc = ctx_acquire(s))) return rc;
-    HIP_TRY(grow((void**)&s->d_frame, &s->frame_bytes, (size_t)d.nx * d.ny * 3 * sizeof(float)));
+    HIP_TRY(s->frame.grow((size_t)d.nx * d.ny * 3 * sizeof(float)));
     HIP_TRY(hipMemset(s->cx->d_counters, 0, 32 * sizeof(unsigned long long)));
     const unsigned long long ptrs[2] = {(unsigned long long)(uintptr_t)d_trace.p, (unsigned long long)(uintptr_t)(d_trace.p + table)};
     HIP_TRY(hipMemcpy(s->cx->d_counters + 30, ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
     const DevCamera cam = to_dev(camera);
     s->whole_scratch = true;  // the trace reads every sample colour back: one sample pass
-    hipError_t e = launch_render<true>(s, cam, d, s->d_frame, nullptr, SampleSlice{}, FrameLayout(d.nx, d.ny, 0u), FrameBlocks{});
+    hipError_t e = launch_render<true>(s, cam, d, s->frame.as<float>(), nullptr, SampleSlice{}, FrameLayout(d.nx, d.ny, 0u), FrameBlocks{});
     s->whole_scratch = false;
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipMemset(s->cx->d_counters + 30, 0, 2 * sizeof(unsigned long long));
@@ -68,7 +68,7 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
     std::vector<uint32_t> h_trace(table);
     std::vector<float> h_col((size_t)3 * d.ns * pix_work);
     HIP_TRY(hipMemcpy(h_trace.data(), d_trace.p, table * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_col.data(), s->cx->d_scratch, h_col.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_col.data(), s->cx->scratch.p, h_col.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) {
       const uint32_t x = xs[i], row = d.ny - 1u - ys[i], sm = samples[i];
       const uint32_t tx = x / d.tile_w, ty = row / d.tile_h, tile = ty * tiles_x + tx;

@@ -234,7 +234,9 @@ def test_par_cast_multi_packed_collective(pkg, gpu, oracle):
     """Scene option multi_gather = 1: every handle ships only the tiles it owns (packed in work-item order) and the first device
     scatters them into the frame -- grouped ncclSend / ncclRecv instead of the full-frame ncclReduce.  Copies only: the frame is the
     oracle's bit for bit with 1, 2, 3 and 8 handles, ragged sizes and both tile sizes; with force_rccl the first handle's tiles take
-    the send / recv path on this one-GPU box too (a clique of one), and rtg_multi_reset counts the transfers."""
+    the send / recv path on this one-GPU box too (a clique of one), and rtg_multi_reset counts the transfers.  The packed buffer is
+    plane-major (rt_multi_planes.h, the one-group PlaneSet): the two smallest frames at the end cover ranks without a tile, a
+    ragged tile and padded work items, with and without force_rccl."""
     for name, nx, ny, ns in (("book1", 176, 112, 6), ("book2", 100, 76, 4)):
         so, cam_o, _, _, _ = build_case(pkg, oracle, name, nx, ny)
         ref, st_o = so.par_cast(cam_o, nx, ny, ns, stats=True)
@@ -266,6 +268,27 @@ def test_par_cast_multi_packed_collective(pkg, gpu, oracle):
         assert_bit_equal(gpu.par_cast_multi(scenes, cam_g, nx, ny, ns), ref, "force_rccl + packed, %d handles" % n)
     issued = gpu.multi_reset()
     assert issued == (2 if n_dev < 2 else 1 + 1), issued   # one transfer per handle that travels (one GPU: the first handle, to itself)
+    # the smallest frames of the plane-major packed buffer, 3 handles: ONE ragged tile (two ranks own nothing), and two 8x8 tiles
+    # per rank (128 work items padded to 256) with pixels beyond the image inside the tiles
+    for nx, ny, tile in ((16, 8, 0), (20, 12, 8)):
+        so, cam_o, _, _, _ = build_case(pkg, oracle, "book1", nx, ny)
+        ref, st_o = so.par_cast(cam_o, nx, ny, 5, stats=True)
+        owners = {t % 3 for t in range(((nx + 7) // 8) * ((ny + 7) // 8) if tile else 1)}
+        for force in (0, 1):
+            scenes = []
+            for i in range(3):
+                b = gpu.builder()
+                world, cam_g, _ = pkg.scenes.random_scene(b, nx, ny)
+                sg = b.scene(world, device=i % min(n_dev, 2))
+                sg.set_option("force_rccl", force)
+                sg.set_option("multi_gather", 1)
+                scenes.append(sg)
+            img, st = gpu.par_cast_multi(scenes, cam_g, nx, ny, 5, stats=True, tile_w=tile, tile_h=tile)
+            assert_bit_equal(img, ref, "%d x %d, 3 handles, packed, force_rccl %d" % (nx, ny, force))
+            for k in ("samples", "aabb_tests", "prim_tests", "shaded_hits", "rays", "draws"):
+                assert st[k] == st_o[k], (nx, ny, force, k)
+            # one transfer per handle that travels: on one GPU the first handle to itself under force_rccl, else the owners on device 1
+            assert gpu.multi_reset() == (force if n_dev < 2 else len([i for i in owners if i % 2])), (nx, ny, force)
 
 
 @pytest.mark.parametrize("name,nx,ny,ns,mb", [("cornell", 300, 300, 400, 16), ("book1", 300, 300, 400, 16), ("book2", 160, 160, 60, 1),

@@ -243,6 +243,24 @@ def test_multi_gpu_slices(pkg, gpu, gather):
                 assert_bit_equal(preview, ref4, "multi n=%d gather=%d resolve at 4" % (n, gather))
         assert_bit_equal(acc, ref, "multi n=%d gather=%d" % (n, gather))
         assert total == {k: st_ref[k] for k in COUNTERS}, (n, gather, total)
+    # 20 x 12 in 8x8 tiles over 3 handles (two tiles per rank, pixels beyond the image inside them), as a PARTIAL then RESUME
+    # pair: the resumed ranks start from the caller's sums on their own tiles and +0 elsewhere
+    nx, ny, ns = 20, 12, 6
+    ref_scene, cam_g, _, _, _ = build_case(pkg, gpu, "book1", nx, ny)
+    ref, st_ref = ref_scene.par_cast(cam_g, nx, ny, ns, stats=True)
+    scenes = []
+    for _ in range(3):
+        sg, _, _, _, _ = build_case(pkg, gpu, "book1", nx, ny)
+        sg.set_option("multi_gather", gather)
+        scenes.append(sg)
+    acc = np.full((ny, nx, 3), NAN_BITS, dtype=np.uint32).view(np.float32)
+    total = {}
+    for b, e in ((0, 2), (2, ns)):
+        _, st = gpu.par_cast_multi(scenes, cam_g, nx, ny, e, out=acc, sample_begin=b, resume=b != 0, partial=e != ns, stats=True, tile_w=8, tile_h=8)
+        for k in COUNTERS:
+            total[k] = total.get(k, 0) + st[k]
+    assert_bit_equal(acc, ref, "multi 20 x 12, 3 handles, gather=%d, 2 + 4 samples" % gather)
+    assert total == {k: st_ref[k] for k in COUNTERS}, (gather, total)
     gpu.multi_reset()
 
 
