@@ -322,6 +322,14 @@ def _stream(stream):
     return C.c_void_p(getattr(stream, "cuda_stream", stream) or None)
 
 
+class _no_context:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
 def _hip_ok(rc, what):
     if rc != 0:
         raise RtError(ERR_DEVICE, "%s failed: %d" % (what, rc))
@@ -671,6 +679,16 @@ ABI_SYMBOLS = [
 ]
 # every symbol include/rtiow_gpu_query.h declares: beside the ABI above, not part of it (no CPU restatement mirrors ray queries)
 QUERY_SYMBOLS = ["query_closest", "query_closest_device", "query_occluded", "query_occluded_device"]
+# include/rtiow_gpu_rays.h: ray frames (not part of ABI_SYMBOLS either)
+RAY_FRAME_SYMBOLS = ["par_cast_rays", "par_cast_rays_device"]
+RAYS_PER_PIXEL, RAYS_PER_SAMPLE = 0, 1
+
+
+def ray_index(nx, ny, sample, row, x, per_sample):
+    """Which ray of a ray frame's array starts sample `sample` of pixel (x, row): include/rtiow_gpu_rays.h.  Plain Python
+    integers: exact beyond 2^32 rays."""
+    p = int(row) * int(nx) + int(x)
+    return int(sample) * int(nx) * int(ny) + p if per_sample else p
 
 
 class Backend:
@@ -743,6 +761,9 @@ class Backend:
         f("query_closest_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, C.c_void_p, C.c_void_p, st])
         f("query_occluded", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, st])
         f("query_occluded_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, qp, C.c_void_p, C.c_void_p, st])
+        # include/rtiow_gpu_rays.h (RAY_FRAME_SYMBOLS): the same convention
+        f("par_cast_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Params), C.c_void_p, st])
+        f("par_cast_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Params), C.c_void_p, C.c_void_p, st])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -1068,7 +1089,7 @@ class Scene:
     # measurement / test hook: RTG_<OPTION>=<int> in the environment of the PYTHON process becomes
     # rtg_scene_set_option(scene, "<option>", <int>) -- the library itself reads no environment variable
     ENV_OPTIONS = ("kernel", "chunks", "lpt", "lpt_phase1", "lpt_deep", "lpt_shift", "ray_lds", "sync", "block", "wg_per_cu", "window",
-                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "box_camera", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling", "query_lds", "query_refill")
+                   "box_leave", "refill_min", "gather_min", "run_ahead", "run_ahead_min", "sphere_min", "verbose", "bvh4", "box_chains", "box_prune", "box_tree", "box_camera", "force_rccl", "multi_gather", "multi_planes", "scratch_mb", "frames_in_flight", "small_frames", "drain_share", "hoist", "deep_sized", "mat_lds", "pool2", "p2_refill", "p2_box_leave", "p2_park", "p2_sphere", "p2_prism", "p2_list", "p2_push", "light_sampling", "query_lds", "query_refill", "ray_pool")
 
     def set_option(self, name, value):
         self.be.check(self.be._scene_set_option(self.h, name.encode(), int(value)))
@@ -1517,6 +1538,80 @@ class Scene:
         """Is anything hit in [t_min, t_max)?  rays [n, 8]: (origin, direction, time, t_max); uint8 [n].  A ConstantMedium
         blocks with probability 1 - transmittance.  stats=True: (out, stats)."""
         return self._query("occluded", 8, rays, seed, t_min, first_index, stream, stats, ((None, np.uint8, "uint8"),))
+
+    # ---- ray frames (include/rtiow_gpu_rays.h) -----------------------------------------------------------------------
+    def cast_rays(self, rays, nx, ny, ns, per_sample=False, seed=0xDEADBEEF, max_bounces=50, flags=0, sample_begin=0, out=None,
+                  background=None, rank=0, nranks=1, stream=None, t_near=0.001, tile_w=0, tile_h=0, stats=False):
+        """Path-trace the caller's rays into a frame: float32 [ny, nx, 3] (row 0 = top), or [2, ny, nx, 3] with
+        FLAG_SUM_SQUARES in `flags`.  rays: [nx * ny, 7] (origin, direction, time), ray p = row * nx + x starting every sample
+        of pixel p; per_sample=True: [ns * nx * ny, 7], sample s of pixel p at s * nx * ny + p (rays.camera_rays makes the
+        library's own camera rays in that layout).  A numpy array takes the host entry point and returns numpy; a torch
+        tensor on the scene's device takes the device entry point on `stream` (default: the current torch stream) and returns
+        a torch tensor, without a host round trip.
+        flags: FLAG_PARTIAL / FLAG_RESUME (with sample_begin) / FLAG_SUM_SQUARES; out: the frame to continue or to write into
+        (the same kind and shape as the result; rendered in place when it is contiguous and the call has no background).
+        background= (FLAG_BACKGROUND): a colour, a dict of bottom / top, or a Background (make_background).
+        rank / nranks / tile_w / tile_h: as in par_cast -- pixels of other ranks keep what `out` held.
+        stats=True returns (frame, rtg_stats as a dict)."""
+        mode = RAYS_PER_SAMPLE if per_sample else RAYS_PER_PIXEL
+        n_rays = ray_index(nx, ny, ns if per_sample else 1, 0, 0, True)
+        if _given(background):
+            flags |= FLAG_BACKGROUND
+        squares = bool(flags & FLAG_SUM_SQUARES)
+        lay = FrameLayout(nx, ny, squares=squares, background=bool(flags & FLAG_BACKGROUND))
+        shape = (2, ny, nx, 3) if squares else (ny, nx, 3)
+        planes = (6 if squares else 3) * nx * ny
+        p = make_params(nx, ny, ns, seed=seed, max_bounces=max_bounces, t_near=t_near, tile_w=tile_w, tile_h=tile_h, rank=rank,
+                        nranks=nranks, flags=flags, sample_begin=sample_begin)
+        block = make_background(background) if _given(background) and background is not True else None
+        st = Stats.new() if stats else None
+        st_arg = C.byref(st) if stats else None
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if not rays.is_cuda:
+                raise ValueError("cast_rays: a torch tensor must live on the scene's device (pass a numpy array for host rays)")
+            if rays.dtype != torch.float32 or not rays.is_contiguous():   # (no temporary copy: the call returns before the kernel reads it)
+                raise ValueError("cast_rays: the rays must be a contiguous float32 tensor")
+            if rays.numel() != 7 * n_rays:
+                raise ValueError("cast_rays: %d floats of rays, expected %d x 7" % (rays.numel(), n_rays))
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device)
+            in_place = out is not None and lay.words == planes and out.is_contiguous() and out.dtype == torch.float32
+            if out is not None and tuple(out.shape) != shape:
+                raise ValueError("cast_rays: out must have shape %r" % (shape,))
+            with torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _no_context():
+                buf = out.reshape(-1) if in_place else torch.zeros(lay.words, dtype=torch.float32, device=rays.device)
+                if out is not None and not in_place:
+                    buf[:planes].copy_(out.reshape(-1))
+            if isinstance(stream, torch.cuda.Stream):
+                buf.record_stream(stream)
+            if block is not None:
+                self._block_copy(buf, block, stream, True, 4 * lay.background, Background.OUT_OFFSET)
+            self.be.check(self.be._par_cast_rays_device(self.h, _device_ptr(rays), mode, C.byref(p), _device_ptr(buf), _stream(stream), st_arg))
+            res = out if in_place else buf[:planes].reshape(shape)
+            if out is not None and not in_place:
+                with torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _no_context():
+                    out.copy_(res)
+                res = out
+        else:
+            rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
+            if rays.shape[0] != n_rays:
+                raise ValueError("cast_rays: %d rays, expected %d" % (rays.shape[0], n_rays))
+            if out is not None and tuple(out.shape) != shape:
+                raise ValueError("cast_rays: out must have shape %r" % (shape,))
+            in_place = (out is not None and lay.words == planes and isinstance(out, np.ndarray) and out.dtype == np.float32
+                        and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"])
+            buf = out.reshape(-1) if in_place else np.zeros(lay.words, dtype=np.float32)
+            if out is not None and not in_place:
+                buf[:planes] = np.asarray(out, dtype=np.float32).reshape(-1)
+            if block is not None:
+                C.memmove(buf.ctypes.data + 4 * lay.background, C.addressof(block), C.sizeof(Background))
+            self.be.check(self.be._par_cast_rays(self.h, rays.ctypes.data, mode, C.byref(p), buf.ctypes.data, st_arg))
+            res = out if in_place else buf[:planes].reshape(shape)
+            if out is not None and not in_place:
+                out[...] = res
+                res = out
+        return (res, st.as_dict()) if stats else res
 
     def debug_samples(self, camera, nx, ny, ns, xs, ys, samples, seed=0xDEADBEEF, trace_kernel=False, **kw):
         """trace_kernel=True: read the keys out of the production ray-pool kernel's per-sample trace (whole frame rendered)."""

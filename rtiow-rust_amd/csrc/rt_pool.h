@@ -300,6 +300,11 @@ struct LaunchConsts {
   uint32_t seg_first, seg_end;  // full-feature pool kernel: the records of the hoisted segment as program counters (flat_scene.h OP_SEG);
                                 // seg_end = 0: no segment, or hoisting switched off -- OP_SEG is then stepped over
   uint32_t p2_lists;            // pool-2 kernel (rt_pool2.h): byte offset of the waves' id lists in LDS
+  // Ray frames (include/rtiow_gpu_rays.h), the RAYS instantiations of the lean pool kernel: the caller's rays, 7 floats each, and
+  // their layout -- 0: ray p starts every sample of pixel p, else: sample s of pixel p at s * nx * ny + p.  At the END: no offset
+  // above moves, and the kernels that never read them keep their text.
+  const float* rays;
+  uint32_t ray_mode, ray_pad;
 };
 typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
 template <typename T>
@@ -714,7 +719,10 @@ RT_DEV uint4 fetch_hi_global(const DevScene& sc, uint32_t idx) {  // pc-scaled s
 // from the winning SPHERE record (the flattener copies the material kind into its flag word).
 // HOT_LDS: the hot slot fields -- the ray (o, d) and (best, best_pc), see pool_lds_bytes -- live in LDS when the
 // program leaves room; the cold fields stay in the global SoA region.
-template <bool USE_LDS, bool COUNT, bool HOT_LDS, bool WIDE = false, bool LIST = false>
+// RAYS (ray frames, include/rtiow_gpu_rays.h): a path's first ray is the caller's -- the END pass loads it from LaunchConsts::rays
+// where the other instantiations draw event 0 and call get_ray; nothing else of the kernel sees the difference (color() restarts
+// the stream at event 1).  Instantiated without COUNT, WIDE and LIST only.
+template <bool USE_LDS, bool COUNT, bool HOT_LDS, bool WIDE = false, bool LIST = false, bool RAYS = false>
 __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void render_lean_pool(
     DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out, uint32_t total_work, uint32_t* __restrict__ queue,
     unsigned long long* counters, PoolTuning tune, uint32_t* __restrict__ g_slots) {
@@ -1235,17 +1243,27 @@ __global__ __launch_bounds__(RT_POOL_MAX_THREADS, RT_POOL_WAVES_PER_EU) void ren
         }
         const bool live = st == ST_GEN;
         if (live) {  // par_cast closure, lib.rs:366-371 (event 0) and color()'s initial state, lib.rs:62-67
+          V3 so, sd;
+          if constexpr (RAYS) {  // the caller's ray: no event-0 draw (a lean program has nothing that reads the ray's time)
+            // 24 of a ray's 28 bytes per lane, at stride 28 over the pixels of a grab: global loads (not flat ones, which would
+            // also count on lgkmcnt), inside the ray's own seven floats
+            typedef const __attribute__((address_space(1))) float* g_ray_ptr;
+            const uint64_t pixel = (uint64_t)row * P.nx + x;
+            const uint64_t at = load_const(&lc->ray_mode) != 0u ? (uint64_t)s * ((uint64_t)P.nx * P.ny) + pixel : pixel;
+            const g_ray_ptr ray = (g_ray_ptr)(uintptr_t)(load_const(&lc->rays) + 7ull * at);
+            so = mk(ray[0], ray[1], ray[2]), sd = mk(ray[3], ray[4], ray[5]);
+          } else {
           const uint32_t y = P.ny - 1u - row;
           SampleRng rng;
           rng.init(seed, y * P.nx + x, s);
           float u = ((float)x + rng.gen_f32()) / (float)P.nx;
           float v = ((float)y + rng.gen_f32()) / (float)P.ny;
-          V3 so, sd;
           float time;
           const DevCamera cam = load_const(&lc->cam);
           get_ray(cam, u, v, rng, so, sd, time);
           if (COUNT) total_draws += rng.draws, cnt.rays++;
           if (COUNT && tr_slot) tr_slot[j] = rng.draws, tr_slot[POOL + j] = 0u, tr_slot[2u * POOL + j] = 0u;
+          }
           RAY_F(PF_O, j) = so.x, RAY_F(PF_O + 1, j) = so.y, RAY_F(PF_O + 2, j) = so.z;
           RAY_F(PF_D, j) = sd.x, RAY_F(PF_D + 1, j) = sd.y, RAY_F(PF_D + 2, j) = sd.z;
           if (!cm.scratch) SLOT_F(PF_COL, j) = col.x, SLOT_F(PF_COL + 1, j) = col.y, SLOT_F(PF_COL + 2, j) = col.z;

@@ -22,6 +22,7 @@
 #include "../../include/rtiow_gpu.h"
 #include "../../include/rtiow_gpu_debug.h"
 #include "../../include/rtiow_gpu_query.h"
+#include "../../include/rtiow_gpu_rays.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -248,6 +249,9 @@ struct rtg_scene {
   // lean kernel whenever the program is lean and fits LDS, 1 = that kernel from QUERY_LDS_MIN_RAYS rays upward (rtg_query.inc)
   int query_lds = 1;
   int query_refill = 16;  // ... and the finished lanes of a wave at which the lean kernel runs its refill arm (rt_query.h; measurement switch)
+  // Scene option ray_pool (include/rtiow_gpu_rays.h): which kernel renders ray frames -- 1 = lean programs on the RAYS instantiations
+  // of the lean pool kernel, 0 = always the general kernel (rtg_rays.inc).  The same bits either way.
+  int ray_pool = 1;
   LaunchCtx ctx[RTG_MAX_FRAMES];           // frames in flight
   int n_ctx = 1, next_ctx = 0;
   LaunchCtx* cx = &ctx[0];                 // the context of the call being made (ctx_acquire)
@@ -960,6 +964,10 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
     s->query_lds = value;
   }
   else if (k == "query_refill") s->query_refill = std::min(64, std::max(1, value));
+  else if (k == "ray_pool") {                                   // ray frames: 1 lean programs on the lean pool kernel (default), 0 always the general kernel
+    if (value < 0 || value > 1) return fail(RTG_ERR_INVALID, "ray_pool: 0 or 1");
+    s->ray_pool = value;
+  }
   else if (k == "small_frames") s->small_frames = value;        // 0: one geometry for every frame size (measurement switch)
   else if (k == "verbose") s->verbose = value;                  // print launch geometry / schedule statistics to stderr
   else if (k == "window") s->window = value;                    // full-feature kernel: records staged in LDS, -1 = automatic
@@ -1217,3 +1225,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 }  // extern "C"
 
 #include "rtg_query.inc"
+
+#include "rtg_rays.inc"

@@ -304,9 +304,13 @@ static hipError_t camera_plan(rtg_scene* s, LeanImages& im, bool tree, const Dev
 // call's samples, not the frame's.  A counts call (sl.counts) runs over its list of active pixels: `pix_work` is the list's
 // length, and the kernel the list variant (LIST; the 4-wide walk of option bvh4 is not instantiated for it: such a call takes
 // the binary walk and reports its counters).
+// `d_rays` (ray frames, rtg_rays.inc; nullptr: a camera frame): the launch has no camera -- `cam` is not read, the camera plan
+// is skipped (the scene's own pruned image is staged: a plan changes cost, never bits) and the kernel is the RAYS instantiation,
+// which exists for production launches of the binary walk only.  Everything else is a production launch's.
 template <bool COUNT>
 static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out,
-                              hipStream_t stream, const SampleSlice& sl) {
+                              hipStream_t stream, const SampleSlice& sl, const float* d_rays = nullptr, uint32_t ray_mode = 0u) {
+  if (d_rays && (COUNT || sl.counts)) return hipErrorNotSupported;
   const uint64_t pix_work = sl.counts ? sl.list_work : rank_pix_work(d);
   if (pix_work == 0) return hipSuccess;  // this rank owns no tile
   if (pix_work > 0xfffffffeull) return hipErrorInvalidValue;
@@ -340,7 +344,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   const int bt = geo.bt;
   const uint32_t waves = (uint32_t)bt / 64;
   const size_t lds_limit = 160 * 1024;
-  const bool wide = s->bvh4 && s->wide_bytes != 0 && !sl.counts;
+  const bool wide = s->bvh4 && s->wide_bytes != 0 && !sl.counts && !d_rays;
   // production launches stage the image without box-chain followers (rt_pool.h box_chain_followers) and without the interior
   // boxes of the pruning plan (rt_box_plan.h); counting launches keep the full image, so that their counters and traces report
   // every test of the reference's walk (option box_prune = 2: they stage the pruned image too, and report the production walk's)
@@ -372,7 +376,7 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   // pass of the call, whose dynamic LDS was sized below from the image of its first pass and which lays LDS out from the image
   // size it is given: only when the camera's image is no larger than that one; else the call keeps its table, and the next call
   // is sized for the camera's.
-  const bool camera_ok = prune && pool_lds_bytes(dev.lds_image_bytes, s->n_mat, waves, true, false) <= lds_limit;
+  const bool camera_ok = prune && !d_rays && pool_lds_bytes(dev.lds_image_bytes, s->n_mat, waves, true, false) <= lds_limit;
   const CameraPlan* cplan = nullptr;
   uint32_t sized_for = 0;  // the image the launch was sized for, 0 = not sized yet
   auto kernel_for = [&](uint32_t bytes) {  // bit 0: the program is staged, bit 1: the hot slot fields live in LDS
@@ -410,6 +414,12 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
   } else if (wide) kernel = ray_lds ? render_lean_pool<true, COUNT, true, true> : render_lean_pool<true, COUNT, false, true>;
   else if (ray_lds) kernel = use_lds ? render_lean_pool<true, COUNT, true> : render_lean_pool<false, COUNT, true>;
   else kernel = use_lds ? render_lean_pool<true, COUNT, false> : render_lean_pool<false, COUNT, false>;
+  if constexpr (!COUNT) {
+    if (d_rays) {
+      if (ray_lds) kernel = use_lds ? render_lean_pool<true, false, true, false, false, true> : render_lean_pool<false, false, true, false, false, true>;
+      else kernel = use_lds ? render_lean_pool<true, false, false, false, false, true> : render_lean_pool<false, false, false, false, false, true>;
+    }
+  }
   if (s->verbose && (chains || prune) && use_lds)
     fprintf(stderr, "[rtg] pool: %s program (%u region(s) rebuilt in %.2f ms), box chains: %u follower record(s)%s, box pruning: %u interior record(s)%s (%s plan %.2f ms): LDS image %u B, %u records of %u; without followers %u B, full image %u B\n",
             tree ? "rebuilt" : "reference", s->n_regions, s->tree_ms, im.n_followers, chains || (prune && s->box_chains) ? " dropped" : " kept", cplan ? cplan->n_pruned : im.n_pruned, prune ? " dropped" : " kept",
@@ -435,7 +445,9 @@ static hipError_t launch_pool(rtg_scene* s, const DevCamera& cam, const DevParam
     hipError_t eg = s->cx->slots.grow((size_t)grid * waves * POOL * POOL_FIELDS * sizeof(uint32_t));
     if (eg != hipSuccess) return eg;
     if (s0 != sl.begin && (eg = camera_image()) != hipSuccess) return eg;  // (a later pass: the plan its first pass probed for)
-    launch_pass_setup(s, LaunchConsts{cam, dp, cm, make_pixmap(dp)}, queue, stream);
+    LaunchConsts c{cam, dp, cm, make_pixmap(dp)};
+    c.rays = d_rays, c.ray_mode = ray_mode;
+    launch_pass_setup(s, c, queue, stream);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(bt), lds, stream, dev, (const LaunchConsts*)s->cx->d_consts, d_out, total_work, queue,
                        s->cx->d_counters, s->pool_tune, s->cx->slots.as<uint32_t>());
     return hipSuccess;

@@ -9,6 +9,9 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_float, c_int, c_void};
 
+/// Ray frames (`include/rtiow_gpu_rays.h`): path-trace the caller's rays.
+pub mod rays;
+
 pub const RTG_OK: c_int = 0;
 pub const RTG_ERR_INVALID: c_int = -1;
 pub const RTG_ERR_EMPTY_BVH: c_int = -2; // bvh.rs:60
