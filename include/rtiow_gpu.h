@@ -560,7 +560,8 @@ int rtg_debug_samples(rtg_scene* s, const rtg_camera* camera, const rtg_params* 
                       const uint32_t* xs, const uint32_t* ys, const uint32_t* samples,
                       float* out_rgb, uint32_t* out_info);
 /* Evaluate the shared libm restatements on the GPU: op 0 = rt_logf, 1 = rt_pow5f, 2 = rt_sinf,
- * 3 = sqrtf, 4 = 1/x, 5 = x/y with y = in2[i] (in2 may be NULL for unary ops). */
+ * 3 = sqrtf, 4 = 1/x, 5 = x/y with y = in2[i], 6 = rt_atan2f(in[i], in2[i]) (rtiow_gpu_image.h); in2 may be NULL for unary
+ * ops. */
 int rtg_debug_math(int device, int op, size_t n, const float* in, const float* in2, float* out);
 
 /* Host-only: flatten `world` and copy the flat program out (8 words per instruction: the lo packet

@@ -682,6 +682,29 @@ QUERY_SYMBOLS = ["query_closest", "query_closest_device", "query_occluded", "que
 # include/rtiow_gpu_rays.h: ray frames (not part of ABI_SYMBOLS either)
 RAY_FRAME_SYMBOLS = ["par_cast_rays", "par_cast_rays_device"]
 RAYS_PER_PIXEL, RAYS_PER_SAMPLE = 0, 1
+# include/rtiow_gpu_image.h: image textures and their probes (not part of ABI_SYMBOLS either: the oracle has no image kind)
+IMAGE_SYMBOLS = ["texture_image", "debug_texture_host", "debug_texture", "debug_atan2f_host"]
+
+
+class ImageParams(C.Structure):
+    """rtg_image_params (include/rtiow_gpu_image.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("mapping", C.c_uint32), ("filter", C.c_uint32), ("wrap_u", C.c_uint32),
+                ("wrap_v", C.c_uint32), ("reserved_in", C.c_uint32), ("m", C.c_float * 8)]
+
+    @classmethod
+    def new(cls, params):
+        """From the dict image.params() makes (or any mapping with its keys)."""
+        p = cls()
+        p.struct_size = C.sizeof(cls)
+        p.mapping, p.filter = int(params.get("mapping", 0)), int(params.get("filter", 0))
+        p.wrap_u, p.wrap_v = int(params.get("wrap_u", 0)), int(params.get("wrap_v", 0))
+        p.reserved_in = int(params.get("reserved_in", 0))
+        m = np.zeros(8, dtype=np.float32)
+        given = np.asarray(params.get("m", ()), dtype=np.float32).reshape(-1)
+        m[:min(8, given.size)] = given[:8]
+        for i in range(8):
+            p.m[i] = float(m[i])
+        return p
 
 
 def ray_index(nx, ny, sample, row, x, per_sample):
@@ -764,6 +787,11 @@ class Backend:
         # include/rtiow_gpu_rays.h (RAY_FRAME_SYMBOLS): the same convention
         f("par_cast_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Params), C.c_void_p, st])
         f("par_cast_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Params), C.c_void_p, C.c_void_p, st])
+        # include/rtiow_gpu_image.h (IMAGE_SYMBOLS)
+        f("texture_image", C.c_uint32, [C.c_void_p, C.POINTER(ImageParams), C.c_uint32, C.c_uint32, c_f32p])
+        f("debug_texture_host", C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, c_f32p, c_f32p])
+        f("debug_texture", C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, c_f32p, c_f32p])
+        f("debug_atan2f_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, c_f32p])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -884,6 +912,14 @@ class Backend:
         return out
 
 
+    def atan2f_host(self, y, x):
+        """rtg_debug_atan2f_host: rt_atan2f(y, x) on the host (image.atan2f is its definition)."""
+        y, x = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in np.broadcast_arrays(y, x))
+        out = np.empty_like(y)
+        self.check(self._debug_atan2f_host(y.size, y.ctypes.data_as(c_f32p), x.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
+
+
 class Builder:
     """Scene under construction.  One method per reference constructor."""
 
@@ -914,6 +950,22 @@ class Builder:
 
     def perlin(self, scale):
         return self.be.check_id(self.be._texture_perlin(self.h, scale))
+
+    def image(self, img, params):
+        """rtg_texture_image (include/rtiow_gpu_image.h): img float32 [h, w, 3], row 0 at the top; params from image.params /
+        image.planar / image.spherical (or an ImageParams).  Returns an ordinary texture id."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("an image is [h, w, 3]")
+        p = params if isinstance(params, ImageParams) else ImageParams.new(params)
+        return self.be.check_id(self.be._texture_image(self.h, C.byref(p), img.shape[1], img.shape[0], img.ctypes.data_as(c_f32p)))
+
+    def texture_host(self, texture, p):
+        """rtg_debug_texture_host: the texture's value at the points p [n, 3] on the host (image and constant textures)."""
+        p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+        out = np.empty_like(p)
+        self.be.check(self.be._debug_texture_host(self.h, texture, len(p), p.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
 
     def set_perlin_tables(self, vecs, perm_x, perm_y, perm_z):
         vecs = np.ascontiguousarray(vecs, dtype=np.float32).reshape(768)
@@ -1493,6 +1545,14 @@ class Scene:
         self.be.check(self.be._debug_hit_top(self.h, n, rays.ctypes.data_as(c_f32p), seed, t_near,
                                              out.ctypes.data_as(c_f32p), mat.ctypes.data_as(c_u32p)))
         return out, mat
+
+    def debug_texture(self, texture, p):
+        """rtg_debug_texture (include/rtiow_gpu_image.h): the texture's value at the points p [n, 3] on the scene's device,
+        through the function every kernel evaluates a texture with.  Every texture kind."""
+        p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+        out = np.empty_like(p)
+        self.be.check(self.be._debug_texture(self.h, texture, len(p), p.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
 
     # ---- ray queries (include/rtiow_gpu_query.h) ---------------------------------------------------------------------
     def _query(self, what, width, rays, seed, t_min, first_index, stream, stats, outputs):

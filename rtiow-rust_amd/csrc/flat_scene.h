@@ -100,7 +100,7 @@ constexpr uint32_t F_GENERAL_BOUNDARY = 1u << 14;  // MEDIUM: the boundary is an
 constexpr uint32_t F_GATHER = 1u << 15;     // any non-BOX record: head of a run of >= 4 list-level records without a Bvh (scheduling
                                             // hint: every ray passes here and then executes the same records in the same order)
 constexpr uint32_t F_MATKIND_SHIFT = 16;    // SPHERE/RECT/MEDIUM: bits 16-18 = MatKind of the record's material (copy, for schedulers)
-constexpr uint32_t F_TEXTURED = 1u << 19;   // SPHERE/RECT/PRISM/MEDIUM: the material reads a checker / Perlin texture (copy, for schedulers)
+constexpr uint32_t F_TEXTURED = 1u << 19;   // SPHERE/RECT/PRISM/MEDIUM: the material reads a checker / Perlin / image texture (copy, for schedulers)
 constexpr uint32_t F_MOVE = 1u << 20;      // SPHERE: a LinearMove sits between the (optional, F_TRANSLATE) Translate and the sphere: after the
                                             // translate, origin -= time * motion (object.rs:505-508; nothing on the way out); motion = lo.xyz of the
                                             // OP_EXT record behind this one, which the SPHERE steps over (pc += 2)
@@ -126,8 +126,16 @@ constexpr int MAX_SAVE_NESTING = 4;       // OP_SAVE .. OP_MERGE pairs inside on
 //   Metal: c = albedo, param = fuzz;  Dielectric: param = ref_idx
 //   DiffuseLight: c = emission when constant, param = brightness
 enum MatKind : uint32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_DIFFUSE_LIGHT = 3, MAT_ISOTROPIC = 4 };
-enum TexKind : uint32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_PERLIN = 2 };
+enum TexKind : uint32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_PERLIN = 2, TEX_IMAGE = 3 };
+constexpr uint32_t TEX_EXT = 4;  // host side only (HostTexture::kind): the slot of an image's continuation record; no handle names it
 // Texture record, 32 bytes: lo = (r, g, b, scale) hi = (t0, t1, -, kind)
+// TEX_IMAGE (include/rtiow_gpu_image.h; not in the reference, whose Texture is a closure): TWO records and a run of texels.
+//   record i     lo = (w, h, flags, first)   hi = (-, -, -, TEX_IMAGE)    flags: rt_image.h IMG_*; first = PACKET index into tex[]
+//   record i + 1 lo = (m0, m1, m2, m3)       hi = (m4, m5, m6, m7)        data only, as OP_EXT continues a SPHERE: the eight mapping
+//                                                                         floats.  It has no kind word and is never evaluated: the
+//                                                                         builder hands out i, and refuses i + 1 as a handle
+//   tex[first + j * w + i] = (r, g, b, -) of texel (i, j), row 0 at the top: the texels of every image stand BEHIND the records
+//   of all textures, in the same buffer (DevScene::tex, one upload), so texture ids keep indexing records: tex[2 * id].
 
 // Light table (scene option light_sampling, rt_light.h): one record per Rect of a SAMPLED DiffuseLight material, in world order.
 // A material is sampled when every primitive of the world's graph that uses it is a Rect at the world's list level, bare or

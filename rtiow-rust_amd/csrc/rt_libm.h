@@ -11,9 +11,15 @@
 // Without FMA contraction (glibc's __powf_sse2 / __sinf_sse2 on pre-Haswell CPUs) powf(x, 5) differs on 6 and sinf on 12
 // of the 2^32 inputs by one ulp; logf is identical either way.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define RT_LIBM_HD __host__ __device__
+#else
+#define RT_LIBM_HD
+#endif
 
+#ifdef __HIPCC__  // the glibc restatements are device code; rt_atan2f at the end of the file is written once for g++ and hipcc
 namespace rtg {
 __device__ __forceinline__ uint32_t gl_asuint(float f) { return __float_as_uint(f); }
 __device__ __forceinline__ float gl_asfloat(uint32_t u) { return __uint_as_float(u); }
@@ -189,4 +195,68 @@ GL_FN float rt_sinf(float y) {
 #undef GL_FN
 #undef GL_TAB
 #undef GL_FMA
+}  // namespace rtg
+#endif  // __HIPCC__
+
+// ---- rt_atan2f (include/rtiow_gpu_image.h: the spherical mapping of an image texture) ------------------------------------------
+// NOT a restatement of a platform libm: the reference has no atan2 (texture.rs knows no images), so this function is its own
+// definition, written once for g++ and hipcc, and rtiow-rust_amd/image.py atan2f() is the same arithmetic in numpy, bit for bit.
+// Float64 inside, every operation rounded on its own (no contraction, no libm call), ONE rounding to float32 at the end:
+//   |y| and |x| are exact in float64; an infinite one becomes 1 and its finite partner 0 (C's atan2f at the infinities);
+//   n = min, d = max of the two, so atan(n / d) lies in [0, pi/4]; above tan(pi/8) the identity atan(q) = pi/4 + atan((q - 1) / (q + 1))
+//   is applied BEFORE the divide, t = (n - d) / (n + d) -- difference and sum of two float32 within a factor 2.5 of each other
+//   are exact in float64 -- so there is one divide and |t| <= tan(pi/8) = 0.41422;
+//   atan(t) = t * sum_{k=0..21} (-1)^k t^2k / (2k + 1): the Taylor series itself, Horner in z = t * t; the first term left out,
+//   t^45 / 45, is below 2e-19, the rounding of 22 Horner steps a few 1e-16 -- against 6e-8, half a float32 ulp;
+//   then pi/2 - r where |y| > |x|, pi - r where x has its sign bit set, -r where y has.
+// So the result is the correctly rounded float32 of atan2 except where the float64 value lies within ~1e-15 (relative) of a
+// rounding boundary, and never more than 1 ulp from it (tests/test_image_texture_abi.py measures it against numpy's float64
+// arctan2).  (+-0, +-0), (+-0, x < 0) = +-pi, the infinities and NaN follow C's atan2f; a result below the float32 subnormals
+// rounds to +-0.
+namespace rtg {
+RT_LIBM_HD inline float rt_atan2f(float y, float x) {
+  if (x != x || y != y) return x + y;
+  const bool neg_x = __builtin_signbit(x), neg_y = __builtin_signbit(y);
+  double ax = __builtin_fabs((double)x), ay = __builtin_fabs((double)y);
+  const double inf = __builtin_inf();
+  if (ax == inf || ay == inf) {
+    const double bx = ax == inf ? 1.0 : 0.0, by = ay == inf ? 1.0 : 0.0;
+    ax = bx, ay = by;
+  }
+  const bool swap = ay > ax;
+  const double n = swap ? ax : ay, d = swap ? ay : ax;
+  const bool upper = n > 0.41421356237309503 * d;  // tan(pi/8)
+  const double num = upper ? n - d : n, den = upper ? n + d : d;
+  const double t = num == 0.0 ? 0.0 : num / den;  // (0, 0): atan2 is +-0 or +-pi, not NaN
+  const double z = t * t;
+  double s = 1.0 / 43.0;
+  // s_k = 1/(2k+1) - z * s_{k+1}: the alternating series, innermost term first
+  s = 1.0 / 41.0 - z * s;
+  s = 1.0 / 39.0 - z * s;
+  s = 1.0 / 37.0 - z * s;
+  s = 1.0 / 35.0 - z * s;
+  s = 1.0 / 33.0 - z * s;
+  s = 1.0 / 31.0 - z * s;
+  s = 1.0 / 29.0 - z * s;
+  s = 1.0 / 27.0 - z * s;
+  s = 1.0 / 25.0 - z * s;
+  s = 1.0 / 23.0 - z * s;
+  s = 1.0 / 21.0 - z * s;
+  s = 1.0 / 19.0 - z * s;
+  s = 1.0 / 17.0 - z * s;
+  s = 1.0 / 15.0 - z * s;
+  s = 1.0 / 13.0 - z * s;
+  s = 1.0 / 11.0 - z * s;
+  s = 1.0 / 9.0 - z * s;
+  s = 1.0 / 7.0 - z * s;
+  s = 1.0 / 5.0 - z * s;
+  s = 1.0 / 3.0 - z * s;
+  s = 1.0 - z * s;
+  double r = t * s;
+  if (upper) r = 0.78539816339744828 + r;   // pi/4
+  if (swap) r = 1.5707963267948966 - r;     // pi/2
+  if (neg_x) r = 3.1415926535897931 - r;    // pi
+  if (neg_y) r = -r;
+  return (float)r;
+}
 }  // namespace rtg

@@ -3,6 +3,7 @@
 #pragma once
 #include "flat_scene.h"
 #include "rt_device.h"
+#include "rt_image.h"
 #include "rt_sphere_hit.h"
 
 namespace rtg {
@@ -11,7 +12,7 @@ struct DevScene {
   const uint4* lo;           // instruction packets 0
   const uint4* hi;           // instruction packets 1
   const uint4* mat;          // 2 packets per material
-  const uint4* tex;          // 2 packets per texture
+  const uint4* tex;          // 2 packets per texture, then the texels of the image textures (flat_scene.h TEX_IMAGE)
   const float4* perlin_vecs; // 256 gradients (perlin.rs VECS)
   const uint8_t* perlin_perm;// PERM_X | PERM_Y | PERM_Z, 3 x 256
   const uint32_t* lds_off;   // lean programs: byte offset of every record inside the LDS image (rt_pool.h); launches of the
@@ -672,6 +673,18 @@ RT_DEV float perlin_turb(const DevScene& sc, V3 p, int depth) {  // perlin.rs:66
   return __builtin_fabsf(accum);
 }
 
+// An image texture (flat_scene.h TEX_IMAGE; include/rtiow_gpu_image.h): record idx = (w, h, flags, first texel packet), the
+// mapping floats in the data record behind it.  Out of line like Perlin noise: its float64 atan2 and four texel fetches stay out
+// of texture_eval's own register allocation; it takes texture_eval's arguments as they stand (and reads the record again), so
+// the call keeps nothing else alive: the record as a further argument would widen texture_eval's own register footprint, and
+// with it the spill area of every pool kernel that calls it.
+__device__ __attribute__((noinline)) V3 image_eval(const DevScene& sc, uint32_t idx, V3 p) {
+  const uint4 lo = sc.tex[2 * idx], m0 = sc.tex[2 * idx + 2], m1 = sc.tex[2 * idx + 3];
+  const float m[8] = {u2f(m0.x), u2f(m0.y), u2f(m0.z), u2f(m0.w), u2f(m1.x), u2f(m1.y), u2f(m1.z), u2f(m1.w)};
+  const ImgRgb c = image_sample(reinterpret_cast<const ImgTexel*>(sc.tex + lo.w), lo.x, lo.y, lo.z, m, p.x, p.y, p.z);
+  return mk(c.r, c.g, c.b);
+}
+
 // out of line on purpose: Perlin turbulence (7 octaves x 8 gradient fetches) is a rare path and would
 // otherwise dominate the register allocation of every kernel that can reach it
 __device__ __attribute__((noinline)) V3 texture_eval(const DevScene& sc, uint32_t idx, V3 p) {
@@ -680,6 +693,7 @@ __device__ __attribute__((noinline)) V3 texture_eval(const DevScene& sc, uint32_
     uint32_t kind = hi.w;
     if (kind == TEX_CONSTANT) return mk(u2f(lo.x), u2f(lo.y), u2f(lo.z));           // texture.rs:8
     if (kind == TEX_PERLIN) return splat(perlin_turb(sc, smul(u2f(lo.w), p), 7));   // texture.rs:23
+    if (kind == TEX_IMAGE) return image_eval(sc, idx, p);
     V3 q = smul(10.f, p);                                                           // texture.rs:12-21
     float s = (rt_sinf(q.x) * rt_sinf(q.y)) * rt_sinf(q.z);
     idx = s < 0.f ? hi.y : hi.x;

@@ -23,6 +23,7 @@
 #include "../../include/rtiow_gpu_debug.h"
 #include "../../include/rtiow_gpu_query.h"
 #include "../../include/rtiow_gpu_rays.h"
+#include "../../include/rtiow_gpu_image.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -166,6 +167,7 @@ struct rtg_scene {
   DevScene dev{};
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
+  std::vector<uint8_t> tex_kind;  // kind of every texture record (flat_scene.h TexKind, TEX_EXT): which ids rtg_debug_texture evaluates
   uint64_t bytes = 0;
   std::vector<void*> owned;    // what `upload` allocated: freed when the scene is destroyed
   const uint32_t* d_parent = nullptr;  // the wrapper around every program record (rt_pool_full.h rebuild_hit)
@@ -465,6 +467,7 @@ rtg_id rtg_texture_constant(rtg_builder* b, const float rgb[3]) {
 rtg_id rtg_texture_checker(rtg_builder* b, rtg_id t0, rtg_id t1) {
   if (!b) return bad("null argument");
   if (t0 >= b->sb.textures.size() || t1 >= b->sb.textures.size()) return bad("checker: bad texture handle");
+  if (b->sb.textures[t0].kind == TEX_EXT || b->sb.textures[t1].kind == TEX_EXT) return bad("checker: bad texture handle");
   HostTexture t;
   t.kind = TEX_CHECKER;
   t.t0 = t0, t.t1 = t1;
@@ -498,7 +501,7 @@ static rtg_id push_material(rtg_builder* b, uint32_t kind, rtg_id tex, const flo
   HostMaterial m;
   m.kind = kind;
   if (tex != RTG_INVALID_ID) {
-    if (tex >= b->sb.textures.size()) return bad("material: bad texture handle");
+    if (tex >= b->sb.textures.size() || b->sb.textures[tex].kind == TEX_EXT) return bad("material: bad texture handle");
     m.tex = tex;
   }
   if (albedo) m.albedo[0] = albedo[0], m.albedo[1] = albedo[1], m.albedo[2] = albedo[2];
@@ -778,7 +781,8 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
   s->features = fs.features;
   s->n_prog = (uint32_t)fs.lo.size();
   s->n_mat = (uint32_t)fs.mat.size() / 2;
-  s->n_tex = (uint32_t)fs.tex.size() / 2;
+  s->n_tex = fs.n_tex;  // records, not the texels behind them
+  for (const HostTexture& t : b->sb.textures) s->tex_kind.push_back((uint8_t)t.kind);
   int rc;
   if ((rc = upload(s, &s->dev.lo, fs.lo.data(), fs.lo.size() * 16)) ||
       (rc = upload(s, &s->dev.hi, fs.hi.data(), fs.hi.size() * 16)) ||
@@ -1227,3 +1231,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 #include "rtg_query.inc"
 
 #include "rtg_rays.inc"
+
+#include "rtg_image.inc"

@@ -226,6 +226,7 @@ __global__ void debug_math_kernel(int op, size_t n, const float* in, const float
     case 2: r = rt_sinf(x); break;
     case 3: r = __builtin_sqrtf(x); break;
     case 4: r = 1.f / x; break;
+    case 6: r = rt_atan2f(x, in2[i]); break;
     default: r = x / in2[i]; break;
   }
   out[i] = r;

@@ -273,7 +273,7 @@ int rtg_debug_camera_plan(rtg_builder* b, const rtg_id* world, size_t n, const u
 }
 
 int rtg_debug_math(int device, int op, size_t n, const float* in, const float* in2, float* out) {
-  if (!in || !out || op < 0 || op > 5 || (op == 5 && !in2)) return fail(RTG_ERR_INVALID, "bad argument");
+  if (!in || !out || op < 0 || op > 6 || (op >= 5 && !in2)) return fail(RTG_ERR_INVALID, "bad argument");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(RTG_ERR_DEVICE, "no HIP device");
   HIP_TRY(hipSetDevice(device));

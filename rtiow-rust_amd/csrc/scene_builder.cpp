@@ -707,6 +707,41 @@ void SceneBuilder::finish_materials(FlatScene* out) const {
       else if (c[i] > 1.f) out->features |= FEAT_BRIGHT_ALBEDO;
     }
   };
+  // An image (flat_scene.h TEX_IMAGE): the thresholds of range_of_constant on the minimum and maximum of its texels, any
+  // non-finite texel counting as outside.  The nearest filter returns texels.  The bilinear filter returns a + t * (b - a) with t
+  // in [0, 1], twice (rt_image.h).  Rounding is monotone, so fl(t * fl(b - a)) lies between 0 and fl(b - a) and the sum between
+  // a and a + fl(b - a); that misses b by the rounding error of b - a alone, at most half an ulp of the larger of two texels
+  // of one sign, and is rounded once more: the value stays within one ulp of [min, max].  The pool kernels' bounds (rt_pool.h
+  // PoolField: a strength that stays finite and non-negative) tolerate that because AT the thresholds nothing is lost at all.
+  // Below: for a, b >= 0, fl(b - a) >= -a (b - a >= -a, and -a is a float), so the addend lies in [-a, 0] and the sum is >= 0.
+  // Above, for a bound M that is a power of two (1 and 4): fl(b - a) <= fl(M - a), off M - a by at most half an ulp below M,
+  // M * 2^-25, so the sum is <= M * (1 + 2^-25), under the midpoint of M and its successor, and rounds to <= M.  So texels in
+  // [0, 1] or [0, 4] give values in [0, 1] or [0, 4], the ranges the constants' thresholds stand for.
+  // One scan per image and flattening, however many materials and checkers lead to it: its class is kept per texture id.
+  constexpr uint32_t kNotScanned = 0xffffffffu;
+  std::vector<uint32_t> image_class(textures.size(), kNotScanned);
+  auto range_of_image = [&](uint32_t id) {
+    if (image_class[id] != kNotScanned) {
+      out->features |= image_class[id];
+      return;
+    }
+    const HostTexture& t = textures[id];
+    const uint32_t before = out->features;
+    out->features = 0;
+    float lo[3] = {t.texels[0], t.texels[1], t.texels[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+    bool finite = true;
+    for (size_t k = 0; k < t.texels.size(); k += 4)
+      for (int c = 0; c < 3; c++) {
+        const float v = t.texels[k + c];
+        if (!std::isfinite(v)) finite = false;
+        if (v < lo[c]) lo[c] = v;
+        if (v > hi[c]) hi[c] = v;
+      }
+    if (!finite) out->features |= FEAT_WIDE_ALBEDO;
+    range_of_constant(lo), range_of_constant(hi);
+    image_class[id] = out->features;
+    out->features |= before;
+  };
   std::vector<uint32_t> todo;
   auto range_of_texture = [&](uint32_t root) {
     todo.assign(1, root);
@@ -716,6 +751,7 @@ void SceneBuilder::finish_materials(FlatScene* out) const {
       const HostTexture& t = textures[id];
       if (t.kind == TEX_CONSTANT) range_of_constant(t.rgb);
       else if (t.kind == TEX_PERLIN) out->features |= perlin_bad ? FEAT_WIDE_ALBEDO : FEAT_BRIGHT_ALBEDO;
+      else if (t.kind == TEX_IMAGE) range_of_image(id);
       else todo.push_back(t.t0), todo.push_back(t.t1);  // checker: children were created earlier (ids < id): no cycles
     }
   };
@@ -736,10 +772,32 @@ void SceneBuilder::finish_materials(FlatScene* out) const {
     out->mat.push_back(Packet{{fbits(c[0]), fbits(c[1]), fbits(c[2]), fbits(m.param)}});
     out->mat.push_back(Packet{{tex, 0, 0, m.kind | (texkind << 8)}});
   }
+  // texture records, then the texels of the images behind them (flat_scene.h TEX_IMAGE): ids keep indexing records
+  // (an image's record names its first texel by a 32-bit packet index: a scene whose records and texels together do not fit one
+  // is refused -- the limit of 2^24 texels holds per image, not for their sum)
+  size_t first = 2 * textures.size(), packets = first;
+  for (const HostTexture& t : textures) packets += t.texels.size() / 4;
+  if (packets > 0xffffffffull) throw BuildError{-4, "scene: the texture records and the texels of all images exceed 2^32 packets"};
   for (const HostTexture& t : textures) {
-    out->tex.push_back(Packet{{fbits(t.rgb[0]), fbits(t.rgb[1]), fbits(t.rgb[2]), fbits(t.scale)}});
-    out->tex.push_back(Packet{{t.t0, t.t1, 0, t.kind}});
+    if (t.kind == TEX_IMAGE) {
+      out->tex.push_back(Packet{{t.w, t.h, t.flags, (uint32_t)first}});
+      out->tex.push_back(Packet{{0, 0, 0, TEX_IMAGE}});
+      first += t.texels.size() / 4;
+    } else if (t.kind == TEX_EXT) {
+      out->tex.push_back(Packet{{fbits(t.m[0]), fbits(t.m[1]), fbits(t.m[2]), fbits(t.m[3])}});
+      out->tex.push_back(Packet{{fbits(t.m[4]), fbits(t.m[5]), fbits(t.m[6]), fbits(t.m[7])}});
+    } else {
+      out->tex.push_back(Packet{{fbits(t.rgb[0]), fbits(t.rgb[1]), fbits(t.rgb[2]), fbits(t.scale)}});
+      out->tex.push_back(Packet{{t.t0, t.t1, 0, t.kind}});
+    }
   }
+  out->n_tex = (uint32_t)textures.size();
+  for (const HostTexture& t : textures)
+    if (t.kind == TEX_IMAGE) {
+      const size_t at = out->tex.size();
+      out->tex.resize(at + t.texels.size() / 4);
+      std::memcpy(out->tex.data() + at, t.texels.data(), t.texels.size() * sizeof(float));
+    }
   out->perlin_vecs = perlin_vecs;
   out->perlin_perm = perlin_perm;
   out->has_perlin = has_perlin;

@@ -45,11 +45,17 @@ struct HostTexture {
   float rgb[3] = {0, 0, 0};
   float scale = 0.f;
   uint32_t t0 = 0, t1 = 0;
+  // TEX_IMAGE (flat_scene.h): size, rt_image.h flag word and the texels as float4 packets; the mapping floats live in the
+  // TEX_EXT slot behind it (m)
+  uint32_t w = 0, h = 0, flags = 0;
+  std::vector<float> texels;
+  float m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 struct FlatScene {
   std::vector<Packet> lo, hi;    // program
-  std::vector<Packet> mat, tex;  // 2 packets per record
+  std::vector<Packet> mat, tex;  // 2 packets per record; tex: then the texels of its images, one packet each (flat_scene.h TEX_IMAGE)
+  uint32_t n_tex = 0;            // texture records in tex
   std::array<float, 1024> perlin_vecs{};  // 256 x float4
   std::array<uint8_t, 768> perlin_perm{};
   uint32_t features = 0;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/rtiow_gpu.h"
+#include "../../include/rtiow_gpu_image.h"
 
 namespace rtiow {
 
@@ -71,6 +72,15 @@ inline Texture checker(Texture t0, Texture t1) {
 }
 inline Texture perlin(float scale) {
   return Texture{[scale](rtg_builder* b) { return check_id(rtg_texture_perlin(b, scale)); }};
+}
+// Not in the reference (include/rtiow_gpu_image.h): w x h texels of three floats, row-major, row 0 at the top, looked up through
+// `params` (mapping, filter, wraps and the eight mapping floats; struct_size is filled in here).  The texels are shared, not
+// copied, until the scene is built.
+inline Texture image(rtg_image_params params, uint32_t w, uint32_t h, std::vector<float> rgb) {
+  if (rgb.size() != (size_t)w * h * 3) throw Error(RTG_ERR_INVALID, "texture::image: rgb must hold w * h * 3 floats");
+  params.struct_size = sizeof(rtg_image_params);
+  auto texels = std::make_shared<const std::vector<float>>(std::move(rgb));
+  return Texture{[params, w, h, texels](rtg_builder* b) { return check_id(rtg_texture_image(b, &params, w, h, texels->data())); }};
 }
 }  // namespace texture
 

@@ -9,6 +9,8 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_float, c_int, c_void};
 
+/// Image textures (`include/rtiow_gpu_image.h`): a sampled image as a fourth texture kind.
+pub mod image;
 /// Ray frames (`include/rtiow_gpu_rays.h`): path-trace the caller's rays.
 pub mod rays;
 
