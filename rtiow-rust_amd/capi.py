@@ -684,6 +684,8 @@ RAY_FRAME_SYMBOLS = ["par_cast_rays", "par_cast_rays_device"]
 RAYS_PER_PIXEL, RAYS_PER_SAMPLE = 0, 1
 # include/rtiow_gpu_image.h: image textures and their probes (not part of ABI_SYMBOLS either: the oracle has no image kind)
 IMAGE_SYMBOLS = ["texture_image", "debug_texture_host", "debug_texture", "debug_atan2f_host"]
+# include/rtiow_gpu_mesh.h: triangles and meshes (not part of ABI_SYMBOLS either: the oracle has no triangle)
+MESH_SYMBOLS = ["object_triangle", "object_mesh", "debug_triangle_host"]
 
 
 class ImageParams(C.Structure):
@@ -792,6 +794,10 @@ class Backend:
         f("debug_texture_host", C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, c_f32p, c_f32p])
         f("debug_texture", C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, c_f32p, c_f32p])
         f("debug_atan2f_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, c_f32p])
+        # include/rtiow_gpu_mesh.h (MESH_SYMBOLS)
+        f("object_triangle", C.c_uint32, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_uint32])
+        f("object_mesh", C.c_uint32, [C.c_void_p, c_f32p, C.c_size_t, c_u32p, C.c_size_t, C.c_uint32, C.c_uint32])
+        f("debug_triangle_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, C.c_float, c_f32p])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -917,6 +923,19 @@ class Backend:
         y, x = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in np.broadcast_arrays(y, x))
         out = np.empty_like(y)
         self.check(self._debug_atan2f_host(y.size, y.ctypes.data_as(c_f32p), x.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
+
+    def triangle_host(self, tri9, rays8, t_min=0.001):
+        """rtg_debug_triangle_host: n (triangle, ray) pairs -- tri9 [n, 9] = v0, v1, v2; rays8 [n, 8] = o, d, time, t_max --
+        through the function the kernels call, on the host.  [n, 8] = hit, t, p, n; zeros on a miss (triangle.hit is its
+        definition)."""
+        tri9 = np.ascontiguousarray(tri9, dtype=np.float32).reshape(-1, 9)
+        rays8 = np.ascontiguousarray(rays8, dtype=np.float32).reshape(-1, 8)
+        if len(tri9) != len(rays8):
+            raise ValueError("triangle_host: one ray per triangle")
+        out = np.empty((len(tri9), 8), dtype=np.float32)
+        self.check(self._debug_triangle_host(len(tri9), tri9.ctypes.data_as(c_f32p), rays8.ctypes.data_as(c_f32p), float(t_min),
+                                             out.ctypes.data_as(c_f32p)))
         return out
 
 
@@ -1110,6 +1129,18 @@ class Builder:
         """Not in the reference: SAH-built Bvh; same results up to exact-t ties, fewer box tests."""
         arr = (C.c_uint32 * max(1, len(objs)))(*objs)
         return self.be.check_id(self.be._object_bvh_sah(self.h, arr, len(objs), exposure[0], exposure[1]))
+
+    def triangle(self, v0, v1, v2, material):
+        """rtg_object_triangle (include/rtiow_gpu_mesh.h): an ordinary object id; counter-clockwise is the front face."""
+        return self.be.check_id(self.be._object_triangle(self.h, _f3(v0), _f3(v1), _f3(v2), material))
+
+    def mesh(self, vertices, indices, material, sah=False):
+        """rtg_object_mesh: vertices [n, 3] float32, indices [m, 3] uint32 (triangle.icosphere / box / grid / load_obj make
+        them) -> the m triangle objects and one Bvh object over them (sah: the SAH builder); returns the Bvh's id."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        return self.be.check_id(self.be._object_mesh(self.h, v.ctypes.data_as(c_f32p), len(v), ix.ctypes.data_as(c_u32p), len(ix),
+                                                     material, int(sah)))
 
     def scene(self, world, device=0):
         """Flatten `world` (the `[Box<dyn Object>]` of lib.rs:33) once into device memory."""

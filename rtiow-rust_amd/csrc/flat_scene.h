@@ -59,6 +59,18 @@ enum Op : uint32_t {
   // Only in the SECOND program of a scene, the one the pool-2 kernel walks (rt_pool2.h; P2Table below):
   OP_LIST = 13,   // hi = (first item, item count, -, op): commits the list-level items [first, first + count) of the P2Table, in
                   //      order, from what was evaluated for them when the ray was created.  A W item is the last of its record.
+  // Only in programs with FEAT_TRI (include/rtiow_gpu_mesh.h; not in the reference, whose primitives are Sphere and Rect):
+  OP_TRI = 14,    // lo = (v0.x, v0.y, v0.z, e1.x)       hi = (e1.y, e1.z, material, op|flags), and ONE data record behind it, as a moving
+                  //      sphere has:            OP_EXT  lo = (e2.x, e2.y, e2.z, N.x)        hi = (N.y, N.z, -, OP_EXT)
+                  //      e1 = v1 - v0, e2 = v2 - v0, N the unit normal of the counter-clockwise side (rt_triangle.h tri_record); the TRI
+                  //      steps over its data record (pc += 2).  Flags: F_FLIP, F_MATKIND, F_TEXTURED, F_GATHER, as for RECT.
+                  //      A triangle is NOT a "plain primitive" in the sense of OP_SEG and the second program: it is never part of
+                  //      a hoisted segment, and a world that holds one has no second program (flatten_pool2 returns false).
+                  //      Who executes it: the one-lane family (rt_trace.h, rt_light.h) and the TRI instantiations of the full-feature
+                  //      pool kernel and the lock-step kernel (rt_full_ops.inc exec_op, rt_pool_full.h rebuild_hit; RT_SLOW_OP / RT_BUSY_OP
+                  //      widen their record classes, whose range ends at OP_SEG).  The lean pool, pool-2 and lean query kernels and
+                  //      every instantiation without the bit hold no TRI case and are never launched on a program with FEAT_TRI
+                  //      (rtg_launch.inc launch_slice / launch_full_pool, rtg_query.inc, rtg_rays.inc).
 };
 
 // ---- the list level, hoisted (pool-2 kernel, rt_pool2.h) -------------------------------------------------------------------
@@ -161,6 +173,8 @@ constexpr uint32_t FEAT_DEEP = 128u;   // a graph shape only the general walk ha
 constexpr uint32_t FEAT_DEEP_FEW_WRAPPERS = 256u;  // no more than DEEP_FEW_WRAPPERS wrappers are ever open at once: ray stacks of 8 instead of 32
 constexpr uint32_t FEAT_DEEP_ONE_LEVEL = 512u;     // no medium inside a medium's boundary: the walk recurses one level (its boundary queries), not three
 constexpr int DEEP_FEW_WRAPPERS = 8;
+constexpr uint32_t FEAT_TRI = 1024u;   // TRI present (include/rtiow_gpu_mesh.h): never a lean program, no hoisted segment, no second program; walked by the
+                                       // FEAT_TRI / TRI instantiations of the one-lane family, the full-feature pool kernel and the lock-step kernel
 constexpr uint32_t FEAT_BRIGHT_ALBEDO = 64u; // an albedo component may exceed 1 (a constant in (1, 4], or Perlin turbulence, <= 3.47): the pool
                                             // kernels then need max_bounces <= 63 for the strength to stay finite
 constexpr uint32_t FEAT_WIDE_ALBEDO = 32u;  // an albedo component outside [0, 4]: path strength may overflow or change sign, so the pool

@@ -128,6 +128,24 @@
         }
       }
       pc += RSZ;
+    } else if (TRI && op == OP_TRI) {  // a triangle (flat_scene.h OP_TRI; rt_triangle.h): the TRI record and its data record
+      if (COUNT) cnt.prim++;
+      const uint4 x_lo = RT_FETCH_LO(pc + RSZ);
+      float t;
+      if (tri_rec_hit_t(cur_lo, cur_hi, x_lo, o, d, GENB ? t_lo : t_near, best, t)) {
+        if (GENB && bmode) {
+          best = t;  // boundary query: only the closest t matters
+        } else {
+#if RT_DEFER_HIT
+          hmat = pc | ((cur_hi.w >> 16) & 8u);
+          best = t, nhits++;
+#else
+          hp = vadd(o, smul(t, d)), hn = tri_rec_normal(cur_hi, x_lo, RT_FETCH_HI(pc + RSZ)), hmat = cur_hi.z | ((cur_hi.w & F_TEXTURED) << 12);
+          best = t, tag = depth, nhits++;
+#endif
+        }
+      }
+      pc += 2u * RSZ;  // (its data record)
     } else if (op == OP_PUSH) {
       const uint32_t kind = (cur_hi.w >> F_KIND_SHIFT) & 7u;
       if (RT_REG_STACK0 && depth == 0u) {  // level 0 rides in registers: every wrapper of the reference's scenes is an outermost one

@@ -9,7 +9,7 @@
 #define RT_CENSUS_AT(base_) \
     if (COUNT) { \
       const uint32_t cop_ = have_ray ? (op == 0xfeu ? 0xfeu : (cur_hi.w & 0xffu)) : 0xffu; \
-      const bool held_ = cop_ == 0xfeu || (cop_ >= OP_SPHERE && cop_ <= OP_SLOW_LAST && (cur_hi.w & F_GATHER) != 0u && !release); \
+      const bool held_ = cop_ == 0xfeu || (RT_SLOW_OP(cop_) && (cur_hi.w & F_GATHER) != 0u && !release); \
       const uint32_t cls_ = !have_ray ? 2u : held_ ? 3u : cop_ == OP_BOX ? 0u : cop_ == OP_END ? 1u : 4u + (cop_ <= 8u ? cop_ : 8u); \
       _Pragma("unroll") for (uint32_t c_ = 0; c_ < 13u; c_++) { \
         const uint32_t n_ = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(cls_ == c_)); \
@@ -24,7 +24,7 @@
     // Lanes at a gather point (head of a list-level run of records every ray executes in the same order)
     // are held until `gather_min` of them wait there -- or nothing else can run -- and then walk the run
     // together: one record kind per iteration, many lanes wide, instead of a few lanes per kind.
-    const bool is_slow = op >= OP_SPHERE && op <= OP_SLOW_LAST;
+    const bool is_slow = RT_SLOW_OP(op);
     const bool at_gather = is_slow && (cur_hi.w & F_GATHER) != 0u;
     const uint64_t b_gather = __builtin_amdgcn_ballot_w64(at_gather);
 #ifndef RT_GATHER_LOW
@@ -113,17 +113,17 @@
 #pragma unroll 1
       do {
       RT_CENSUS_AT(16u);
-      if (COUNT) n_slow_it++, n_slow_lanes += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(op >= OP_SPHERE && op <= OP_SLOW_LAST));
+      if (COUNT) n_slow_it++, n_slow_lanes += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(RT_SLOW_OP(op)));
       exec_op(op, o, d, inv, time, best, pc, cur_lo, cur_hi, hp, hn, hmat, depth, tag, nhits, root_hits, ev_draws, RT_R_PIXEL, r_sample,
               RT_R_EVENT, stack, sv_o, sv_d, bmode, t_lo, b_saved, b_t1);
-      if (op >= OP_SPHERE && op <= OP_SLOW_LAST) {
+      if (RT_SLOW_OP(op)) {
         cur_lo = RT_FETCH_LO(pc), cur_hi = RT_FETCH_HI(pc), op = cur_hi.w & 0xffu;
         if ((cur_hi.w & F_GATHER) && !release) op = 0xfeu;  // arrived at a gather point: wait for the next batch
       }
       ahead++;
       {  // run ahead while enough lanes sit on slow records -- or while NO lane waits at a BOX record: then nobody is held up, and a
          // thin wave (the drain at the end of a launch: a handful of long paths) walks a list-level run in one pass, not one pass per record
-        const uint64_t m_sl = __builtin_amdgcn_ballot_w64(op >= OP_SPHERE && op <= OP_SLOW_LAST);
+        const uint64_t m_sl = __builtin_amdgcn_ballot_w64(RT_SLOW_OP(op));
         more = ahead < tune.run_ahead && ((uint32_t)__builtin_popcountll(m_sl) >= tune.run_ahead_min ||
                                           (RT_RUN_AHEAD_NOBOX && m_sl != 0 && __builtin_amdgcn_ballot_w64(op == OP_BOX) == 0));
       }

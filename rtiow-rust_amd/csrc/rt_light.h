@@ -25,7 +25,7 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
     float t;
     constexpr int XD = (FEAT & FEAT_DEEP_FEW_WRAPPERS) ? DEEP_FEW_WRAPPERS : MAX_DEEP_XFORM_DEPTH;
     constexpr int ML = (FEAT & FEAT_DEEP_ONE_LEVEL) ? 1 : MAX_MEDIUM_NESTING;
-    return walk_deep<0, COUNT, XD, ML, true>(sc, 0u, sc.n_prog, o, d, time, t_near, t_max, rng, nullptr, t, cnt);
+    return walk_deep<0, COUNT, XD, ML, true, (FEAT & FEAT_TRI) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, t_max, rng, nullptr, t, cnt);
   }
   V3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   int depth = 0;
@@ -77,6 +77,13 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
       pc++;
       continue;
     }
+    if ((FEAT & FEAT_TRI) && op == OP_TRI) {
+      if (COUNT) cnt.prim++;
+      float t;
+      if (tri_rec_hit_t(lo, hi, sc.lo[pc + 1], o, d, t_near, t_max, t)) return true;
+      pc += 2;  // (its data record)
+      continue;
+    }
     if ((FEAT & FEAT_XFORM) && op == OP_PUSH) {
       uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -109,11 +116,11 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
       float t1, t2;
       bool h1, h2 = false;
       if (hi.w & F_GENERAL_BOUNDARY) {
-        const BoundaryHit b1 = boundary_hit_t(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
+        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
         h1 = b1.any != 0u, t1 = b1.t;
         if (COUNT) cnt.aabb += b1.n_aabb, cnt.prim += b1.n_prim;
         if (h1) {
-          const BoundaryHit b2 = boundary_hit_t(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
+          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
           h2 = b2.any != 0u, t2 = b2.t;
           if (COUNT) cnt.aabb += b2.n_aabb, cnt.prim += b2.n_prim;
         }

@@ -135,6 +135,11 @@ RT_DEV QueueRsrc make_queue_rsrc(uint32_t* wave_base) {
   // raw buffer (stride 0, bounds = the wave's stack space in bytes; word 3 = gfx9 raw-buffer format bits)
   return __builtin_amdgcn_make_buffer_rsrc(wave_base, 0, FPOOL * FPOOL_FIELDS * 4u, 0x00020000);
 }
+// Which records a slow pass executes, and which keep a lane busy: the range SPHERE .. SEG (BOX .. SEG) and, in the instantiations for
+// programs with FEAT_TRI, the triangle record (flat_scene.h OP_TRI = 14, outside that range).  A lane standing on a record that is
+// neither BOX, nor slow, nor END would never advance: every classification of a lane's record goes through these two.
+#define RT_SLOW_OP(op_) (((op_) >= OP_SPHERE && (op_) <= OP_SLOW_LAST) || (TRI && (op_) == (uint32_t)OP_TRI))
+#define RT_BUSY_OP(op_) (((op_) >= OP_BOX && (op_) <= OP_SLOW_LAST) || (TRI && (op_) == (uint32_t)OP_TRI))
 #define RT_IN_LDS(pc_) (PROG == 1 || (PROG == 2 && (pc_) < win_bytes))
 #define RT_FETCH_LO(pc_) (RT_IN_LDS(pc_) ? *reinterpret_cast<const uint4*>(s_bytes + (pc_)) : sc.lo[(pc_) >> 5])
 #define RT_FETCH_HI(pc_) (RT_IN_LDS(pc_) ? *reinterpret_cast<const uint4*>(s_bytes + (pc_) + 16u) : fetch_hi_global(sc, (pc_) >> 5))
@@ -193,7 +198,9 @@ RT_DEV void full_push_finished(const QueueRsrc qr, uint32_t& s_count, uint32_t& 
 // and resume the main walk behind the stream.  The boundary's BOX records run in the box loop and its primitives in the
 // slow passes like any others, so a complex boundary is scheduled as well as the rest of the scene.  A template variant:
 // 5 more VGPRs, paid only by scenes that need it.
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false>
+// TRI: the program may hold OP_TRI records (FEAT_TRI): the TRI cases of exec_op and rebuild_hit and the wider record classes are
+// compiled into these instantiations alone -- the others keep the code they had.
+template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false>
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_pool(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -372,6 +379,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
       p = vadd(ro, smul(t, rd));
     } else if (r_op == OP_PRISM) {
       p = vadd(ro, smul(t, rd)), n = prism_normal(bpc & 7u);
+    } else if (TRI && r_op == OP_TRI) {  // p = o + t d as Rect does, n = +-N from the record pair
+      p = vadd(ro, smul(t, rd)), n = tri_rec_normal(r_hi, RT_FETCH_LO(rpc + RSZ), RT_FETCH_HI(rpc + RSZ));
     } else {  // MEDIUM: object.rs:567-571
       p = vadd(ro, smul(t, rd)), n = mk(1.f, 0.f, 0.f);
     }
@@ -394,7 +403,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
   for (;;) {
     uint32_t op = have_ray ? (cur_hi.w & 0xffu) : 0xffu;
     const uint64_t m_box = __builtin_amdgcn_ballot_w64(op == OP_BOX);
-    const uint64_t m_slow = __builtin_amdgcn_ballot_w64(op >= OP_SPHERE && op <= OP_SLOW_LAST);
+    const uint64_t m_slow = __builtin_amdgcn_ballot_w64(RT_SLOW_OP(op));
     const uint32_t n_busy = (uint32_t)__builtin_popcountll(m_box | m_slow);
     // ============================== SERVICE ======================================================
     // due when enough lanes are idle AND the service can do something for them: rays to hand out (T), or a full shade pass once
@@ -811,7 +820,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
 #undef RT_R_PIXEL
 #undef RT_R_EVENT
     op = have_ray ? (cur_hi.w & 0xffu) : 0xffu;
-    const uint32_t busy = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(op >= OP_BOX && op <= OP_SLOW_LAST));
+    const uint32_t busy = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(RT_BUSY_OP(op)));
     if (64u - busy >= tune.refill_min || busy == 0) break;
     }
   }
@@ -846,6 +855,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
   }
 }
 
+#undef RT_SLOW_OP
+#undef RT_BUSY_OP
 #undef RT_IN_LDS
 #undef RT_FETCH_LO
 #undef RT_FETCH_HI

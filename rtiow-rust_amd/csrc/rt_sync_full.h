@@ -10,7 +10,7 @@
 
 namespace rtg {
 
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false>
+template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false>  // (TRI: as render_full_pool's)
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_sync(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -31,6 +31,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
     }
   }
   const char* s_bytes = reinterpret_cast<const char*>(s_mem);
+#define RT_SLOW_OP(op_) (((op_) >= OP_SPHERE && (op_) <= OP_SLOW_LAST) || (TRI && (op_) == (uint32_t)OP_TRI))  // (rt_pool_full.h)
+#define RT_BUSY_OP(op_) (((op_) >= OP_BOX && (op_) <= OP_SLOW_LAST) || (TRI && (op_) == (uint32_t)OP_TRI))
 #define RT_IN_LDS(pc_) (PROG == 1 || (PROG == 2 && (pc_) < win_bytes))
 #define RT_FETCH_LO(pc_) (RT_IN_LDS(pc_) ? *reinterpret_cast<const uint4*>(s_bytes + (pc_)) : sc.lo[(pc_) >> 5])
 #define RT_FETCH_HI(pc_) (RT_IN_LDS(pc_) ? *reinterpret_cast<const uint4*>(s_bytes + (pc_) + 16u) : fetch_hi_global(sc, (pc_) >> 5))
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
 #undef RT_R_PIXEL
 #undef RT_R_EVENT
     op = have_ray ? (cur_hi.w & 0xffu) : 0xffu;
-    if (__builtin_amdgcn_ballot_w64(op >= OP_BOX && op <= OP_SLOW_LAST) == 0) break;
+    if (__builtin_amdgcn_ballot_w64(RT_BUSY_OP(op)) == 0) break;
     }
     if (have_ray) st = ST_SHADE;
   }
@@ -274,6 +276,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
       atomicAdd(&counters[16], t_shade), atomicAdd(&counters[17], 0ull), atomicAdd(&counters[18], t_box), atomicAdd(&counters[19], t_slow);
     }
   }
+#undef RT_SLOW_OP
+#undef RT_BUSY_OP
 #undef RT_IN_LDS
 #undef RT_FETCH_LO
 #undef RT_FETCH_HI

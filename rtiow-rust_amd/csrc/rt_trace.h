@@ -5,6 +5,7 @@
 #include "rt_device.h"
 #include "rt_image.h"
 #include "rt_sphere_hit.h"
+#include "rt_triangle.h"
 
 namespace rtg {
 
@@ -127,6 +128,17 @@ RT_DEV V3 prism_normal(uint32_t face) {  // object.rs:212 + FlipNormals (object.
   return (face & 4u) ? vneg(n) : n;
 }
 
+// A triangle (flat_scene.h OP_TRI; include/rtiow_gpu_mesh.h): (lo, hi) the TRI record, xlo = lo of the data record behind it.
+// The test itself is rt_triangle.h's, the one source for host and device.
+RT_DEV bool tri_rec_hit_t(uint4 lo, uint4 hi, uint4 xlo, V3 o, V3 d, float t0, float t1, float& t_out) {
+  return tri_hit_t(Tri3{u2f(lo.x), u2f(lo.y), u2f(lo.z)}, Tri3{u2f(lo.w), u2f(hi.x), u2f(hi.y)}, Tri3{u2f(xlo.x), u2f(xlo.y), u2f(xlo.z)},
+                   Tri3{o.x, o.y, o.z}, Tri3{d.x, d.y, d.z}, t0, t1, t_out);
+}
+RT_DEV V3 tri_rec_normal(uint4 hi, uint4 xlo, uint4 xhi) {  // N, or -N under an odd number of FlipNormals; two-sided like Rect
+  const V3 n = mk(u2f(xlo.w), u2f(xhi.x), u2f(xhi.y));
+  return (hi.w & F_FLIP) ? vneg(n) : n;
+}
+
 // object.rs:349-355
 RT_DEV V3 rot_y(V3 p, float s, float c) {
   return mk(vdot(p, mk(c, 0.f, s)), vdot(p, mk(0.f, 1.f, 0.f)), vdot(p, mk(-s, 0.f, c)));
@@ -184,6 +196,8 @@ struct BoundaryHit {
   float t;
   uint32_t any, n_aabb, n_prim;
 };
+// TRI: the stream may hold OP_TRI records (programs with FEAT_TRI); the instantiation without keeps the code it had
+template <bool TRI = false>
 __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __restrict__ prog_lo, const uint4* __restrict__ prog_hi,
                                                                 uint32_t first, uint32_t end_pc, V3 o, V3 d, float time,
                                                                 float t_lo, float t_hi) {
@@ -231,6 +245,11 @@ __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __r
       uint32_t face;
       if (prism_hit_t(lo, hi, o, d, t_lo, best, t, face)) best = t, any = true;
       pc++;
+    } else if (TRI && op == OP_TRI) {
+      n_prim++;
+      float t;
+      if (tri_rec_hit_t(lo, hi, prog_lo[pc + 1], o, d, t_lo, best, t)) best = t, any = true;
+      pc += 2;  // (its data record)
     } else if (op == OP_PUSH) {
       const uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -272,7 +291,8 @@ __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __r
 // needs (FEAT_DEEP_FEW_WRAPPERS / FEAT_DEEP_ONE_LEVEL) -- the stacks are private memory and registers of every lane.
 // ANY (LEVEL 0, `rec` == null; rt_light.h occluded): an occlusion query over [t_lo, t_hi) -- returns at the first accepted hit,
 // t_out unset.  Its boundary queries are the ordinary closest-t ones.
-template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING, bool ANY = false>
+// TRI: the program may hold OP_TRI records (FEAT_TRI); the instantiations without keep the code they had.
+template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING, bool ANY = false, bool TRI = false>
 __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t first, uint32_t end_pc, V3 o, V3 d, const float time,
                                                     const float t_lo, const float t_hi, SampleRng& rng, HitRec* rec, float& t_out,
                                                     Counts& cnt) {
@@ -353,6 +373,16 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
         if (ANY) return true;
       }
       pc++;
+    } else if (TRI && op == OP_TRI) {
+      if (COUNT) cnt.prim++;
+      const uint4 xlo = sc.lo[pc + 1];
+      float t;
+      if (tri_rec_hit_t(lo, hi, xlo, o, d, t_lo, best, t)) {
+        if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]), rec->mat = hi.z;
+        best = t, any = true, tag = depth, nhits++;
+        if (ANY) return true;
+      }
+      pc += 2;  // (its data record)
     } else if (op == OP_PUSH) {
       uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -397,14 +427,14 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
       float t1 = 0.f, t2 = 0.f;
       bool h1 = false, h2 = false;
       if (general) {
-        if constexpr (LEVEL < ML) h1 = walk_deep<LEVEL + 1, COUNT, XD, ML>(sc, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX, rng, nullptr, t1, cnt);
+        if constexpr (LEVEL < ML) h1 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI>(sc, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX, rng, nullptr, t1, cnt);
       } else {
         if (COUNT) cnt.prim++;
         h1 = prim_hit_t(blo, bhi, o, d, -F32_MAX, F32_MAX, t1);
       }
       if (h1) {
         if (general) {
-          if constexpr (LEVEL < ML) h2 = walk_deep<LEVEL + 1, COUNT, XD, ML>(sc, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX, rng, nullptr, t2, cnt);
+          if constexpr (LEVEL < ML) h2 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI>(sc, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX, rng, nullptr, t2, cnt);
         } else {
           if (COUNT) cnt.prim++;
           h2 = prim_hit_t(blo, bhi, o, d, t1 + 0.0001f, F32_MAX, t2);
@@ -461,7 +491,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
     float t;
     constexpr int XD = (FEAT & FEAT_DEEP_FEW_WRAPPERS) ? DEEP_FEW_WRAPPERS : MAX_DEEP_XFORM_DEPTH;
     constexpr int ML = (FEAT & FEAT_DEEP_ONE_LEVEL) ? 1 : MAX_MEDIUM_NESTING;
-    return walk_deep<0, COUNT, XD, ML>(sc, 0u, sc.n_prog, o, d, time, t_near, F32_MAX, rng, &rec, t, cnt);
+    return walk_deep<0, COUNT, XD, ML, false, (FEAT & FEAT_TRI) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, F32_MAX, rng, &rec, t, cnt);
   }
   V3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);  // aabb.rs:17, hoisted: depends on the ray only
   float best = F32_MAX;
@@ -535,6 +565,17 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       pc++;
       continue;
     }
+    if ((FEAT & FEAT_TRI) && op == OP_TRI) {  // include/rtiow_gpu_mesh.h; rt_triangle.h
+      if (COUNT) cnt.prim++;
+      const uint4 xlo = sc.lo[pc + 1];
+      float t;
+      if (tri_rec_hit_t(lo, hi, xlo, o, d, t_near, best, t)) {
+        rec.t = t, rec.p = vadd(o, smul(t, d)), rec.n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]), rec.mat = hi.z;
+        best = t, any = true, tag = depth, nhits++;
+      }
+      pc += 2;  // (its data record)
+      continue;
+    }
     if ((FEAT & FEAT_XFORM) && op == OP_PUSH) {
       uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -583,7 +624,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       float t1, t2;
       bool h1, h2 = false;
       if (general) {
-        const BoundaryHit b1 = boundary_hit_t(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
+        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
         h1 = b1.any != 0u, t1 = b1.t;
         if (COUNT) cnt.aabb += b1.n_aabb, cnt.prim += b1.n_prim;
       } else {
@@ -592,7 +633,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       }
       if (h1) {
         if (general) {
-          const BoundaryHit b2 = boundary_hit_t(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
+          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
           h2 = b2.any != 0u, t2 = b2.t;
           if (COUNT) cnt.aabb += b2.n_aabb, cnt.prim += b2.n_prim;
         } else {

@@ -24,6 +24,7 @@
 #include "../../include/rtiow_gpu_query.h"
 #include "../../include/rtiow_gpu_rays.h"
 #include "../../include/rtiow_gpu_image.h"
+#include "../../include/rtiow_gpu_mesh.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -823,7 +824,7 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
     s->dev2.lds_off = nullptr, s->dev2.lds_image_bytes = 0;
     for (const Packet& h : fs.hi2) s->n_box2 += (h.w[3] & 0xffu) == OP_BOX ? 1u : 0u;
   }
-  if ((fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0) {  // lean program (BOX / SPHERE / END): layout of its LDS image (rt_pool.h)
+  if ((fs.features & FEAT_NOT_LEAN) == 0) {  // lean program (BOX / SPHERE / END): layout of its LDS image (rt_pool.h)
     s->ref.lo = s->dev.lo, s->ref.hi = s->dev.hi;
     if ((rc = lean_images(s, &s->ref, fs.lo, fs.hi))) {
       rtg_scene_destroy(s);
@@ -1233,3 +1234,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 #include "rtg_rays.inc"
 
 #include "rtg_image.inc"
+
+#include "rtg_mesh.inc"

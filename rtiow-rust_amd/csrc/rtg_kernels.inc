@@ -3,6 +3,8 @@
 // Kernels
 // ===================================================================================================
 constexpr uint32_t FEAT_ALL = FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | FEAT_TEXTURE;
+// a program with none of these bits is lean (BOX / SPHERE / END records only)
+constexpr uint32_t FEAT_NOT_LEAN = FEAT_ALL | FEAT_BOUNDARY | FEAT_TRI;
 
 __device__ __forceinline__ void flush_counts(const Counts& c, uint32_t draws, unsigned long long* g) {
   // one atomic per counter per wave would be nicer; the instrumented variant is not the timed one

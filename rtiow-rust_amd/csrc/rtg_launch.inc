@@ -54,6 +54,7 @@ static uint64_t owned_pixels(const DevParams& d) {
 template <bool SIZED, typename F>
 static void with_feat(const rtg_scene* s, F&& f) {
   constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+  if ((s->features & FEAT_DEEP) && (s->features & FEAT_TRI)) return f(std::integral_constant<uint32_t, D | FEAT_TRI>{});  // (one size: the largest)
   if (s->features & FEAT_DEEP) {
     if constexpr (SIZED) {
       const bool few = s->deep_sized && (s->features & FEAT_DEEP_FEW_WRAPPERS) != 0, one = s->deep_sized && (s->features & FEAT_DEEP_ONE_LEVEL) != 0;
@@ -63,7 +64,8 @@ static void with_feat(const rtg_scene* s, F&& f) {
     }
     return f(std::integral_constant<uint32_t, D>{});
   }
-  if ((s->features & (FEAT_ALL | FEAT_BOUNDARY)) == 0) return f(std::integral_constant<uint32_t, 0u>{});
+  if ((s->features & FEAT_NOT_LEAN) == 0) return f(std::integral_constant<uint32_t, 0u>{});
+  if (s->features & FEAT_TRI) return f(std::integral_constant<uint32_t, FEAT_ALL | FEAT_TRI>{});  // (the only walks with a TRI case)
   return f(std::integral_constant<uint32_t, FEAT_ALL>{});
 }
 // Runtime bools as template arguments: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).  For kernel families of which
@@ -602,16 +604,27 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   const bool mats_in_lds = s->mat_lds > 0 && prog == 1 && full_pool_lds_bytes(window, waves) + mat_bytes <= budget;
   const size_t lds = full_pool_lds_bytes(window, waves) + (mats_in_lds ? mat_bytes : 0);
   void (*kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, uint32_t*, float*,
-                 uint32_t);
+                 uint32_t) = nullptr;
   const bool genb = (s->features & FEAT_BOUNDARY) != 0;  // a medium bounded by an object graph: the nested-walk variant
   void (*sync_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, PoolTuning, float*, uint32_t) = nullptr;
   void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
-  with_bools([&](auto tex_c, auto genb_c, auto list_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
-    constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value;
-    kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, LI> : (prog == 1 ? render_full_pool<1, T, COUNT, G, LI> : render_full_pool<2, T, COUNT, G, LI>);
-    sync_kernel = render_full_sync<1, T, COUNT, G, LI>;
-    pool2_kernel = render_full_pool2<T, COUNT, LI>;
-  }, tex, genb, sl.counts);
+  // a program with FEAT_TRI: the instantiations that execute OP_TRI records (rt_pool_full.h TRI) -- no LIST ones (launch_slice sends a
+  // counts call of such a scene to the baseline kernel) and never the pool-2 kernel (such a scene has no second program)
+  const bool tri = (s->features & FEAT_TRI) != 0;
+  with_bools([&](auto tex_c, auto genb_c, auto list_c, auto tri_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
+    constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value, TR = decltype(tri_c)::value;
+    if constexpr (TR) {
+      if constexpr (!LI) {
+        kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, false, true> : (prog == 1 ? render_full_pool<1, T, COUNT, G, false, true> : render_full_pool<2, T, COUNT, G, false, true>);
+        sync_kernel = render_full_sync<1, T, COUNT, G, false, true>;
+      }
+    } else {
+      kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, LI> : (prog == 1 ? render_full_pool<1, T, COUNT, G, LI> : render_full_pool<2, T, COUNT, G, LI>);
+      sync_kernel = render_full_sync<1, T, COUNT, G, LI>;
+      pool2_kernel = render_full_pool2<T, COUNT, LI>;
+    }
+  }, tex, genb, sl.counts, tri);
+  if (!kernel) return hipErrorInvalidValue;  // (a counts call on a FEAT_TRI program: not routed here)
   // The lock-step kernel (rt_sync_full.h: one path per lane, no stacks, no pools) renders list worlds without a Bvh -- and, by
   // default (option sync = -1), programs whose Bvhs are tiny (<= 32 BOX records: the Criterion scene of benches/scene.rs has 15,
   // volume_test under bvh::from_scene 5; a box loop has nothing to batch there) and frames with fewer work items than the chip has
@@ -839,11 +852,14 @@ template <bool COUNT>
 static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevParams& d, float* d_out, hipStream_t stream, const SampleSlice& sl) {
   // geometry / texture features pick the kernel; the albedo-range bits only say whether the pool kernels' "accum
   // is +0" argument holds (rt_pool.h PoolField)
-  const uint32_t geom = s->features & (FEAT_ALL | FEAT_BOUNDARY);
+  const uint32_t geom = s->features & FEAT_NOT_LEAN;
   const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
   // FEAT_DEEP: graph shapes only the general walk of the baseline kernel handles (flat_scene.h)
   // scene option light_sampling: the one-lane-per-pixel family in every case, whatever options kernel, bvh4 and the pool thresholds say
-  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP) && !s->light_sampling;
+  // FEAT_TRI: the full-feature pool kernel and the lock-step kernel have instantiations that execute the record (rt_pool_full.h TRI);
+  // their LIST variants do not exist, so a counts call of such a scene renders on the baseline kernel
+  const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP) && !s->light_sampling &&
+                       !((s->features & FEAT_TRI) && sl.counts);
   if (pool_ok) {  // (launch_full_pool names the kernel it picks)
     s->cx->last_kernel = geom != 0 ? KernelKind::full_pool : KernelKind::lean_pool;
     return geom != 0 ? launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl) : launch_pool<COUNT>(s, cam, d, d_out, stream, sl);

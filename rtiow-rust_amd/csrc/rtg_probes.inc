@@ -199,7 +199,7 @@ static int debug_lean_program(const char* who, rtg_builder* b, const rtg_id* wor
     } catch (const BuildError& e) {
       return fail(e.code, e.msg);
     }
-    *lean = (fs.features & (FEAT_ALL | FEAT_BOUNDARY)) == 0;
+    *lean = (fs.features & FEAT_NOT_LEAN) == 0;
     lo->swap(fs.lo), hi->swap(fs.hi);
   }
   if (hi->size() > 0x7fffffffu) return fail(RTG_ERR_INVALID, std::string(who) + ": program too large");

@@ -26,7 +26,7 @@ const char* query_refusal(const rtg_query_params* p, size_t n, const rtg_stats* 
 // Does the lean kernel answer a query of n rays on this scene (option query_lds)?
 bool query_takes_lean(const rtg_scene* s, uint64_t n) {
   if (s->query_lds == 0) return false;
-  if ((s->features & (FEAT_ALL | FEAT_BOUNDARY | FEAT_DEEP)) != 0u) return false;  // BOX / SPHERE / END records only
+  if ((s->features & (FEAT_NOT_LEAN | FEAT_DEEP)) != 0u) return false;  // BOX / SPHERE / END records only
   if (s->n_prog == 0u || s->n_prog > QUERY_LEAN_MAX_RECORDS) return false;          // the reference program + the hand-out counter in 160 KB
   return s->query_lds >= 2 || n >= QUERY_LDS_MIN_RAYS;
 }

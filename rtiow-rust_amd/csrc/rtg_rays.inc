@@ -73,7 +73,7 @@ int rays_check(const rtg_scene* s, const float* rays, uint32_t ray_mode, const r
 
 // Does the lean pool kernel render a ray frame of this scene (option ray_pool)?  launch_slice's conditions for a camera frame.
 bool rays_take_pool(const rtg_scene* s, const DevParams& d) {
-  if (!s->ray_pool || (s->features & (FEAT_ALL | FEAT_BOUNDARY | FEAT_DEEP)) != 0u) return false;
+  if (!s->ray_pool || (s->features & (FEAT_NOT_LEAN | FEAT_DEEP)) != 0u) return false;
   const bool accum_zero = !(s->features & FEAT_WIDE_ALBEDO) && (!(s->features & FEAT_BRIGHT_ALBEDO) || d.max_bounces <= 63u);
   return accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu;
 }

@@ -3,6 +3,8 @@
 // the reference's would.
 #include "scene_builder.h"
 
+#include "rt_triangle.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -57,6 +59,9 @@ uint32_t SceneBuilder::add_object(const HostObject& o) {
       if (o.mat >= materials.size()) throw BuildError{-1, "constant_medium: bad material handle"};
       break;
     case HostObject::BVH: break;
+    case HostObject::TRI:
+      if (o.mat >= materials.size()) throw BuildError{-1, "triangle: bad material handle"};
+      break;
     default:
       if (!valid(o.a)) throw BuildError{-1, "wrapper: bad object handle"};
   }
@@ -112,6 +117,13 @@ Box3 SceneBuilder::bounding_box(uint32_t id, float e0, float e1) const {
       return merge(s, t);
     }
     case HostObject::MEDIUM: return bounding_box(o.a, e0, e1);
+    case HostObject::TRI:  // Rect's pad on every axis: a triangle may be flat in any of them, and Aabb::hit needs end > start
+      for (int i = 0; i < 3; i++) {
+        const float* v = triangles[o.a].v;  // the vertices as given (finite: add_triangle)
+        r.mn[i] = fmin_rs(fmin_rs(v[i], v[3 + i]), v[6 + i]) - 0.0001f;
+        r.mx[i] = fmax_rs(fmax_rs(v[i], v[3 + i]), v[6 + i]) + 0.0001f;
+      }
+      return r;
     default: return bvh_nodes[o.a].box;  // BVH
   }
 }
@@ -232,6 +244,61 @@ uint32_t SceneBuilder::add_bvh(const uint32_t* objs, size_t n, float e0, float e
   return (uint32_t)objects.size() - 1;
 }
 
+// include/rtiow_gpu_mesh.h.  The record (e1, e2, N) is made once, here, by the function the kernels' hit test comes with.
+static bool make_triangle(const float* v, HostTriangle* tri, const char** why) {
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(v[i])) return *why = "triangle: a vertex coordinate is not finite", false;
+  Tri3 e1, e2, nn;
+  const float len = tri_record(Tri3{v[0], v[1], v[2]}, Tri3{v[3], v[4], v[5]}, Tri3{v[6], v[7], v[8]}, e1, e2, nn);
+  if (!(len > 0.f) || !std::isfinite(len))
+    return *why = "triangle: the length of cross(v1 - v0, v2 - v0) is 0 or not finite (scale such a mesh with rtg_object_scale)", false;
+  const float rec[9] = {e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, nn.x, nn.y, nn.z};
+  for (int i = 0; i < 9; i++) tri->v[i] = v[i], tri->rec[i] = rec[i];
+  return true;
+}
+
+uint32_t SceneBuilder::add_triangle(const float* v, uint32_t material) {
+  if (material >= materials.size()) throw BuildError{-1, "triangle: bad material handle"};
+  HostTriangle tri;
+  const char* why = nullptr;
+  if (!make_triangle(v, &tri, &why)) throw BuildError{-1, why};
+  HostObject o;
+  o.kind = HostObject::TRI, o.mat = material, o.a = (uint32_t)triangles.size();
+  triangles.push_back(tri);
+  return add_object(o);
+}
+
+uint32_t SceneBuilder::add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah) {
+  if (n_triangles == 0) throw BuildError{-2, "Can't create a BVH from zero objects."};  // bvh.rs:60
+  if (material >= materials.size()) throw BuildError{-1, "mesh: bad material handle"};
+  if (n_triangles > 0xfffffffeull - objects.size()) throw BuildError{-4, "mesh: more triangles than object ids"};
+  std::vector<HostTriangle> tris(n_triangles);  // every triangle is checked before the builder changes
+  for (size_t t = 0; t < n_triangles; t++) {
+    float v[9];
+    for (int k = 0; k < 3; k++) {
+      const uint32_t ix = indices[3 * t + k];
+      if (ix >= n_vertices) throw BuildError{-1, "mesh: a vertex index is >= n_vertices"};
+      for (int c = 0; c < 3; c++) v[3 * k + c] = vertices[3 * (size_t)ix + c];
+    }
+    const char* why = nullptr;
+    if (!make_triangle(v, &tris[t], &why)) throw BuildError{-1, std::string("mesh: ") + why};
+  }
+  const size_t n_obj = objects.size(), n_nodes = bvh_nodes.size(), n_tri = triangles.size();
+  try {
+    std::vector<uint32_t> ids(n_triangles);
+    triangles.insert(triangles.end(), tris.begin(), tris.end());
+    for (size_t t = 0; t < n_triangles; t++) {
+      HostObject o;
+      o.kind = HostObject::TRI, o.mat = material, o.a = (uint32_t)(n_tri + t);
+      ids[t] = add_object(o);
+    }
+    return add_bvh(ids.data(), ids.size(), 0.f, 0.f, sah);  // (exposure (0, 0): nothing inside moves)
+  } catch (...) {
+    objects.resize(n_obj), bvh_nodes.resize(n_nodes), triangles.resize(n_tri);
+    throw;
+  }
+}
+
 // ---- flattening ------------------------------------------------------------------------------------
 namespace {
 void push(FlatScene* s, float a, float b, float c, float d, uint32_t e, uint32_t f, uint32_t g, uint32_t h) {
@@ -326,7 +393,8 @@ bool SceneBuilder::holds_medium(uint32_t id) const {
   switch (o.kind) {
     case HostObject::MEDIUM: return true;
     case HostObject::SPHERE:
-    case HostObject::RECT: return false;
+    case HostObject::RECT:
+    case HostObject::TRI: return false;
     case HostObject::AND: return holds_medium(o.a) || holds_medium(o.b);
     case HostObject::BVH: {
       std::vector<int32_t> todo(1, (int32_t)o.a);
@@ -361,6 +429,20 @@ void SceneBuilder::emit_bvh(int32_t node_id, int depth, FlatScene* out, int boun
 void SceneBuilder::emit(uint32_t id, bool under_bvh, int depth, FlatScene* out, int boundary, bool mark_roots, int saves) const {
   const HostObject& o = objects[id];
   if (fuse_primitive(*this, id, out, true, true)) return;
+  {  // FlipNormals* Triangle -> one TRI record and its data record (flat_scene.h OP_TRI); negation is exact, so F_FLIP gives the
+     // bits a PUSH / POP pair would.  Not in fuse_primitive: a triangle is no plain primitive (no segment, no second program,
+     // and as a medium's boundary it is an object graph).
+    bool flip = false;
+    uint32_t t = id;
+    while (objects[t].kind == HostObject::FLIP) flip = !flip, t = objects[t].a;
+    if (objects[t].kind == HostObject::TRI) {
+      const float *v = triangles[objects[t].a].v, *r = triangles[objects[t].a].rec;  // v0; e1, e2, N
+      push(out, v[0], v[1], v[2], r[0], fbits(r[1]), fbits(r[2]), objects[t].mat, OP_TRI | (flip ? F_FLIP : 0u) | mat_flags(*this, objects[t].mat));
+      push(out, r[3], r[4], r[5], r[6], fbits(r[7]), fbits(r[8]), 0, OP_EXT);
+      out->features |= FEAT_TRI;
+      return;
+    }
+  }
   switch (o.kind) {
     case HostObject::AND: {
       float p0[3], p1[3];
@@ -481,7 +563,7 @@ void SceneBuilder::flatten(const uint32_t* world, size_t n, FlatScene* out) cons
   bool has_box = false;
   for (const Packet& h : out->hi) has_box |= (h.w[3] & 0xffu) == OP_BOX;
   const bool full_pool = has_box && (out->features & (FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | FEAT_TEXTURE | FEAT_BOUNDARY)) != 0u &&
-                         !(out->features & FEAT_DEEP);
+                         !(out->features & (FEAT_DEEP | FEAT_TRI));  // (a TRI: the one-lane family, flat_scene.h OP_TRI)
   if (hoist_segments && full_pool && seg1 > seg0) flatten_program(world, n, out, seg0, seg1);
   if (full_pool) (void)flatten_pool2(world, n, out);  // the second program, when the world has the shape for it
   if (out->features & FEAT_DEEP) {  // which instantiation of the general walk this graph needs (flat_scene.h)
@@ -632,7 +714,7 @@ bool SceneBuilder::flatten_pool2(const uint32_t* world, size_t n, FlatScene* out
     for (size_t k = pi.second.first_obj; k < pi.second.end_obj; k++) emit(world[k], false, 0, &w);
     it.b = (uint32_t)w.lo.size();
   }
-  if (w.features & (FEAT_DEEP | FEAT_BOUNDARY)) return false;
+  if (w.features & (FEAT_DEEP | FEAT_BOUNDARY | FEAT_TRI)) return false;  // (FEAT_TRI: no world with a triangle has a second program, flat_scene.h OP_TRI)
   out->lo2 = std::move(w.lo), out->hi2 = std::move(w.hi);
   out->p2 = t;
   return true;
@@ -654,7 +736,8 @@ void SceneBuilder::light_table(const uint32_t* world, size_t n, std::vector<Ligh
       todo.pop_back();
       switch (o.kind) {
         case HostObject::SPHERE:
-        case HostObject::RECT: use[o.mat] |= OTHER; break;
+        case HostObject::RECT:
+        case HostObject::TRI: use[o.mat] |= OTHER; break;  // (a triangle emitter is found by scattered rays at full weight, never sampled)
         case HostObject::AND: todo.push_back(o.a), todo.push_back(o.b); break;
         case HostObject::MEDIUM: use[o.mat] |= OTHER, todo.push_back(o.a); break;
         case HostObject::BVH: {

@@ -20,11 +20,16 @@ struct Packet {
 };
 
 struct HostObject {
-  enum Kind : uint8_t { SPHERE, RECT, FLIP, TRANSLATE, SCALE, ROTATE_Y, AND, MOVE, MEDIUM, BVH } kind;
+  enum Kind : uint8_t { SPHERE, RECT, FLIP, TRANSLATE, SCALE, ROTATE_Y, AND, MOVE, MEDIUM, BVH, TRI } kind;
   float f[6] = {0, 0, 0, 0, 0, 0};  // kind-specific scalars (see scene_builder.cpp)
-  uint32_t a = 0xffffffffu, b = 0xffffffffu;  // children (object ids) / bvh root node id
+  uint32_t a = 0xffffffffu, b = 0xffffffffu;  // children (object ids) / bvh root node id / TRI: index into SceneBuilder::triangles
   uint32_t mat = 0xffffffffu;
   int axis = 0;
+};
+
+struct HostTriangle {  // include/rtiow_gpu_mesh.h: the vertices as given (the bounding box is theirs) and the record rt_triangle.h tri_record makes
+  float v[9];    // v0, v1, v2
+  float rec[9];  // e1, e2, N
 };
 
 struct HostBvhNode {  // bvh.rs:9-19
@@ -71,6 +76,7 @@ class SceneBuilder {
  public:
   std::vector<HostObject> objects;
   std::vector<HostBvhNode> bvh_nodes;
+  std::vector<HostTriangle> triangles;  // one per TRI object
   std::vector<HostMaterial> materials;
   std::vector<HostTexture> textures;
   std::array<float, 1024> perlin_vecs{};
@@ -80,6 +86,9 @@ class SceneBuilder {
   // All return an id or throw BuildError.
   uint32_t add_object(const HostObject& o);
   uint32_t add_bvh(const uint32_t* objs, size_t n, float e0, float e1, bool sah = false);
+  // include/rtiow_gpu_mesh.h: one triangle (v: 9 floats), and n_triangles of them under one Bvh; a refusal leaves the builder as it was
+  uint32_t add_triangle(const float* v, uint32_t material);
+  uint32_t add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah);
   Box3 bounding_box(uint32_t obj, float e0, float e1) const;
   void flatten(const uint32_t* world, size_t n, FlatScene* out) const;
   // The light table of `world` (flat_scene.h LightRect) and, per material, whether it is sampled (scene option light_sampling)

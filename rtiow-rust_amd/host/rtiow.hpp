@@ -27,6 +27,7 @@
 
 #include "../../include/rtiow_gpu.h"
 #include "../../include/rtiow_gpu_image.h"
+#include "../../include/rtiow_gpu_mesh.h"
 
 namespace rtiow {
 
@@ -201,6 +202,28 @@ struct ConstantMedium {  // object.rs:533-541
 };
 template <class O>
 ConstantMedium(O, float, Material) -> ConstantMedium<O>;
+// Not in the reference (include/rtiow_gpu_mesh.h): a triangle, counter-clockwise front face, two-sided like Rect ...
+struct Triangle {
+  Vec3 v0, v1, v2;
+  Material material;
+  rtg_id flatten(rtg_builder* b) const { return check_id(rtg_object_triangle(b, v0.data(), v1.data(), v2.data(), material.emit(b))); }
+};
+// ... and an indexed mesh of them under one Bvh (sah: the SAH builder instead of Bvh::new's median split).  The arrays are
+// shared, not copied, until the scene is built.
+struct Mesh {
+  std::shared_ptr<const std::vector<float>> vertices;    // 3 per vertex
+  std::shared_ptr<const std::vector<uint32_t>> indices;  // 3 per triangle
+  Material material;
+  bool sah = false;
+  rtg_id flatten(rtg_builder* b) const {
+    return check_id(rtg_object_mesh(b, vertices->data(), vertices->size() / 3, indices->data(), indices->size() / 3, material.emit(b), sah ? 1u : 0u));
+  }
+};
+inline Mesh mesh(std::vector<float> vertices, std::vector<uint32_t> indices, Material m, bool sah = false) {
+  if (vertices.size() % 3 || indices.size() % 3) throw Error(RTG_ERR_INVALID, "object::mesh: three floats per vertex, three indices per triangle");
+  return Mesh{std::make_shared<const std::vector<float>>(std::move(vertices)), std::make_shared<const std::vector<uint32_t>>(std::move(indices)),
+              std::move(m), sah};
+}
 }  // namespace object
 
 namespace bvh {

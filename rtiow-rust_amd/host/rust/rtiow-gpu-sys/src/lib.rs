@@ -11,6 +11,8 @@ use std::os::raw::{c_char, c_float, c_int, c_void};
 
 /// Image textures (`include/rtiow_gpu_image.h`): a sampled image as a fourth texture kind.
 pub mod image;
+/// Triangles and meshes (`include/rtiow_gpu_mesh.h`): a third primitive beside Sphere and Rect.
+pub mod mesh;
 /// Ray frames (`include/rtiow_gpu_rays.h`): path-trace the caller's rays.
 pub mod rays;
 

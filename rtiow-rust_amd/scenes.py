@@ -79,6 +79,21 @@ def cornell_box_scene(b, nx, ny):
     return cornell_box_with_boxes(b), cam, exposure
 
 
+def cornell_mesh_scene(b, nx, ny, subdivisions=2, sah=False):
+    """Not in the reference: the Cornell box with two triangle meshes (include/rtiow_gpu_mesh.h) in place of its two prisms --
+    an icosphere of 20 * 4^subdivisions triangles where the short box stood, and the tall box as a 12-triangle box mesh under
+    the reference's own Translate{RotateY}."""
+    from . import triangle
+    cam, exposure = _cornell_camera(b.be, nx, ny)
+    scene = cornell_box(b)
+    white = b.lambertian(b.constant(vfrom(0.73)))
+    vs, fs = triangle.icosphere(subdivisions, radius=82.5, centre=(212.5, 82.5, 147.5))
+    scene.append(b.mesh(vs, fs, white, sah=sah))
+    vb, fb = triangle.box((0.0, 0.0, 0.0), (165.0, 330.0, 165.0))
+    scene.append(b.translate(v(265.0, 0.0, 295.0), b.rotate_y(15.0, b.mesh(vb, fb, white, sah=sah))))
+    return scene, cam, exposure
+
+
 def motion_test(b, nx, ny):
     """main.rs:33-67"""
     cam, exposure = _cornell_camera(b.be, nx, ny)
