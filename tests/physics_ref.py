@@ -1,11 +1,12 @@
-"""An independent float64 statement of what the renderer computes, for test_physics_oracle.py (the CPU restatement) and
-test_physics_gpu.py (the HIP kernels).  Nothing here is computed by either: the one thing shared with the project is the
+"""An independent float64 statement of what the renderer computes, for test_physics_oracle.py (the CPU restatement),
+test_physics_gpu.py (the HIP kernels) and the random mesh worlds of test_fuzz_mesh.py / test_fuzz_mesh_gpu.py.  Nothing here is computed by either: the one thing shared with the project is the
 builder surface -- Recorder wraps a Builder and keeps a Python description of every texture, material and object beside its
 handle -- and every expectation below comes from that description in numpy float64.
 
 A. closest_hit: the closest hit of rays with a recorded graph, written from the geometry.  A graph is flattened to its
-   primitives (spheres, axis rects; a prism is six rects, a Bvh its leaves, And both sides), each with the chain of
-   Translate / Scale / RotateY / LinearMove above it and the parity of its FlipNormals; the closest hit is the smallest
+   primitives (spheres, axis rects, triangles; a prism is six rects, a mesh its triangles, a Bvh its leaves, And both
+   sides), each with the chain of Translate / Scale / RotateY / LinearMove above it and the parity of its FlipNormals; the
+   closest hit is the smallest
    admissible ray parameter over the primitives.  Conventions (the reference's, read as a specification): a rect's ranges are
    half open and its normal is +axis; RotateY(theta) maps a local point (x, y, z) to (c x + s z, y, -s x + c z); Scale
    multiplies points by the factor and DIVIDES the normal by it, without renormalising; LinearMove shifts the ray origin by
@@ -24,6 +25,25 @@ A. closest_hit: the closest hit of rays with a recorded graph, written from the 
    TOL_T, TOL_P, TOL_N are 4 x those figures: 2.1e-03, 4.8e-04, 6.8e-04.  Float32 error grows with 1 / margin, a wrong formula moves answers by O(1).
    The feature planes use the same margin and tolerances per pixel (cap 10 % of pixels); under a checker a pixel is also
    left out when |sin sin sin| at one of its hits is within TOL_P of zero.
+   Triangles (Recorder.triangle / mesh; one Prim("tri", (v0, v1, v2)) each): the plane crossing t = n.(v0 - o) / n.d with
+   n = e1 x e2 and the barycentric coordinates by Cramer's rule on the Gram matrix of (e1, e2) -- not Moeller-Trumbore's cross
+   products --, edges inclusive, the unit normal n / |n|.  Margin terms: the barycentric distances |u|, |v|, |1 - u - v|;
+   |n.d| / (|e1| |e2| |d|); the crossing's distance from t_near (alone, when the crossing lies behind the origin).  This is
+   the one statement of the triangle: triangle_ref.closest_hit64 calls it, and its docstring holds what was measured on
+   mesh_cases' graphs (worst t 8.3e-05, p 1.3e-04, normal 2.5e-07; 0.10 .. 2.05 % left out).
+   At the scale of the random worlds (fuzz_scenes.py: tens to hundreds of units, origins up to 1500 away; 2048 rays a world;
+   fuzz_mesh_cases.py holds the seed sets and test_fuzz_mesh.py prints the figures), measured on the CPU, float32:
+     spheres, rects and prisms, eight analytic worlds on the restatement: 0.10 .. 0.54 % left out; worst t 1.5e-03, p 7.3e-06,
+     normal 1.1e-04;
+     triangles, the twelve media-free mesh worlds through triangle_ref.closest32: 0.00 .. 1.23 % left out; worst t 5.3e-04,
+     p 8.3e-06, normal 2.0e-07;
+     no flag, material or primitive mismatch in either.  Per hit kind the tolerance there is the larger of the recorded one
+     and 4 x these (fuzz_mesh_cases.TOL).
+   Image textures (Recorder.image) are evaluated by image_ref.sample64, also as a checker's child.  A nearest-filtered image
+   joins the leave-the-pixel-out rule with its margin (texels to the next texel change) against what the position tolerance
+   TOL_P max(1, |p|) can move (x, y), plus image_ref.NEAREST_MARGIN.  A bilinear image gets a per-point allowance on the albedo,
+   derived and not measured: the local slope of the tent sum times that shift (image_ref.bilinear_allowance), plus the
+   measured BILINEAR_TOL of the image's size (image_ref's docstring: 1.4e-06 at 2 x 3 .. 2.4e-06 at 8 x 8, worst, on the CPU).
 B. exact_radiance: no reference at all -- all albedos 0.5 and one emitter colour of powers of two make every sample's colour
    exactly 0.5^bounces * L in float32.
 C. trace_tree: a float64 tracer of deterministic interfaces (mirror metal, dielectric with Schlick) that returns, for one
@@ -131,6 +151,21 @@ class Recorder:
     def bvh_sah(self, objs, exposure=(0.0, 1.0)):
         return self._put(self.objects, self._b.bvh_sah(objs, exposure), ("bvh", tuple(objs)))
 
+    def image(self, img, params):
+        """texels [h, w, 3] and the in-fields of the parameters, the eight floats rounded to float32"""
+        prm = dict(mapping=int(params["mapping"]), filter=int(params["filter"]), wrap_u=int(params["wrap_u"]), wrap_v=int(params["wrap_v"]),
+                   m=_r32(np.asarray(params["m"]).reshape(-1)[:8]))
+        return self._put(self.textures, self._b.image(img, params), ("image", _r32(img), prm))
+
+    def triangle(self, v0, v1, v2, material):
+        tri = _r32([[v0[0], v0[1], v0[2]], [v1[0], v1[1], v1[2]], [v2[0], v2[1], v2[2]]])
+        return self._put(self.objects, self._b.triangle(v0, v1, v2, material), ("tri", tri, material))
+
+    def mesh(self, vertices, indices, material, sah=False):
+        """[m, 3, 3]: the three vertices of every face, in the order of `indices`"""
+        tris = _r32(np.asarray(vertices).reshape(-1, 3))[np.asarray(indices, dtype=np.int64).reshape(-1, 3)]
+        return self._put(self.objects, self._b.mesh(vertices, indices, material, sah=sah), ("mesh", tris, material, bool(sah)))
+
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # A. the closest hit
@@ -152,6 +187,11 @@ def primitives(rec, world, media=None):
             into.append(Prim("sphere", (r[1],), r[2], chain, sign))
         elif k == "rect":
             into.append(Prim("rect", r[1:5], r[5], chain, sign))
+        elif k == "tri":
+            into.append(Prim("tri", (r[1][0], r[1][1], r[1][2]), r[2], chain, sign))
+        elif k == "mesh":
+            for tri in r[1]:
+                into.append(Prim("tri", (tri[0], tri[1], tri[2]), r[2], chain, sign))
         elif k == "prism":
             p0, p1, m = r[1], r[2], r[3]
             for ax in range(3):
@@ -242,20 +282,29 @@ def _rect_centre(pr):
     return q
 
 
+def _centre(pr):
+    if pr.kind == "sphere":
+        return np.zeros((1, 3))
+    if pr.kind == "tri":
+        return ((pr.params[0] + pr.params[1] + pr.params[2]) / 3.0)[None, :]
+    return _rect_centre(pr)
+
+
 def closest_hit(prims, o, d, time, t_near=T_NEAR, fault=None, roots=True):
     """The closest hit of the rays (o, d, time: float64 [n, 3], [n, 3], [n]) with `prims`: a dict of hit (bool), t, p, n,
-    material (uint32 handle) and margin (the conditioning margin of the docstring).  roots=False leaves the roots' distance
+    material (uint32 handle), prim (the index of the winning primitive in `prims`, -1 on a miss) and margin (the conditioning
+    margin of the docstring).  roots=False leaves the roots' distance
     from t_near out of the margin: a ray that starts ON a surface has a root at 0, t_near away from t_near by construction."""
     o, d, time = np.asarray(o, F), np.asarray(d, F), np.asarray(time, F)
     n = len(o)
     inf = np.full(n, np.inf)
     best, second = inf.copy(), inf.copy()
-    bp, bn, bm = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, np.uint32)
+    bp, bn, bm, bi = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, np.uint32), np.full(n, -1, np.int64)
     dlen = np.sqrt(_dot(d, d))
     size = np.maximum(1.0, np.sqrt(_dot(o, o)))
     seen = []
     with np.errstate(all="ignore"):
-        for pr in prims:
+        for number, pr in enumerate(prims):
             lo, ld = _to_local(pr.chain, o, d, time, fault)
             if pr.kind == "sphere":
                 r = pr.params[0]
@@ -273,6 +322,29 @@ def closest_hit(prims, o, d, time, t_near=T_NEAR, fault=None, roots=True):
                 ts = np.where(np.isfinite(t), t, 0.0)
                 pl = lo + ts[:, None] * ld
                 nl = pl / r
+            elif pr.kind == "tri":
+                # the plane crossing t = n.(v0 - o) / n.d with n = e1 x e2, barycentrics by Cramer's rule on the Gram matrix of
+                # (e1, e2), inclusive edges.  Margin: the barycentric distances |u|, |v|, |1 - u - v|; |n.d| / (|e1| |e2| |d|);
+                # the crossing's distance from t_near (alone, when the crossing is behind the origin)
+                v0, e1, e2 = pr.params[0], pr.params[1] - pr.params[0], pr.params[2] - pr.params[0]
+                nn = np.cross(e1, e2)
+                den = ld @ nn
+                tt = ((v0 - lo) @ nn) / den
+                ts = np.where(np.isfinite(tt), tt, 0.0)
+                q = lo + ts[:, None] * ld - v0
+                a11, a12, a22 = e1 @ e1, e1 @ e2, e2 @ e2
+                b1, b2 = q @ e1, q @ e2
+                gram = a11 * a22 - a12 * a12
+                u, v = (b1 * a22 - b2 * a12) / gram, (b2 * a11 - b1 * a12) / gram
+                inside = (u >= 0) & (v >= 0) & (u + v <= 1)
+                t = np.where(np.isfinite(tt) & (tt >= t_near) & inside, tt, np.inf)
+                bary = np.minimum(np.minimum(np.abs(u), np.abs(v)), np.abs(1.0 - u - v))
+                detm = np.abs(den) / (np.sqrt(a11) * np.sqrt(a22) * np.sqrt(_dot(ld, ld)))
+                rootm = np.abs(tt - t_near) * dlen / size if roots else inf
+                m = np.where(np.isfinite(tt), np.where(tt >= 0, np.minimum(np.minimum(bary, detm), rootm), rootm), detm)
+                front = np.where(np.isfinite(tt), tt, -np.inf)
+                pl = lo + ts[:, None] * ld
+                nl = np.broadcast_to(nn / np.sqrt(nn @ nn), (n, 3))
             else:
                 ax, r0, r1, k = pr.params
                 a0, a1 = [i for i in range(3) if i != ax]
@@ -293,13 +365,13 @@ def closest_hit(prims, o, d, time, t_near=T_NEAR, fault=None, roots=True):
             better = t < best
             second = np.where(better, best, np.minimum(second, t))
             best = np.where(better, t, best)
-            bp[better], bn[better], bm[better] = pw[better], nw[better], pr.material
+            bp[better], bn[better], bm[better], bi[better] = pw[better], nw[better], pr.material, number
             seen.append((front, m))
         hit = np.isfinite(best)
         margin = np.where(np.isfinite(second), (second - best) / np.abs(best), np.inf)
         for front, m in seen:
             margin = np.where(front <= best, np.minimum(margin, m), margin)
-    return {"hit": hit, "t": np.where(hit, best, 0.0), "p": bp, "n": bn, "material": bm, "margin": margin}
+    return {"hit": hit, "t": np.where(hit, best, 0.0), "p": bp, "n": bn, "material": bm, "prim": bi, "margin": margin}
 
 
 def aimed_rays(prims, n, seed, origin_box=None, near=None):
@@ -314,13 +386,26 @@ def aimed_rays(prims, n, seed, origin_box=None, near=None):
         v = rs.normal(size=(k, 3))
         return v / np.sqrt(_dot(v, v))[:, None]
 
-    def around(which, spread):
+    def around(which, spread, target=False):
         out = np.zeros((n, 3))
         for i in np.unique(which):
             at = which == i
             k, pr = int(at.sum()), prims[i]
             if pr.kind == "sphere":
                 q = pr.params[0] * spread(k)[:, None] * unit(k)
+            elif pr.kind == "tri":
+                # a target: the point of the plane with barycentrics from -0.1 .. 1.1 (u, v drawn; a pair beyond the third edge
+                # is mirrored back, so that about a sixth of the targets lie just outside an edge); an origin: such a point moved
+                # off the plane by 0.05 .. 3.05 times the triangle's size, to either side
+                v0, e1, e2 = pr.params[0], pr.params[1] - pr.params[0], pr.params[2] - pr.params[0]
+                u, v = rs.uniform(-0.1, 1.1, k), rs.uniform(-0.1, 1.1, k)
+                over = u + v > 1.1
+                u, v = np.where(over, 1.0 - u, u), np.where(over, 1.0 - v, v)
+                q = v0 + u[:, None] * e1 + v[:, None] * e2
+                if not target:
+                    nn = np.cross(e1, e2)
+                    off = 0.5 * (np.sqrt(e1 @ e1) + np.sqrt(e2 @ e2)) * (0.05 + spread(k)) * rs.choice([-1.0, 1.0], k)
+                    q = q + off[:, None] * (nn / np.sqrt(nn @ nn))
             else:
                 ax, r0, r1, kk = pr.params
                 a0, a1 = [a for a in range(3) if a != ax]
@@ -336,13 +421,13 @@ def aimed_rays(prims, n, seed, origin_box=None, near=None):
     dst = np.where(rs.uniform(size=n) < 0.5, src, rs.randint(0, len(prims), n))
     if near is not None:
         zero = np.zeros(1)
-        centre = np.array([point_to_world(pr.chain, np.zeros((1, 3)) if pr.kind == "sphere" else _rect_centre(pr), zero)[0] for pr in prims])
+        centre = np.array([point_to_world(pr.chain, _centre(pr), zero)[0] for pr in prims])
         for i in np.unique(src):
             close = np.nonzero(np.sqrt(((centre - centre[i]) ** 2).sum(axis=1)) <= near)[0]
             at = (src == i) & (dst != src)
             dst[at] = close[rs.randint(0, len(close), int(at.sum()))]
     origin = around(src, lambda k: rs.uniform(0.0, 3.0, k))          # < 1: inside a sphere, > 1: outside
-    target = around(dst, lambda k: rs.uniform(0.0, 1.15, k) ** 0.5)  # spheres: a chord, sometimes a near miss
+    target = around(dst, lambda k: rs.uniform(0.0, 1.15, k) ** 0.5, target=True)  # spheres: a chord, sometimes a near miss
     if origin_box is not None:
         origin = np.clip(origin, np.array(origin_box[0], F), np.array(origin_box[1], F))
     d = target - origin
@@ -503,24 +588,45 @@ def check_hits(pkg, be, name, fault=None):
 
 
 # feature planes ------------------------------------------------------------------------------------------------------------
-def texture_value(rec, tex, p):
-    """(value [n, 3], the smallest |sin sin sin| met on the way [n]) of a constant / checker texture at the points p."""
+def texture_value3(rec, tex, p, fault=None):
+    """(value [n, 3], eps [n], allowance [n]) of a constant / checker / image texture at the points p.  eps is the "leave the
+    pixel out when eps <= TOL_P" figure: the smallest |sin sin sin| met on the way and, for a nearest-filtered image, TOL_P times
+    the ratio of the sampler's margin (texels to the next texel change) to what can move (x, y): the position tolerance
+    TOL_P max(1, |p|) through image_ref.texel_shift, plus image_ref.NEAREST_MARGIN.  allowance is what a bilinear image's value
+    may deviate by: image_ref.bilinear_allowance for that position tolerance (derived: slope times shift) plus the measured
+    BILINEAR_TOL of the image's size."""
+    import image_ref as IR
     r = rec.textures[tex]
+    none, zero = np.full(len(p), np.inf), np.zeros(len(p))
     if r[0] == "constant":
-        return np.broadcast_to(r[1], p.shape).copy(), np.full(len(p), np.inf)
+        return np.broadcast_to(r[1], p.shape).copy(), none, zero
+    if r[0] == "image":
+        img, prm = r[1], r[2]
+        h, w = img.shape[0], img.shape[1]
+        val, margin = IR.sample64(img, prm, p, fault=fault)
+        dp = TOL_P * np.maximum(1.0, np.sqrt(_dot(p, p)))
+        if prm["filter"] == IR.NEAREST:
+            dx, dy = IR.texel_shift(prm, w, h, p, dp)
+            return val, TOL_P * margin / (np.maximum(dx, dy) + IR.NEAREST_MARGIN), zero
+        return val, none, IR.bilinear_allowance(img, prm, p, dp) + IR.BILINEAR_TOL[(w, h)]
     if r[0] != "checker":
-        raise ValueError("only constant and checker textures have a closed form here")
+        raise ValueError("only constant, checker and image textures have a closed form here")
     s = np.sin(10.0 * p).prod(axis=1)
-    v0, e0 = texture_value(rec, r[1], p)
-    v1, e1 = texture_value(rec, r[2], p)
+    v0, e0, a0 = texture_value3(rec, r[1], p, fault)
+    v1, e1, a1 = texture_value3(rec, r[2], p, fault)
     odd = s < 0
-    return np.where(odd[:, None], v1, v0), np.minimum(np.abs(s), np.where(odd, e1, e0))
+    return np.where(odd[:, None], v1, v0), np.minimum(np.abs(s), np.where(odd, e1, e0)), np.where(odd, a1, a0)
 
 
-def albedo_value(rec, mats, p, hit=None):
+def texture_value(rec, tex, p):
+    """(value [n, 3], the smallest eps met on the way [n]) of a constant / checker / image texture at the points p."""
+    return texture_value3(rec, tex, p)[0:2]
+
+
+def albedo_value3(rec, mats, p, hit=None, fault=None):
     """What the feature pass calls the albedo: Lambertian / Isotropic the texture, Metal its colour, Dielectric 1,
-    DiffuseLight brightness * texture."""
-    out, eps = np.zeros((len(p), 3)), np.full(len(p), np.inf)
+    DiffuseLight brightness * texture -- with eps and the allowance of texture_value3 (a light's times its brightness)."""
+    out, eps, allow = np.zeros((len(p), 3)), np.full(len(p), np.inf), np.zeros(len(p))
     hit = np.ones(len(p), bool) if hit is None else hit
     for m in np.unique(mats[hit]):
         at = hit & (mats == m)
@@ -530,37 +636,66 @@ def albedo_value(rec, mats, p, hit=None):
         elif r[0] == "dielectric":
             out[at] = 1.0
         else:
-            v, e = texture_value(rec, r[1], p[at])
-            out[at], eps[at] = (r[2] * v if r[0] == "light" else v), e
-    return out, eps
+            v, e, a = texture_value3(rec, r[1], p[at], fault)
+            out[at], eps[at], allow[at] = (r[2] * v if r[0] == "light" else v), e, (r[2] * a if r[0] == "light" else a)
+    return out, eps, allow
 
 
-def feature_reference(rec, world, cam, nx, ny, grid, fault=None):
+def albedo_value(rec, mats, p, hit=None):
+    return albedo_value3(rec, mats, p, hit)[0:2]
+
+
+def feature_reference(rec, world, cam, nx, ny, grid, fault=None, allowance=False, image_fault=None):
     """The albedo / normal / depth planes of RTG_FLAG_FEATURES in float64 from the camera block: (planes [ny, nx, 7], usable
     [ny, nx]).  Rays: pixel (x, row), y = ny - 1 - row, cell centres (i + 0.5) / g of a g x g grid, from the camera origin, at
-    mid exposure; a plane is the mean over the g * g rays, a miss counting as zero."""
+    mid exposure; a plane is the mean over the g * g rays, a miss counting as zero.  allowance=True: also the albedo allowance
+    per pixel [ny, nx] (the mean of the rays' allowances of texture_value3) and, per pixel, whether a ray met an image texture on
+    a triangle."""
     prims = primitives(rec, world)
     v3 = lambda a: np.array([a[0], a[1], a[2]], dtype=F)
     origin, llc, hor, ver = v3(cam.origin), v3(cam.lower_left_corner), v3(cam.horizontal), v3(cam.vertical)
     time = float(cam.exposure_start) + 0.5 * (float(cam.exposure_end) - float(cam.exposure_start))
     x, row = np.meshgrid(np.arange(nx, dtype=F), np.arange(ny, dtype=F))
     y = ny - 1 - row
-    acc, usable = np.zeros((ny * nx, 7)), np.ones(ny * nx, bool)
+    acc, usable, allow, on_tri = np.zeros((ny * nx, 7)), np.ones(ny * nx, bool), np.zeros(ny * nx), np.zeros(ny * nx, bool)
+    kinds = np.array([pr.kind == "tri" for pr in prims] + [False])
     for j in range(grid):
         for i in range(grid):
             u, v = ((x + (i + 0.5) / grid) / nx).ravel(), ((y + (j + 0.5) / grid) / ny).ravel()
             d = llc + u[:, None] * hor + v[:, None] * ver - origin
             h = closest_hit(prims, np.broadcast_to(origin, d.shape), d, np.full(len(d), time), fault=fault)
             hit = h["hit"]
-            alb, eps = albedo_value(rec, h["material"], h["p"], hit)
+            alb, eps, alw = albedo_value3(rec, h["material"], h["p"], hit, image_fault)
             usable &= h["margin"] > MARGIN
             usable &= ~hit | (eps > TOL_P)
             acc += np.where(hit[:, None], np.concatenate([alb, h["n"], h["t"][:, None]], axis=1), 0.0)
-    return (acc / (grid * grid)).reshape(ny, nx, 7), usable.reshape(ny, nx)
+            allow += np.where(hit, alw, 0.0)
+            on_tri |= hit & kinds[h["prim"]] & _shows_image(rec, h["material"], hit)
+    planes, usable = (acc / (grid * grid)).reshape(ny, nx, 7), usable.reshape(ny, nx)
+    if allowance:
+        return planes, usable, (allow / (grid * grid)).reshape(ny, nx), on_tri.reshape(ny, nx)
+    return planes, usable
 
 
-def compare_planes(ref, usable, albedo, normal, depth, what):
-    da = float(np.abs(albedo.astype(F) - ref[..., 0:3])[usable].max())
+def _has_image(rec, tex):
+    r = rec.textures[tex]
+    return r[0] == "image" or (r[0] == "checker" and (_has_image(rec, r[1]) or _has_image(rec, r[2])))
+
+
+def _shows_image(rec, mats, hit):
+    """per ray: the material's texture is an image or a checker that holds one"""
+    out = np.zeros(len(mats), bool)
+    for m in np.unique(mats[hit]):
+        r = rec.materials[int(m)]
+        if r[0] in ("lambertian", "isotropic", "light") and _has_image(rec, r[1]):
+            out |= hit & (mats == m)
+    return out
+
+
+def compare_planes(ref, usable, albedo, normal, depth, what, allow=None):
+    """allow [ny, nx]: the albedo allowance per pixel of feature_reference (image textures), beyond TOL_N"""
+    da = np.abs(albedo.astype(F) - ref[..., 0:3])
+    da = float((da if allow is None else np.maximum(da - allow[..., None], 0.0))[usable].max())
     dn = float(np.abs(normal.astype(F) - ref[..., 3:6])[usable].max())
     z = ref[..., 6]
     dz = float((np.abs(depth.astype(F) - z) / np.where(z > 0, z, 1.0))[usable].max())

@@ -6,7 +6,8 @@ normal without renormalising, LinearMove leaving p where the inner object put it
 A graph is a list of GROUPS (mesh_cases.py makes them beside the builder calls): {"tri": [m, 3, 3] float32 vertices, "chain":
 ((kind, parameter), ...) outermost first, "sign": +1 / -1, "mat": material id}.
 
-closest_hit64   geometry in float64: per triangle the plane crossing t = n.(v0 - o) / n.d with n = e1 x e2 and the barycentric
+closest_hit64   physics_ref.closest_hit over the groups' triangles (its triangle branch is the statement; this module keeps the
+                name and the description): geometry in float64: per triangle the plane crossing t = n.(v0 - o) / n.d with n = e1 x e2 and the barycentric
                 coordinates by Cramer's rule on the Gram matrix of (e1, e2) -- not Moeller-Trumbore's cross products; the
                 unit normal is n / |n| in float64.
                 Per ray the conditioning margin is the smallest of: the barycentric distances |u|, |v|, |1 - u - v|;
@@ -42,51 +43,17 @@ TOL_T, TOL_P, TOL_N = 4 * WORST_T, 4 * WORST_P, 4 * WORST_N
 MIN_HIT_SHARE, MIN_MISS_SHARE = 0.25, 0.10
 
 
+def prims_of(groups):
+    """The groups as physics_ref primitives: one Prim("tri", ...) per triangle, in order."""
+    return [PR.Prim("tri", (tri[0], tri[1], tri[2]), g["mat"], tuple(g["chain"]), g["sign"]) for g in groups for tri in np.asarray(g["tri"], F)]
+
+
 def closest_hit64(groups, o, d, time, t_near=T_NEAR):
-    """dict of hit, t, p, n, material, triangle (a running number over the groups in order, -1 on a miss) and margin."""
-    o, d, time = np.asarray(o, F), np.asarray(d, F), np.asarray(time, F)
-    n = len(o)
-    best, second = np.full(n, np.inf), np.full(n, np.inf)
-    bp, bn, bm, bi = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, np.uint32), np.full(n, -1, np.int64)
-    dlen = np.sqrt(_dot(d, d))
-    size = np.maximum(1.0, np.sqrt(_dot(o, o)))
-    seen = []
-    number = 0
-    with np.errstate(all="ignore"):
-        for g in groups:
-            lo, ld = _to_local(g["chain"], o, d, time)
-            for tri in np.asarray(g["tri"], F):
-                v0, e1, e2 = tri[0], tri[1] - tri[0], tri[2] - tri[0]
-                nn = np.cross(e1, e2)
-                den = ld @ nn
-                tt = ((v0 - lo) @ nn) / den
-                ts = np.where(np.isfinite(tt), tt, 0.0)
-                q = lo + ts[:, None] * ld - v0
-                a11, a12, a22 = e1 @ e1, e1 @ e2, e2 @ e2
-                b1, b2 = q @ e1, q @ e2
-                gram = a11 * a22 - a12 * a12
-                u, v = (b1 * a22 - b2 * a12) / gram, (b2 * a11 - b1 * a12) / gram
-                inside = (u >= 0) & (v >= 0) & (u + v <= 1)
-                t = np.where(np.isfinite(tt) & (tt >= t_near) & inside, tt, np.inf)
-                bary = np.minimum(np.minimum(np.abs(u), np.abs(v)), np.abs(1.0 - u - v))
-                detm = np.abs(den) / (np.sqrt(a11) * np.sqrt(a22) * np.sqrt(_dot(ld, ld)))
-                rootm = np.abs(tt - t_near) * dlen / size
-                m = np.where(np.isfinite(tt), np.where(tt >= 0, np.minimum(np.minimum(bary, detm), rootm), rootm), detm)
-                front = np.where(np.isfinite(tt), tt, -np.inf)
-                pl = lo + ts[:, None] * ld
-                nl = np.broadcast_to(nn / np.sqrt(nn @ nn), (n, 3))
-                pw, nw = _to_world(g["chain"], pl, g["sign"] * nl)
-                better = t < best
-                second = np.where(better, best, np.minimum(second, t))
-                best = np.where(better, t, best)
-                bp[better], bn[better], bm[better], bi[better] = pw[better], nw[better], g["mat"], number
-                seen.append((front, m))
-                number += 1
-        hit = np.isfinite(best)
-        margin = np.where(np.isfinite(second), (second - best) / np.abs(best), np.inf)
-        for front, m in seen:
-            margin = np.where(front <= best, np.minimum(margin, m), margin)
-    return {"hit": hit, "t": np.where(hit, best, 0.0), "p": bp, "n": bn, "material": bm, "triangle": bi, "margin": margin}
+    """dict of hit, t, p, n, material, triangle (a running number over the groups in order, -1 on a miss) and margin:
+    physics_ref.closest_hit over the groups' triangles -- the one statement of the triangle."""
+    ref = PR.closest_hit(prims_of(groups), o, d, time, t_near=t_near)
+    ref["triangle"] = ref["prim"]
+    return ref
 
 
 # ---- the float32 side on the CPU ----------------------------------------------------------------------------------------------
