@@ -35,7 +35,8 @@
  * refuses as a whole, with the builder unchanged: a NULL argument, an index >= n_vertices, any triangle rtg_object_triangle would
  * refuse, n_triangles == 0 (RTG_ERR_EMPTY_BVH's message) or sah > 1.
  *
- * Per-vertex normals and UVs are not part of this header: textures are functions of p and work on a mesh as they stand.  A
+ * Per-vertex normals and UVs are not part of this header: textures are functions of p and work on a mesh as they stand;
+ * rtiow_gpu_surface.h adds them (rtg_object_triangle_attr, rtg_object_mesh_attr) and textures that follow the surface.  A
  * DiffuseLight on a triangle emits, and is found by scattered rays at full weight; scene option light_sampling never samples it.
  *
  * Which kernels.  A scene that holds a triangle is a full-feature scene: camera frames render on the full-feature ray-pool

@@ -686,6 +686,9 @@ RAYS_PER_PIXEL, RAYS_PER_SAMPLE = 0, 1
 IMAGE_SYMBOLS = ["texture_image", "debug_texture_host", "debug_texture", "debug_atan2f_host"]
 # include/rtiow_gpu_mesh.h: triangles and meshes (not part of ABI_SYMBOLS either: the oracle has no triangle)
 MESH_SYMBOLS = ["object_triangle", "object_mesh", "debug_triangle_host"]
+# include/rtiow_gpu_surface.h: per-vertex normals and UVs, surface-mapped textures (not part of ABI_SYMBOLS either)
+SURFACE_SYMBOLS = ["object_triangle_attr", "object_mesh_attr", "texture_surface", "debug_triangle_attr_host", "debug_hit_surface"]
+FEAT_SURFACE = 2048   # flat_scene.h: the flattened program holds a triangle with per-vertex normals or UVs
 
 
 class ImageParams(C.Structure):
@@ -798,6 +801,12 @@ class Backend:
         f("object_triangle", C.c_uint32, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_uint32])
         f("object_mesh", C.c_uint32, [C.c_void_p, c_f32p, C.c_size_t, c_u32p, C.c_size_t, C.c_uint32, C.c_uint32])
         f("debug_triangle_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, C.c_float, c_f32p])
+        # include/rtiow_gpu_surface.h (SURFACE_SYMBOLS)
+        f("object_triangle_attr", C.c_uint32, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_uint32])
+        f("object_mesh_attr", C.c_uint32, [C.c_void_p, c_f32p, C.c_size_t, c_u32p, C.c_size_t, c_f32p, c_f32p, C.c_uint32, C.c_uint32])
+        f("texture_surface", C.c_uint32, [C.c_void_p, C.c_uint32])
+        f("debug_triangle_attr_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, C.c_uint32, c_f32p, C.c_float, c_f32p])
+        f("debug_hit_surface", C.c_int, [C.c_void_p, C.c_size_t, c_f32p, C.c_uint64, C.c_float, c_f32p, c_u32p])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -938,6 +947,20 @@ class Backend:
                                              out.ctypes.data_as(c_f32p)))
         return out
 
+    def triangle_attr_host(self, tri9, attr15, has, rays8, t_min=0.001):
+        """rtg_debug_triangle_attr_host (include/rtiow_gpu_surface.h): n (triangle, ray) pairs -- tri9 [n, 9]; attr15 [n, 15] =
+        n0, n1, n2, uv0, uv1, uv2; has: bit 0 use the normals, bit 1 use the UVs; rays8 [n, 8] -- through the functions the
+        kernels call, on the host.  [n, 10] = hit, t, p, n, tu, tv; zeros on a miss (triangle.hit + triangle.shade define it)."""
+        tri9 = np.ascontiguousarray(tri9, dtype=np.float32).reshape(-1, 9)
+        attr15 = np.ascontiguousarray(attr15, dtype=np.float32).reshape(-1, 15)
+        rays8 = np.ascontiguousarray(rays8, dtype=np.float32).reshape(-1, 8)
+        if len(tri9) != len(rays8) or len(tri9) != len(attr15):
+            raise ValueError("triangle_attr_host: one ray and one attribute row per triangle")
+        out = np.empty((len(tri9), 10), dtype=np.float32)
+        self.check(self._debug_triangle_attr_host(len(tri9), tri9.ctypes.data_as(c_f32p), attr15.ctypes.data_as(c_f32p), int(has),
+                                                  rays8.ctypes.data_as(c_f32p), float(t_min), out.ctypes.data_as(c_f32p)))
+        return out
+
 
 class Builder:
     """Scene under construction.  One method per reference constructor."""
@@ -978,6 +1001,11 @@ class Builder:
             raise ValueError("an image is [h, w, 3]")
         p = params if isinstance(params, ImageParams) else ImageParams.new(params)
         return self.be.check_id(self.be._texture_image(self.h, C.byref(p), img.shape[1], img.shape[0], img.ctypes.data_as(c_f32p)))
+
+    def surface(self, texture):
+        """rtg_texture_surface (include/rtiow_gpu_surface.h): `texture` evaluated at a hit's surface coordinates (tu, tv, 0)
+        instead of p.  For lambertian() and diffuse_light() only, and only on triangles with UVs."""
+        return self.be.check_id(self.be._texture_surface(self.h, texture))
 
     def texture_host(self, texture, p):
         """rtg_debug_texture_host: the texture's value at the points p [n, 3] on the host (image and constant textures)."""
@@ -1134,11 +1162,30 @@ class Builder:
         """rtg_object_triangle (include/rtiow_gpu_mesh.h): an ordinary object id; counter-clockwise is the front face."""
         return self.be.check_id(self.be._object_triangle(self.h, _f3(v0), _f3(v1), _f3(v2), material))
 
-    def mesh(self, vertices, indices, material, sah=False):
+    def triangle_attr(self, v0, v1, v2, material, normals=None, uvs=None):
+        """rtg_object_triangle_attr (include/rtiow_gpu_surface.h): normals [3, 3] and / or uvs [3, 2] of v0, v1, v2; with both
+        None it is triangle()."""
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(9)
+        t = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(6)
+        return self.be.check_id(self.be._object_triangle_attr(self.h, _f3(v0), _f3(v1), _f3(v2),
+                                                              None if n is None else n.ctypes.data_as(c_f32p),
+                                                              None if t is None else t.ctypes.data_as(c_f32p), material))
+
+    def mesh(self, vertices, indices, material, sah=False, normals=None, uvs=None):
         """rtg_object_mesh: vertices [n, 3] float32, indices [m, 3] uint32 (triangle.icosphere / box / grid / load_obj make
-        them) -> the m triangle objects and one Bvh object over them (sah: the SAH builder); returns the Bvh's id."""
+        them) -> the m triangle objects and one Bvh object over them (sah: the SAH builder); returns the Bvh's id.
+        normals [n, 3] / uvs [n, 2] (triangle.icosphere_attr / vertex_normals / load_obj_attr make them): rtg_object_mesh_attr
+        (include/rtiow_gpu_surface.h); with both None, today's call."""
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         ix = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        if normals is not None or uvs is not None:
+            nn = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            uv = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 2)
+            if (nn is not None and len(nn) != len(v)) or (uv is not None and len(uv) != len(v)):
+                raise ValueError("mesh: one normal and one UV per vertex")
+            return self.be.check_id(self.be._object_mesh_attr(self.h, v.ctypes.data_as(c_f32p), len(v), ix.ctypes.data_as(c_u32p), len(ix),
+                                                              None if nn is None else nn.ctypes.data_as(c_f32p),
+                                                              None if uv is None else uv.ctypes.data_as(c_f32p), material, int(sah)))
         return self.be.check_id(self.be._object_mesh(self.h, v.ctypes.data_as(c_f32p), len(v), ix.ctypes.data_as(c_u32p), len(ix),
                                                      material, int(sah)))
 
@@ -1575,6 +1622,16 @@ class Scene:
         mat = np.zeros(n, dtype=np.uint32)
         self.be.check(self.be._debug_hit_top(self.h, n, rays.ctypes.data_as(c_f32p), seed, t_near,
                                              out.ctypes.data_as(c_f32p), mat.ctypes.data_as(c_u32p)))
+        return out, mat
+
+    def debug_hit_surface(self, rays, seed=1, t_near=0.001):
+        """rtg_debug_hit_surface (include/rtiow_gpu_surface.h): debug_hit_top with (tu, tv) behind the normal.  ([n, 10], mat)"""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
+        n = rays.shape[0]
+        out = np.zeros((n, 10), dtype=np.float32)
+        mat = np.zeros(n, dtype=np.uint32)
+        self.be.check(self.be._debug_hit_surface(self.h, n, rays.ctypes.data_as(c_f32p), seed, t_near,
+                                                 out.ctypes.data_as(c_f32p), mat.ctypes.data_as(c_u32p)))
         return out, mat
 
     def debug_texture(self, texture, p):

@@ -71,6 +71,14 @@ enum Op : uint32_t {
                   //      widen their record classes, whose range ends at OP_SEG).  The lean pool, pool-2 and lean query kernels and
                   //      every instantiation without the bit hold no TRI case and are never launched on a program with FEAT_TRI
                   //      (rtg_launch.inc launch_slice / launch_full_pool, rtg_query.inc, rtg_rays.inc).
+                  //      Only in programs with FEAT_SURFACE (include/rtiow_gpu_surface.h): a triangle with per-vertex normals and / or
+                  //      UVs carries F_TRI_NORMALS / F_TRI_UVS and THREE data records; the TRI steps over all of them (pc += 4):
+                  //        OP_EXT  lo = (e2.x, e2.y, e2.z, N.x)       hi = (N.y, N.z, n0.x, OP_EXT)     (word 6 of the plain data record)
+                  //        OP_EXT  lo = (n0.y, n0.z, n1.x, n1.y)      hi = (n1.z, n2.x, n2.y, OP_EXT)
+                  //        OP_EXT  lo = (n2.z, u0, v0, u1)            hi = (v1, u2, v2, OP_EXT)
+                  //      n0 .. n2 the vertex normals as given, (u0, v0) .. (u2, v2) the vertex UVs; the words of an attribute the
+                  //      triangle does not have are +0.  A triangle with neither keeps its two records, word for word.  Walks that
+                  //      only want t (boundary queries, occlusion) read the first data record alone and take the same step.
 };
 
 // ---- the list level, hoisted (pool-2 kernel, rt_pool2.h) -------------------------------------------------------------------
@@ -106,6 +114,9 @@ struct P2Table {
 constexpr uint32_t F_TRANSLATE = 1u << 8;   // SPHERE: origin -= off on the way in, p += off on the way out
 constexpr uint32_t F_FLIP = 1u << 9;        // SPHERE/RECT: normal = -normal (odd number of FlipNormals)
 constexpr uint32_t F_AXIS_SHIFT = 10;       // RECT: bits 10-11 = orthogonal axis (0/1/2)
+constexpr uint32_t F_TRI_NORMALS = 1u << 10;  // TRI (the bits are RECT's axis bits): per-vertex normals in its data records, four records in all
+constexpr uint32_t F_TRI_UVS = 1u << 11;      // TRI: per-vertex UVs in its data records, four records in all
+constexpr uint32_t F_TRI_ATTR = F_TRI_NORMALS | F_TRI_UVS;
 constexpr uint32_t F_UNDER_BVH = 1u << 12;  // MEDIUM: lives below a Bvh node (hit-merge rule of bvh.rs:104-112)
 constexpr uint32_t F_BVH_ROOT = 1u << 13;   // BOX: root of an outermost Bvh (a Bvh not nested below another Bvh)
 constexpr uint32_t F_GENERAL_BOUNDARY = 1u << 14;  // MEDIUM: the boundary is an object graph (several records), not one primitive
@@ -133,13 +144,18 @@ constexpr int MAX_DEEP_XFORM_DEPTH = 32;  // ... and the general walk's (FEAT_DE
 constexpr int MAX_MEDIUM_NESTING = 3;     // media inside the boundary of a medium inside ...: levels the general walk follows
 constexpr int MAX_SAVE_NESTING = 4;       // OP_SAVE .. OP_MERGE pairs inside one another
 
-// Material record, 32 bytes (two uint4): lo = (c.r, c.g, c.b, param) hi = (texture, -, -, kind|texkind<<8)
+// Material record, 32 bytes (two uint4): lo = (c.r, c.g, c.b, param) hi = (texture, -, -, kind|texkind<<8|MAT_SURFACE)
+//   MAT_SURFACE (include/rtiow_gpu_surface.h rtg_texture_surface): the texture is evaluated at the hit's surface coordinates
+//   (tu, tv, 0) instead of p; `texture` and texkind are the CHILD's.  Lambertian and DiffuseLight only.
 //   Lambertian / Isotropic: c = albedo when the texture is constant, else `texture` indexes tex[]
 //   Metal: c = albedo, param = fuzz;  Dielectric: param = ref_idx
 //   DiffuseLight: c = emission when constant, param = brightness
 enum MatKind : uint32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_DIFFUSE_LIGHT = 3, MAT_ISOTROPIC = 4 };
 enum TexKind : uint32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_PERLIN = 2, TEX_IMAGE = 3 };
 constexpr uint32_t TEX_EXT = 4;  // host side only (HostTexture::kind): the slot of an image's continuation record; no handle names it
+constexpr uint32_t TEX_SURFACE = 5;  // host side only: rtg_texture_surface(child), t0 = child.  Its slot in tex[] is a black constant no
+                                     // record refers to: a material built on it carries the child's id and kind and MAT_SURFACE
+constexpr uint32_t MAT_SURFACE = 1u << 16;  // material record hi.w, above kind and texkind
 // Texture record, 32 bytes: lo = (r, g, b, scale) hi = (t0, t1, -, kind)
 // TEX_IMAGE (include/rtiow_gpu_image.h; not in the reference, whose Texture is a closure): TWO records and a run of texels.
 //   record i     lo = (w, h, flags, first)   hi = (-, -, -, TEX_IMAGE)    flags: rt_image.h IMG_*; first = PACKET index into tex[]
@@ -175,6 +191,8 @@ constexpr uint32_t FEAT_DEEP_ONE_LEVEL = 512u;     // no medium inside a medium'
 constexpr int DEEP_FEW_WRAPPERS = 8;
 constexpr uint32_t FEAT_TRI = 1024u;   // TRI present (include/rtiow_gpu_mesh.h): never a lean program, no hoisted segment, no second program; walked by the
                                        // FEAT_TRI / TRI instantiations of the one-lane family, the full-feature pool kernel and the lock-step kernel
+constexpr uint32_t FEAT_SURFACE = 2048u; // a TRI with F_TRI_NORMALS / F_TRI_UVS present (include/rtiow_gpu_surface.h): always with FEAT_TRI; walked by the
+                                       // FEAT_SURFACE / SURF instantiations of the same three kernel families, which carry (tu, tv) beside the hit normal
 constexpr uint32_t FEAT_BRIGHT_ALBEDO = 64u; // an albedo component may exceed 1 (a constant in (1, 4], or Perlin turbulence, <= 3.47): the pool
                                             // kernels then need max_bounces <= 63 for the strength to stay finite
 constexpr uint32_t FEAT_WIDE_ALBEDO = 32u;  // an albedo component outside [0, 4]: path strength may overflow or change sign, so the pool

@@ -22,14 +22,15 @@ struct FeatureBufs {
   uint32_t* blk_u32;  // per block of the feature kernel: traced, missed
 };
 
-// what a material returns as its colour at p: the attenuation of scatter(), emitted() for a light (material.rs:55-128)
+// what a material returns as its colour at the hit: the attenuation of scatter(), emitted() for a light (material.rs:55-128);
+// a surface-mapped texture (MAT_SURFACE) is read at the hit's (tu, tv, 0) as color() reads it
 template <uint32_t FEAT>
-RT_DEV V3 feature_albedo(const DevScene& sc, uint32_t mat, V3 p) {
-  const uint4 mlo = sc.mat[2 * mat], mhi = sc.mat[2 * mat + 1];
+RT_DEV V3 feature_albedo(const DevScene& sc, const HitRecOf<FEAT>& h) {
+  const uint4 mlo = sc.mat[2 * h.mat], mhi = sc.mat[2 * h.mat + 1];
   const uint32_t kind = mhi.w & 0xffu;
   if (kind == MAT_METAL) return mk(u2f(mlo.x), u2f(mlo.y), u2f(mlo.z));
   if (kind == MAT_DIELECTRIC) return splat(1.f);
-  const V3 t = material_texture<FEAT>(sc, mlo, mhi, p);
+  const V3 t = material_texture<FEAT>(sc, mlo, mhi, texture_point(h, mhi));
   return kind == MAT_DIFFUSE_LIGHT ? smul(u2f(mlo.w), t) : t;
 }
 
@@ -62,12 +63,12 @@ __global__ __launch_bounds__(256) void features_kernel(DevScene sc, DevCamera ca
         SampleRng rng;
         rng.init(((uint64_t)P.seed_hi << 32) | P.seed_lo, y * P.nx + x, 0);
         rng.set_event(1);
-        HitRec h;
+        HitRecOf<FEAT> h;
         Counts cnt = {0, 0, 0, 0};
         V3 ha = mk(0.f, 0.f, 0.f), hn = mk(0.f, 0.f, 0.f);
         float hz = 0.f;
         if (hit_top<FEAT, false>(sc, cam.origin, d, time, P.t_near, rng, h, cnt)) {
-          ha = feature_albedo<FEAT>(sc, h.mat, h.p), hn = h.n, hz = h.t;
+          ha = feature_albedo<FEAT>(sc, h), hn = h.n, hz = h.t;
           any = true;
         }
         a = vadd(a, ha), n = vadd(n, hn), z = z + hz;

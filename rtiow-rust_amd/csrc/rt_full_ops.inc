@@ -5,6 +5,9 @@
 // RT_DEFER_HIT (defined by the includer) = 1: a hit is kept as (best, record pc | prism face | "textured" bit 3) in `hmat` -- no
 // point, no normal, nothing for a POP to transform; the shade pass rebuilds the record from the ray and t, replaying the wrappers
 // around the winning record (rt_pool_full.h rebuild_hit).  0: the hit record (hp, hn, material) rides in registers.
+// SURF (the includer's template parameter): attribute triangles (FEAT_SURFACE).  Under RT_DEFER_HIT only the record step differs;
+// without it the TRI case also writes the includer's h_tu / h_tv.  No other record resets them: only a material with MAT_SURFACE
+// reads them, and the builder accepts such a material on triangles with UVs alone, which write them when they win.
   // ConstantMedium::hit once both boundary queries hit at t1, t2 (object.rs:553-574): clamp to the range, one draw from the
   // event's stream, exponential free path.  `med_lo / med_hi` = the MEDIUM record (density, material, flags).
   auto medium_between = [&](float t1, float t2, const uint4 med_lo, const uint4 med_hi, [[maybe_unused]] const uint32_t med_pc, const V3 o, const V3 d, float& best, V3& hp,
@@ -140,12 +143,21 @@
           hmat = pc | ((cur_hi.w >> 16) & 8u);
           best = t, nhits++;
 #else
-          hp = vadd(o, smul(t, d)), hn = tri_rec_normal(cur_hi, x_lo, RT_FETCH_HI(pc + RSZ)), hmat = cur_hi.z | ((cur_hi.w & F_TEXTURED) << 12);
+          hp = vadd(o, smul(t, d)), hmat = cur_hi.z | ((cur_hi.w & F_TEXTURED) << 12);
+          if constexpr (SURF) {  // include/rtiow_gpu_surface.h: the shading normal, and (tu, tv) beside hp / hn (the includer's h_tu, h_tv)
+            h_tu = 0.f, h_tv = 0.f;
+            if (cur_hi.w & F_TRI_ATTR)
+              hn = tri_rec_shade(cur_lo, cur_hi, x_lo, RT_FETCH_HI(pc + RSZ), RT_FETCH_LO(pc + 2u * RSZ), RT_FETCH_HI(pc + 2u * RSZ), RT_FETCH_LO(pc + 3u * RSZ),
+                                 RT_FETCH_HI(pc + 3u * RSZ), o, d, h_tu, h_tv);
+            else hn = tri_rec_normal(cur_hi, x_lo, RT_FETCH_HI(pc + RSZ));
+          } else {
+            hn = tri_rec_normal(cur_hi, x_lo, RT_FETCH_HI(pc + RSZ));
+          }
           best = t, tag = depth, nhits++;
 #endif
         }
       }
-      pc += 2u * RSZ;  // (its data record)
+      pc += (SURF && (cur_hi.w & F_TRI_ATTR)) ? 4u * RSZ : 2u * RSZ;  // (its data record; an attribute triangle's three: flat_scene.h)
     } else if (op == OP_PUSH) {
       const uint32_t kind = (cur_hi.w >> F_KIND_SHIFT) & 7u;
       if (RT_REG_STACK0 && depth == 0u) {  // level 0 rides in registers: every wrapper of the reference's scenes is an outermost one

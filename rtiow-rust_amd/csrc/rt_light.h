@@ -25,7 +25,7 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
     float t;
     constexpr int XD = (FEAT & FEAT_DEEP_FEW_WRAPPERS) ? DEEP_FEW_WRAPPERS : MAX_DEEP_XFORM_DEPTH;
     constexpr int ML = (FEAT & FEAT_DEEP_ONE_LEVEL) ? 1 : MAX_MEDIUM_NESTING;
-    return walk_deep<0, COUNT, XD, ML, true, (FEAT & FEAT_TRI) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, t_max, rng, nullptr, t, cnt);
+    return walk_deep<0, COUNT, XD, ML, true, (FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, t_max, rng, nullptr, t, cnt);
   }
   V3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   int depth = 0;
@@ -81,7 +81,7 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
       if (COUNT) cnt.prim++;
       float t;
       if (tri_rec_hit_t(lo, hi, sc.lo[pc + 1], o, d, t_near, t_max, t)) return true;
-      pc += 2;  // (its data record)
+      pc += (FEAT & FEAT_SURFACE) ? tri_rec_step(hi) : 2u;  // (its data record; an attribute triangle's three)
       continue;
     }
     if ((FEAT & FEAT_XFORM) && op == OP_PUSH) {
@@ -116,11 +116,11 @@ RT_DEV bool occluded(const DevScene& sc, V3 o, V3 d, float time, float t_near, f
       float t1, t2;
       bool h1, h2 = false;
       if (hi.w & F_GENERAL_BOUNDARY) {
-        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
+        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
         h1 = b1.any != 0u, t1 = b1.t;
         if (COUNT) cnt.aabb += b1.n_aabb, cnt.prim += b1.n_prim;
         if (h1) {
-          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
+          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
           h2 = b2.any != 0u, t2 = b2.t;
           if (COUNT) cnt.aabb += b2.n_aabb, cnt.prim += b2.n_prim;
         }
@@ -169,7 +169,7 @@ RT_DEV V3 color_ls(const DevScene& sc, const LightTable& lt, V3 o, V3 d, float t
   V3 strength = splat(1.f);
   uint32_t bounces = 0;
   bool sampled_before = false;  // step 2 ran at the previous hit
-  HitRec hit;
+  HitRecOf<FEAT> hit;
   rng.set_event(1);
   while (hit_top<FEAT, COUNT>(sc, o, d, time, P.t_near, rng, hit, cnt)) {
     if (COUNT) cnt.shaded++;
@@ -177,7 +177,7 @@ RT_DEV V3 color_ls(const DevScene& sc, const LightTable& lt, V3 o, V3 d, float t
     const uint32_t kind = mhi.w & 0xffu;
     const float param = u2f(mlo.w);
     if (kind == MAT_DIFFUSE_LIGHT) {  // material.rs:108, :120-128
-      if (!(sampled_before && lt.sampled[hit.mat])) accum = vadd(accum, vmul(strength, smul(param, material_texture<FEAT>(sc, mlo, mhi, hit.p))));
+      if (!(sampled_before && lt.sampled[hit.mat])) accum = vadd(accum, vmul(strength, smul(param, material_texture<FEAT>(sc, mlo, mhi, texture_point(hit, mhi)))));
       bounces_out = bounces;
       return accum;
     }
@@ -186,7 +186,7 @@ RT_DEV V3 color_ls(const DevScene& sc, const LightTable& lt, V3 o, V3 d, float t
     bool scattered = true;
     sampled_before = false;
     if (kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC) {
-      att = material_texture<FEAT>(sc, mlo, mhi, hit.p);
+      att = material_texture<FEAT>(sc, mlo, mhi, texture_point(hit, mhi));
       if (bounces < P.max_bounces) {
         sampled_before = true;
         const float u0 = rng.gen_f32(), u1 = rng.gen_f32(), u2 = rng.gen_f32();

@@ -200,7 +200,11 @@ RT_DEV void full_push_finished(const QueueRsrc qr, uint32_t& s_count, uint32_t& 
 // 5 more VGPRs, paid only by scenes that need it.
 // TRI: the program may hold OP_TRI records (FEAT_TRI): the TRI cases of exec_op and rebuild_hit and the wider record classes are
 // compiled into these instantiations alone -- the others keep the code they had.
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false>
+// SURF (only with TRI): the program may hold attribute triangles (FEAT_SURFACE; include/rtiow_gpu_surface.h): four records each.  The
+// walk only steps further (exec_op under RT_DEFER_HIT keeps (t, record pc) as for every hit); rebuild_hit recomputes u, v from the
+// primitive-space ray it already has and returns the shading normal and (tu, tv), which the shade pass hands to a surface-mapped
+// texture in place of p.
+template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_pool(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -335,6 +339,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
   // outermost first) turn the ray into the one the primitive was tested with (object.rs:275-278, 357-361, 309-313, 505-508), the
   // primitive builds (p, normal) as its `hit` does, the wrappers take the record back out, innermost first (object.rs:279-282,
   // 365-369, 314-318, 249-252).  Same operands, same order: the same bits.
+  float s_tu = 0.f, s_tv = 0.f;  // SURF: the surface coordinates of the hit rebuild_hit rebuilt last
   auto rebuild_hit = [&](const uint32_t bpc, V3 ro, V3 rd, const float rtime, const float t, V3& p, V3& n, uint32_t& mat) {
     constexpr uint32_t NONE = 0xffffffffu;
     const uint32_t rpc = bpc & ~(RSZ - 1u);
@@ -380,7 +385,16 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
     } else if (r_op == OP_PRISM) {
       p = vadd(ro, smul(t, rd)), n = prism_normal(bpc & 7u);
     } else if (TRI && r_op == OP_TRI) {  // p = o + t d as Rect does, n = +-N from the record pair
-      p = vadd(ro, smul(t, rd)), n = tri_rec_normal(r_hi, RT_FETCH_LO(rpc + RSZ), RT_FETCH_HI(rpc + RSZ));
+      p = vadd(ro, smul(t, rd));
+      if constexpr (SURF) {  // ... or the interpolated normal and (tu, tv) of an attribute triangle, from the ray the test saw
+        s_tu = 0.f, s_tv = 0.f;
+        if (r_hi.w & F_TRI_ATTR)
+          n = tri_rec_shade(r_lo, r_hi, RT_FETCH_LO(rpc + RSZ), RT_FETCH_HI(rpc + RSZ), RT_FETCH_LO(rpc + 2u * RSZ), RT_FETCH_HI(rpc + 2u * RSZ),
+                            RT_FETCH_LO(rpc + 3u * RSZ), RT_FETCH_HI(rpc + 3u * RSZ), ro, rd, s_tu, s_tv);
+        else n = tri_rec_normal(r_hi, RT_FETCH_LO(rpc + RSZ), RT_FETCH_HI(rpc + RSZ));
+      } else {
+        n = tri_rec_normal(r_hi, RT_FETCH_LO(rpc + RSZ), RT_FETCH_HI(rpc + RSZ));
+      }
     } else {  // MEDIUM: object.rs:567-571
       p = vadd(ro, smul(t, rd)), n = mk(1.f, 0.f, 0.f);
     }
@@ -461,7 +475,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             const uint32_t m_off = load_const(&lc->mat_lds);
             if (m_off) mlo = s_mem[(m_off >> 4) + 2u * hm], mhi = s_mem[(m_off >> 4) + 2u * hm + 1u];
             else mlo = sc.mat[2 * hm], mhi = sc.mat[2 * hm + 1];
-            texval = material_texture<PASS_FEAT>(sc, mlo, mhi, p);  // = albedo / emission colour for constant textures
+            if constexpr (SURF) texval = material_texture<PASS_FEAT>(sc, mlo, mhi, (mhi.w & MAT_SURFACE) ? mk(s_tu, s_tv, 0.f) : p);
+            else texval = material_texture<PASS_FEAT>(sc, mlo, mhi, p);  // = albedo / emission colour for constant textures
           }
           strength = mk(SQ_LD_F(SQ_STRENGTH, j), SQ_LD_F(SQ_STRENGTH + 1, j), SQ_LD_F(SQ_STRENGTH + 2, j));
           bounces = SQ_LD_U(SQ_BOUNCES, j), s = SQ_LD_U(SQ_SAMPLE, j);

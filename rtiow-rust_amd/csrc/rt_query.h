@@ -24,7 +24,7 @@ __global__ __launch_bounds__(QUERY_GENERAL_BLOCK) void query_closest_kernel(DevS
   SampleRng rng;
   rng.init(((uint64_t)seed_hi << 32) | seed_lo, first + (uint32_t)i, 0);
   rng.set_event(1);
-  HitRec h;
+  HitRecOf<FEAT> h;
   Counts cnt = {0, 0, 0, 0};
   const bool hit = hit_top<FEAT, false>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t_min, rng, h, cnt);
   float* o = out + 8ull * i;

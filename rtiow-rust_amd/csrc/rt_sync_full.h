@@ -10,7 +10,7 @@
 
 namespace rtg {
 
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false>  // (TRI: as render_full_pool's)
+template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>  // (TRI, SURF: as render_full_pool's)
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_sync(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -55,6 +55,7 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
   uint32_t pc = 0;
   uint4 cur_lo = make_uint4(0, 0, 0, 0), cur_hi = make_uint4(0, 0, 0, OP_END);
   V3 hp = o, hn = o;
+  [[maybe_unused]] float h_tu = 0.f, h_tv = 0.f;  // SURF alone: the hit's surface coordinates, beside hp / hn from the hit to its SHADE phase
   uint32_t hmat = NO_HIT;
   uint32_t depth = 0, tag = 0, nhits = 0, root_hits = 0, ev_draws = 0;
   V3 sv_o = mk(0.f, 0.f, 0.f), sv_d = sv_o;  // level 0 of the transform stack (rt_full_ops.inc)
@@ -98,7 +99,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
         V3 texval = mk(0.f, 0.f, 0.f);
         if (hm != NO_HIT) {
           mlo = sc.mat[2 * hm], mhi = sc.mat[2 * hm + 1];
-          texval = material_texture<FEAT>(sc, mlo, mhi, p);
+          if constexpr (SURF) texval = material_texture<FEAT>(sc, mlo, mhi, (mhi.w & MAT_SURFACE) ? mk(h_tu, h_tv, 0.f) : p);
+          else texval = material_texture<FEAT>(sc, mlo, mhi, p);
         }
         const V3 sd = d;
         SampleRng rng;

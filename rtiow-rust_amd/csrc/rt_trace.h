@@ -81,6 +81,24 @@ struct HitRec {  // object.rs:61-71
   uint32_t mat;
 };
 
+// ... and, in the instantiations for programs with FEAT_SURFACE alone (include/rtiow_gpu_surface.h), the hit's surface
+// coordinates: a triangle's interpolated UVs, (0, 0) for a triangle without UVs and for every other primitive.
+struct HitRecS : HitRec {
+  float tu, tv;
+};
+template <bool SURF>
+struct HitRecPick {
+  typedef HitRec type;
+};
+template <>
+struct HitRecPick<true> {
+  typedef HitRecS type;
+};
+template <uint32_t FEAT>
+using HitRecOf = typename HitRecPick<(FEAT & FEAT_SURFACE) != 0u>::type;
+RT_DEV void hit_no_surface(HitRec&) {}
+RT_DEV void hit_no_surface(HitRecS& r) { r.tu = 0.f, r.tv = 0.f; }
+
 struct Counts {
   uint32_t aabb, prim, shaded, rays;
 };
@@ -137,6 +155,30 @@ RT_DEV bool tri_rec_hit_t(uint4 lo, uint4 hi, uint4 xlo, V3 o, V3 d, float t0, f
 RT_DEV V3 tri_rec_normal(uint4 hi, uint4 xlo, uint4 xhi) {  // N, or -N under an odd number of FlipNormals; two-sided like Rect
   const V3 n = mk(u2f(xlo.w), u2f(xhi.x), u2f(xhi.y));
   return (hi.w & F_FLIP) ? vneg(n) : n;
+}
+
+// An attribute triangle (flat_scene.h F_TRI_NORMALS / F_TRI_UVS): records in front of the next one, its own included
+RT_DEV uint32_t tri_rec_step(uint4 hi) { return (hi.w & F_TRI_ATTR) ? 4u : 2u; }
+// The shading normal and (tu, tv) of a hit on it, from the primitive-space ray: (lo, hi) the TRI record, (x, a, b) its three data
+// records.  rt_triangle.h tri_uv gives the u, v the accept test used, tri_shade the interpolation.
+RT_DEV V3 tri_rec_shade(uint4 lo, uint4 hi, uint4 xlo, uint4 xhi, uint4 alo, uint4 ahi, uint4 blo, uint4 bhi, V3 o, V3 d, float& tu, float& tv) {
+  float u, v;
+  tri_uv(Tri3{u2f(lo.x), u2f(lo.y), u2f(lo.z)}, Tri3{u2f(lo.w), u2f(hi.x), u2f(hi.y)}, Tri3{u2f(xlo.x), u2f(xlo.y), u2f(xlo.z)}, Tri3{o.x, o.y, o.z},
+         Tri3{d.x, d.y, d.z}, u, v);
+  const TriAttr a{Tri3{u2f(xhi.z), u2f(alo.x), u2f(alo.y)}, Tri3{u2f(alo.z), u2f(alo.w), u2f(ahi.x)}, Tri3{u2f(ahi.y), u2f(ahi.z), u2f(blo.x)},
+                  u2f(blo.y), u2f(blo.z), u2f(blo.w), u2f(bhi.x), u2f(bhi.y), u2f(bhi.z)};
+  const Tri3 n = tri_shade(u, v, a, Tri3{u2f(xlo.w), u2f(xhi.x), u2f(xhi.y)}, (hi.w & F_TRI_NORMALS) != 0u, (hi.w & F_TRI_UVS) != 0u, tu, tv);
+  const V3 r = mk(n.x, n.y, n.z);
+  return (hi.w & F_FLIP) ? vneg(r) : r;
+}
+// ... for a walk over the program in global memory (the one-lane family): writes rec.n, rec.tu, rec.tv
+RT_DEV void tri_rec_attr(const uint4* __restrict__ plo, const uint4* __restrict__ phi, uint32_t pc, uint4 lo, uint4 hi, uint4 xlo, V3 o, V3 d, HitRecS& rec) {
+  const uint4 xhi = phi[pc + 1];
+  if (hi.w & F_TRI_ATTR) {
+    rec.n = tri_rec_shade(lo, hi, xlo, xhi, plo[pc + 2], phi[pc + 2], plo[pc + 3], phi[pc + 3], o, d, rec.tu, rec.tv);
+  } else {
+    rec.n = tri_rec_normal(hi, xlo, xhi), rec.tu = 0.f, rec.tv = 0.f;
+  }
 }
 
 // object.rs:349-355
@@ -197,7 +239,8 @@ struct BoundaryHit {
   uint32_t any, n_aabb, n_prim;
 };
 // TRI: the stream may hold OP_TRI records (programs with FEAT_TRI); the instantiation without keeps the code it had
-template <bool TRI = false>
+// SURF: ... and attribute triangles (FEAT_SURFACE): only their step differs here
+template <bool TRI = false, bool SURF = false>
 __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __restrict__ prog_lo, const uint4* __restrict__ prog_hi,
                                                                 uint32_t first, uint32_t end_pc, V3 o, V3 d, float time,
                                                                 float t_lo, float t_hi) {
@@ -249,7 +292,7 @@ __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __r
       n_prim++;
       float t;
       if (tri_rec_hit_t(lo, hi, prog_lo[pc + 1], o, d, t_lo, best, t)) best = t, any = true;
-      pc += 2;  // (its data record)
+      pc += SURF ? tri_rec_step(hi) : 2u;  // (its data record; an attribute triangle's three)
     } else if (op == OP_PUSH) {
       const uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -292,9 +335,10 @@ __device__ __attribute__((noinline)) BoundaryHit boundary_hit_t(const uint4* __r
 // ANY (LEVEL 0, `rec` == null; rt_light.h occluded): an occlusion query over [t_lo, t_hi) -- returns at the first accepted hit,
 // t_out unset.  Its boundary queries are the ordinary closest-t ones.
 // TRI: the program may hold OP_TRI records (FEAT_TRI); the instantiations without keep the code they had.
-template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING, bool ANY = false, bool TRI = false>
+// SURF: ... and attribute triangles (FEAT_SURFACE): the hit record is HitRecS.
+template <int LEVEL, bool COUNT, int XD = MAX_DEEP_XFORM_DEPTH, int ML = MAX_MEDIUM_NESTING, bool ANY = false, bool TRI = false, bool SURF = false>
 __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t first, uint32_t end_pc, V3 o, V3 d, const float time,
-                                                    const float t_lo, const float t_hi, SampleRng& rng, HitRec* rec, float& t_out,
+                                                    const float t_lo, const float t_hi, SampleRng& rng, typename HitRecPick<SURF>::type* rec, float& t_out,
                                                     Counts& cnt) {
   V3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   float best = t_hi;
@@ -304,7 +348,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
   V3 so[XD], sd[XD];
   // OP_SAVE .. OP_MERGE: the hit in front of an And-with-medium leaf of a Bvh
   float sv_best[MAX_SAVE_NESTING];
-  HitRec sv_rec[MAX_SAVE_NESTING];
+  typename HitRecPick<SURF>::type sv_rec[MAX_SAVE_NESTING];
   int sv_tag[MAX_SAVE_NESTING];
   uint32_t sv_nhits[MAX_SAVE_NESTING], sv_root[MAX_SAVE_NESTING];
   bool sv_any[MAX_SAVE_NESTING];
@@ -343,6 +387,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
           if (hi.w & F_TRANSLATE) p = vadd(p, off);
           if (hi.w & F_FLIP) n = vneg(n);
           rec->t = t, rec->p = p, rec->n = n, rec->mat = hi.z;
+          hit_no_surface(*rec);
         }
         best = t, any = true, tag = depth, nhits++;
         if (ANY) return true;
@@ -357,6 +402,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
           V3 n = mk(axis == 0 ? 1.f : 0.f, axis == 1 ? 1.f : 0.f, axis == 2 ? 1.f : 0.f);
           if (hi.w & F_FLIP) n = vneg(n);
           rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = n, rec->mat = hi.z;
+          hit_no_surface(*rec);
         }
         best = t, any = true, tag = depth, nhits++;
         if (ANY) return true;
@@ -368,7 +414,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
       uint32_t face = 0;
       const uint32_t nh = prism_hit_t(lo, hi, o, d, t_lo, best, t, face);
       if (nh) {
-        if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = prism_normal(face), rec->mat = hi.z;
+        if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = prism_normal(face), rec->mat = hi.z, hit_no_surface(*rec);
         best = t, any = true, tag = depth, nhits += nh;
         if (ANY) return true;
       }
@@ -378,11 +424,15 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
       const uint4 xlo = sc.lo[pc + 1];
       float t;
       if (tri_rec_hit_t(lo, hi, xlo, o, d, t_lo, best, t)) {
-        if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]), rec->mat = hi.z;
+        if (rec) {
+          rec->t = t, rec->p = vadd(o, smul(t, d)), rec->mat = hi.z;
+          if constexpr (SURF) tri_rec_attr(sc.lo, sc.hi, pc, lo, hi, xlo, o, d, *rec);
+          else rec->n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]);
+        }
         best = t, any = true, tag = depth, nhits++;
         if (ANY) return true;
       }
-      pc += 2;  // (its data record)
+      pc += SURF ? tri_rec_step(hi) : 2u;  // (its data record; an attribute triangle's three)
     } else if (op == OP_PUSH) {
       uint32_t kind = (hi.w >> F_KIND_SHIFT) & 7u;
       so[depth] = o, sd[depth] = d;
@@ -427,14 +477,14 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
       float t1 = 0.f, t2 = 0.f;
       bool h1 = false, h2 = false;
       if (general) {
-        if constexpr (LEVEL < ML) h1 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI>(sc, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX, rng, nullptr, t1, cnt);
+        if constexpr (LEVEL < ML) h1 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI, SURF>(sc, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX, rng, nullptr, t1, cnt);
       } else {
         if (COUNT) cnt.prim++;
         h1 = prim_hit_t(blo, bhi, o, d, -F32_MAX, F32_MAX, t1);
       }
       if (h1) {
         if (general) {
-          if constexpr (LEVEL < ML) h2 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI>(sc, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX, rng, nullptr, t2, cnt);
+          if constexpr (LEVEL < ML) h2 = walk_deep<LEVEL + 1, COUNT, XD, ML, false, TRI, SURF>(sc, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX, rng, nullptr, t2, cnt);
         } else {
           if (COUNT) cnt.prim++;
           h2 = prim_hit_t(blo, bhi, o, d, t1 + 0.0001f, F32_MAX, t2);
@@ -449,7 +499,7 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
               float t = t1 + hit_distance / vlen(d);
               bool accept = !(hi.w & F_UNDER_BVH) || nhits == root_hits || !(best < t);  // merge rule: see hit_top
               if (accept) {
-                if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = mk(1.f, 0.f, 0.f), rec->mat = hi.z;
+                if (rec) rec->t = t, rec->p = vadd(o, smul(t, d)), rec->n = mk(1.f, 0.f, 0.f), rec->mat = hi.z, hit_no_surface(*rec);
                 best = t, any = true, tag = depth, nhits++;
                 if (ANY) return true;
               }
@@ -485,13 +535,13 @@ __device__ __attribute__((noinline)) bool walk_deep(const DevScene& sc, uint32_t
 // t_range.end; t_range.start is always t_near.  Returns Some/None, fills `rec` (world space).
 template <uint32_t FEAT, bool COUNT>
 RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, SampleRng& rng,
-                    HitRec& rec, Counts& cnt) {
+                    HitRecOf<FEAT>& rec, Counts& cnt) {
   if (COUNT) cnt.rays++;
   if (FEAT & FEAT_DEEP) {  // graph shapes only the general walk handles
     float t;
     constexpr int XD = (FEAT & FEAT_DEEP_FEW_WRAPPERS) ? DEEP_FEW_WRAPPERS : MAX_DEEP_XFORM_DEPTH;
     constexpr int ML = (FEAT & FEAT_DEEP_ONE_LEVEL) ? 1 : MAX_MEDIUM_NESTING;
-    return walk_deep<0, COUNT, XD, ML, false, (FEAT & FEAT_TRI) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, F32_MAX, rng, &rec, t, cnt);
+    return walk_deep<0, COUNT, XD, ML, false, (FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc, 0u, sc.n_prog, o, d, time, t_near, F32_MAX, rng, &rec, t, cnt);
   }
   V3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);  // aabb.rs:17, hoisted: depends on the ray only
   float best = F32_MAX;
@@ -535,6 +585,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
         if (hi.w & F_TRANSLATE) p = vadd(p, off);   // object.rs:279-282
         if (hi.w & F_FLIP) n = vneg(n);             // object.rs:249-252
         rec.t = t, rec.p = p, rec.n = n, rec.mat = hi.z;
+        hit_no_surface(rec);
         best = t, any = true, tag = depth, nhits++;
       }
       pc++;
@@ -548,6 +599,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
         V3 n = mk(axis == 0 ? 1.f : 0.f, axis == 1 ? 1.f : 0.f, axis == 2 ? 1.f : 0.f);
         if (hi.w & F_FLIP) n = vneg(n);
         rec.t = t, rec.p = vadd(o, smul(t, d)), rec.n = n, rec.mat = hi.z;
+        hit_no_surface(rec);
         best = t, any = true, tag = depth, nhits++;
       }
       pc++;
@@ -560,6 +612,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       const uint32_t nh = prism_hit_t(lo, hi, o, d, t_near, best, t, face);
       if (nh) {
         rec.t = t, rec.p = vadd(o, smul(t, d)), rec.n = prism_normal(face), rec.mat = hi.z;
+        hit_no_surface(rec);
         best = t, any = true, tag = depth, nhits += nh;
       }
       pc++;
@@ -570,10 +623,12 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       const uint4 xlo = sc.lo[pc + 1];
       float t;
       if (tri_rec_hit_t(lo, hi, xlo, o, d, t_near, best, t)) {
-        rec.t = t, rec.p = vadd(o, smul(t, d)), rec.n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]), rec.mat = hi.z;
+        rec.t = t, rec.p = vadd(o, smul(t, d)), rec.mat = hi.z;
+        if constexpr ((FEAT & FEAT_SURFACE) != 0u) tri_rec_attr(sc.lo, sc.hi, pc, lo, hi, xlo, o, d, rec);  // include/rtiow_gpu_surface.h
+        else rec.n = tri_rec_normal(hi, xlo, sc.hi[pc + 1]);
         best = t, any = true, tag = depth, nhits++;
       }
-      pc += 2;  // (its data record)
+      pc += (FEAT & FEAT_SURFACE) ? tri_rec_step(hi) : 2u;  // (its data record; an attribute triangle's three)
       continue;
     }
     if ((FEAT & FEAT_XFORM) && op == OP_PUSH) {
@@ -624,7 +679,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       float t1, t2;
       bool h1, h2 = false;
       if (general) {
-        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
+        const BoundaryHit b1 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, -F32_MAX, F32_MAX);
         h1 = b1.any != 0u, t1 = b1.t;
         if (COUNT) cnt.aabb += b1.n_aabb, cnt.prim += b1.n_prim;
       } else {
@@ -633,7 +688,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
       }
       if (h1) {
         if (general) {
-          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
+          const BoundaryHit b2 = boundary_hit_t<(FEAT & FEAT_TRI) != 0u, (FEAT & FEAT_SURFACE) != 0u>(sc.lo, sc.hi, pc + 1, hi.x, o, d, time, t1 + 0.0001f, F32_MAX);
           h2 = b2.any != 0u, t2 = b2.t;
           if (COUNT) cnt.aabb += b2.n_aabb, cnt.prim += b2.n_prim;
         } else {
@@ -655,6 +710,7 @@ RT_DEV bool hit_top(const DevScene& sc, V3 o, V3 d, float time, float t_near, Sa
               bool accept = !(hi.w & F_UNDER_BVH) || nhits == root_hits || !(best < t);
               if (accept) {
                 rec.t = t, rec.p = vadd(o, smul(t, d)), rec.n = mk(1.f, 0.f, 0.f), rec.mat = hi.z;
+                hit_no_surface(rec);
                 best = t, any = true, tag = depth, nhits++;
               }
             }
@@ -748,6 +804,12 @@ RT_DEV V3 material_texture(const DevScene& sc, uint4 mlo, uint4 mhi, V3 p) {
   return mk(u2f(mlo.x), u2f(mlo.y), u2f(mlo.z));
 }
 
+// Where a material's texture is evaluated for a hit: p -- or, for a material built on rtg_texture_surface (MAT_SURFACE, programs
+// with FEAT_SURFACE alone), the hit's surface coordinates (tu, tv, 0).  The substitution happens HERE, at the call sites of
+// material_texture: texture_eval keeps its signature and its register footprint (see image_eval above).
+RT_DEV V3 texture_point(const HitRec& h, uint4) { return h.p; }
+RT_DEV V3 texture_point(const HitRecS& h, uint4 mhi) { return (mhi.w & MAT_SURFACE) ? mk(h.tu, h.tv, 0.f) : h.p; }
+
 template <bool INLINE_POW = false>
 RT_DEV float schlick(float cos, float ref_idx) {  // material.rs:142-146
   float r0 = (1.f - ref_idx) / (1.f + ref_idx);
@@ -771,7 +833,7 @@ RT_DEV V3 color(const DevScene& sc, V3 o, V3 d, float time, const DevParams& P, 
   V3 accum = mk(0.f, 0.f, 0.f);
   V3 strength = splat(1.f);
   uint32_t bounces = 0;
-  HitRec hit;
+  HitRecOf<FEAT> hit;
   rng.set_event(1);
   while (hit_top<FEAT, COUNT>(sc, o, d, time, P.t_near, rng, hit, cnt)) {
     if (COUNT) cnt.shaded++;
@@ -779,14 +841,14 @@ RT_DEV V3 color(const DevScene& sc, V3 o, V3 d, float time, const DevParams& P, 
     const uint32_t kind = mhi.w & 0xffu;
     const float param = u2f(mlo.w);
     V3 emitted = mk(0.f, 0.f, 0.f);  // material.rs:120-128
-    if (kind == MAT_DIFFUSE_LIGHT) emitted = smul(param, material_texture<FEAT>(sc, mlo, mhi, hit.p));
+    if (kind == MAT_DIFFUSE_LIGHT) emitted = smul(param, material_texture<FEAT>(sc, mlo, mhi, texture_point(hit, mhi)));
     accum = vadd(accum, vmul(strength, emitted));  // lib.rs:76
     V3 nd, att;
     bool scattered = true;
     if (kind == MAT_LAMBERTIAN) {  // material.rs:57-65
       V3 target = vadd(vadd(hit.p, hit.n), in_unit_sphere(rng));
       nd = vsub(target, hit.p);
-      att = material_texture<FEAT>(sc, mlo, mhi, hit.p);
+      att = material_texture<FEAT>(sc, mlo, mhi, texture_point(hit, mhi));
     } else if (kind == MAT_METAL) {  // material.rs:66-80
       V3 refl = reflect(vunit(d), hit.n);
       nd = vadd(refl, smul(param, in_unit_sphere(rng)));
@@ -820,7 +882,7 @@ RT_DEV V3 color(const DevScene& sc, V3 o, V3 d, float time, const DevParams& P, 
       scattered = false;
     } else {  // Isotropic, material.rs:109-116
       nd = in_unit_sphere(rng);
-      att = material_texture<FEAT>(sc, mlo, mhi, hit.p);
+      att = material_texture<FEAT>(sc, mlo, mhi, texture_point(hit, mhi));
     }
     if (!scattered) {  // lib.rs:88-91
       bounces_out = bounces;

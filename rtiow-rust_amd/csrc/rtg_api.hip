@@ -25,6 +25,7 @@
 #include "../../include/rtiow_gpu_rays.h"
 #include "../../include/rtiow_gpu_image.h"
 #include "../../include/rtiow_gpu_mesh.h"
+#include "../../include/rtiow_gpu_surface.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -169,6 +170,7 @@ struct rtg_scene {
   uint32_t features = 0;
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   std::vector<uint8_t> tex_kind;  // kind of every texture record (flat_scene.h TexKind, TEX_EXT): which ids rtg_debug_texture evaluates
+  std::vector<uint32_t> tex_child;  // ... and the child of every TEX_SURFACE id (include/rtiow_gpu_surface.h), the id itself otherwise
   uint64_t bytes = 0;
   std::vector<void*> owned;    // what `upload` allocated: freed when the scene is destroyed
   const uint32_t* d_parent = nullptr;  // the wrapper around every program record (rt_pool_full.h rebuild_hit)
@@ -469,6 +471,7 @@ rtg_id rtg_texture_checker(rtg_builder* b, rtg_id t0, rtg_id t1) {
   if (!b) return bad("null argument");
   if (t0 >= b->sb.textures.size() || t1 >= b->sb.textures.size()) return bad("checker: bad texture handle");
   if (b->sb.textures[t0].kind == TEX_EXT || b->sb.textures[t1].kind == TEX_EXT) return bad("checker: bad texture handle");
+  if (b->sb.textures[t0].kind == TEX_SURFACE || b->sb.textures[t1].kind == TEX_SURFACE) return bad("checker: a surface texture is no checker child");
   HostTexture t;
   t.kind = TEX_CHECKER;
   t.t0 = t0, t.t1 = t1;
@@ -503,6 +506,7 @@ static rtg_id push_material(rtg_builder* b, uint32_t kind, rtg_id tex, const flo
   m.kind = kind;
   if (tex != RTG_INVALID_ID) {
     if (tex >= b->sb.textures.size() || b->sb.textures[tex].kind == TEX_EXT) return bad("material: bad texture handle");
+    if (kind == MAT_ISOTROPIC && b->sb.textures[tex].kind == TEX_SURFACE) return bad("isotropic: a medium has no surface for a surface texture");
     m.tex = tex;
   }
   if (albedo) m.albedo[0] = albedo[0], m.albedo[1] = albedo[1], m.albedo[2] = albedo[2];
@@ -784,6 +788,7 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
   s->n_mat = (uint32_t)fs.mat.size() / 2;
   s->n_tex = fs.n_tex;  // records, not the texels behind them
   for (const HostTexture& t : b->sb.textures) s->tex_kind.push_back((uint8_t)t.kind);
+  for (size_t i = 0; i < b->sb.textures.size(); i++) s->tex_child.push_back(b->sb.textures[i].kind == TEX_SURFACE ? b->sb.textures[i].t0 : (uint32_t)i);
   int rc;
   if ((rc = upload(s, &s->dev.lo, fs.lo.data(), fs.lo.size() * 16)) ||
       (rc = upload(s, &s->dev.hi, fs.hi.data(), fs.hi.size() * 16)) ||
@@ -1236,3 +1241,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 #include "rtg_image.inc"
 
 #include "rtg_mesh.inc"
+
+#include "rtg_surface.inc"

@@ -42,6 +42,11 @@ rtg_id rtg_texture_image(rtg_builder* b, const rtg_image_params* params, uint32_
 int rtg_debug_texture_host(rtg_builder* b, rtg_id texture, size_t n, const float* p, float* out) {
   if (!b || (n && (!p || !out))) return fail(RTG_ERR_INVALID, "null argument");
   if (texture >= b->sb.textures.size() || b->sb.textures[texture].kind == TEX_EXT) return fail(RTG_ERR_INVALID, "rtg_debug_texture_host: bad texture handle");
+  if (b->sb.textures[texture].kind == TEX_SURFACE) {  // include/rtiow_gpu_surface.h: the child's value at (p.x, p.y, 0)
+    std::vector<float> q(p, p + 3 * n);
+    for (size_t i = 0; i < n; i++) q[3 * i + 2] = 0.f;
+    return rtg_debug_texture_host(b, b->sb.textures[texture].t0, n, q.data(), out);
+  }
   const HostTexture& t = b->sb.textures[texture];
   if (t.kind == TEX_CONSTANT) {
     for (size_t i = 0; i < n; i++) out[3 * i] = t.rgb[0], out[3 * i + 1] = t.rgb[1], out[3 * i + 2] = t.rgb[2];
@@ -66,7 +71,14 @@ int rtg_debug_texture(rtg_scene* s, rtg_id texture, size_t n, const float* p, fl
   DevBuf<float> d_p, d_out;
   HIP_TRY(d_p.alloc(3 * n));
   HIP_TRY(d_out.alloc(3 * n));
-  HIP_TRY(hipMemcpy(d_p.p, p, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  if (s->tex_kind[texture] == TEX_SURFACE) {  // include/rtiow_gpu_surface.h: the child's value at (p.x, p.y, 0)
+    std::vector<float> q(p, p + 3 * n);
+    for (size_t i = 0; i < n; i++) q[3 * i + 2] = 0.f;
+    HIP_TRY(hipMemcpy(d_p.p, q.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    texture = s->tex_child[texture];
+  } else {
+    HIP_TRY(hipMemcpy(d_p.p, p, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  }
   hipLaunchKernelGGL(debug_texture_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, s->dev, (uint32_t)texture, n, d_p.p, d_out.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());

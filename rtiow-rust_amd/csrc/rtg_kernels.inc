@@ -4,7 +4,7 @@
 // ===================================================================================================
 constexpr uint32_t FEAT_ALL = FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | FEAT_TEXTURE;
 // a program with none of these bits is lean (BOX / SPHERE / END records only)
-constexpr uint32_t FEAT_NOT_LEAN = FEAT_ALL | FEAT_BOUNDARY | FEAT_TRI;
+constexpr uint32_t FEAT_NOT_LEAN = FEAT_ALL | FEAT_BOUNDARY | FEAT_TRI;  // (FEAT_SURFACE never comes without FEAT_TRI)
 
 __device__ __forceinline__ void flush_counts(const Counts& c, uint32_t draws, unsigned long long* g) {
   // one atomic per counter per wave would be nicer; the instrumented variant is not the timed one
@@ -185,7 +185,7 @@ __global__ void debug_hit_top_kernel(DevScene sc, uint32_t n, const float* rays,
   SampleRng rng;
   rng.init(((uint64_t)seed_hi << 32) | seed_lo, i, 0);
   rng.set_event(1);
-  HitRec h;
+  HitRecOf<FEAT> h;
   Counts cnt = {0, 0, 0, 0};
   bool hit = hit_top<FEAT, false>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t_near, rng, h, cnt);
   float* o = out + 8ull * i;
@@ -193,6 +193,30 @@ __global__ void debug_hit_top_kernel(DevScene sc, uint32_t n, const float* rays,
   o[1] = hit ? h.t : 0.f;
   o[2] = hit ? h.p.x : 0.f, o[3] = hit ? h.p.y : 0.f, o[4] = hit ? h.p.z : 0.f;
   o[5] = hit ? h.n.x : 0.f, o[6] = hit ? h.n.y : 0.f, o[7] = hit ? h.n.z : 0.f;
+  out_mat[i] = hit ? h.mat : 0xffffffffu;
+}
+
+// rtg_debug_hit_surface (include/rtiow_gpu_surface.h): the same with (tu, tv) behind the normal.  Only the FEAT_SURFACE
+// instantiations carry them; every other program answers (0, 0), as the definition says of a world without attribute triangles.
+template <uint32_t FEAT>
+__global__ void debug_hit_surface_kernel(DevScene sc, uint32_t n, const float* rays, uint32_t seed_lo, uint32_t seed_hi, float t_near, float* out,
+                                         uint32_t* out_mat) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 7ull * i;
+  SampleRng rng;
+  rng.init(((uint64_t)seed_hi << 32) | seed_lo, i, 0);
+  rng.set_event(1);
+  HitRecS h;
+  h.tu = 0.f, h.tv = 0.f;
+  Counts cnt = {0, 0, 0, 0};
+  bool hit = hit_top<FEAT, false>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t_near, rng, h, cnt);
+  float* o = out + 10ull * i;
+  o[0] = hit ? 1.f : 0.f;
+  o[1] = hit ? h.t : 0.f;
+  o[2] = hit ? h.p.x : 0.f, o[3] = hit ? h.p.y : 0.f, o[4] = hit ? h.p.z : 0.f;
+  o[5] = hit ? h.n.x : 0.f, o[6] = hit ? h.n.y : 0.f, o[7] = hit ? h.n.z : 0.f;
+  o[8] = hit ? h.tu : 0.f, o[9] = hit ? h.tv : 0.f;
   out_mat[i] = hit ? h.mat : 0xffffffffu;
 }
 

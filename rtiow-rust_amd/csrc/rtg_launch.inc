@@ -54,6 +54,7 @@ static uint64_t owned_pixels(const DevParams& d) {
 template <bool SIZED, typename F>
 static void with_feat(const rtg_scene* s, F&& f) {
   constexpr uint32_t D = FEAT_ALL | FEAT_DEEP;
+  if ((s->features & FEAT_DEEP) && (s->features & FEAT_SURFACE)) return f(std::integral_constant<uint32_t, D | FEAT_TRI | FEAT_SURFACE>{});
   if ((s->features & FEAT_DEEP) && (s->features & FEAT_TRI)) return f(std::integral_constant<uint32_t, D | FEAT_TRI>{});  // (one size: the largest)
   if (s->features & FEAT_DEEP) {
     if constexpr (SIZED) {
@@ -65,6 +66,7 @@ static void with_feat(const rtg_scene* s, F&& f) {
     return f(std::integral_constant<uint32_t, D>{});
   }
   if ((s->features & FEAT_NOT_LEAN) == 0) return f(std::integral_constant<uint32_t, 0u>{});
+  if (s->features & FEAT_SURFACE) return f(std::integral_constant<uint32_t, FEAT_ALL | FEAT_TRI | FEAT_SURFACE>{});  // (attribute triangles: include/rtiow_gpu_surface.h)
   if (s->features & FEAT_TRI) return f(std::integral_constant<uint32_t, FEAT_ALL | FEAT_TRI>{});  // (the only walks with a TRI case)
   return f(std::integral_constant<uint32_t, FEAT_ALL>{});
 }
@@ -610,20 +612,21 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   void (*pool2_kernel)(DevScene, const LaunchConsts*, float*, uint32_t, uint32_t*, unsigned long long*, Pool2Tuning, uint32_t*, const P2Table*) = nullptr;
   // a program with FEAT_TRI: the instantiations that execute OP_TRI records (rt_pool_full.h TRI) -- no LIST ones (launch_slice sends a
   // counts call of such a scene to the baseline kernel) and never the pool-2 kernel (such a scene has no second program)
-  const bool tri = (s->features & FEAT_TRI) != 0;
-  with_bools([&](auto tex_c, auto genb_c, auto list_c, auto tri_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
-    constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value, TR = decltype(tri_c)::value;
+  // ... with FEAT_SURFACE (attribute triangles, include/rtiow_gpu_surface.h): their SURF siblings, chosen the same way
+  const bool tri = (s->features & FEAT_TRI) != 0, surf = (s->features & FEAT_SURFACE) != 0;
+  with_bools([&](auto tex_c, auto genb_c, auto list_c, auto tri_c, auto surf_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
+    constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value, TR = decltype(tri_c)::value, SU = decltype(surf_c)::value;
     if constexpr (TR) {
       if constexpr (!LI) {
-        kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, false, true> : (prog == 1 ? render_full_pool<1, T, COUNT, G, false, true> : render_full_pool<2, T, COUNT, G, false, true>);
-        sync_kernel = render_full_sync<1, T, COUNT, G, false, true>;
+        kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, false, true, SU> : (prog == 1 ? render_full_pool<1, T, COUNT, G, false, true, SU> : render_full_pool<2, T, COUNT, G, false, true, SU>);
+        sync_kernel = render_full_sync<1, T, COUNT, G, false, true, SU>;
       }
-    } else {
+    } else if constexpr (!SU) {
       kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, LI> : (prog == 1 ? render_full_pool<1, T, COUNT, G, LI> : render_full_pool<2, T, COUNT, G, LI>);
       sync_kernel = render_full_sync<1, T, COUNT, G, LI>;
       pool2_kernel = render_full_pool2<T, COUNT, LI>;
     }
-  }, tex, genb, sl.counts, tri);
+  }, tex, genb, sl.counts, tri, surf);
   if (!kernel) return hipErrorInvalidValue;  // (a counts call on a FEAT_TRI program: not routed here)
   // The lock-step kernel (rt_sync_full.h: one path per lane, no stacks, no pools) renders list worlds without a Bvh -- and, by
   // default (option sync = -1), programs whose Bvhs are tiny (<= 32 BOX records: the Criterion scene of benches/scene.rs has 15,

@@ -49,6 +49,7 @@ uint32_t SceneBuilder::add_object(const HostObject& o) {
     case HostObject::SPHERE:
     case HostObject::RECT:
       if (o.mat >= materials.size()) throw BuildError{-1, "object: bad material handle"};
+      if (surface_material(o.mat)) throw BuildError{-1, "object: a material on a surface texture goes on triangles with UVs only"};
       if (o.kind == HostObject::RECT && (o.axis < 0 || o.axis > 2)) throw BuildError{-1, "rect: bad axis"};
       break;
     case HostObject::AND:
@@ -57,10 +58,12 @@ uint32_t SceneBuilder::add_object(const HostObject& o) {
     case HostObject::MEDIUM:
       if (!valid(o.a)) throw BuildError{-1, "constant_medium: bad boundary handle"};
       if (o.mat >= materials.size()) throw BuildError{-1, "constant_medium: bad material handle"};
+      if (surface_material(o.mat)) throw BuildError{-1, "constant_medium: a medium has no surface for a surface texture"};
       break;
     case HostObject::BVH: break;
     case HostObject::TRI:
       if (o.mat >= materials.size()) throw BuildError{-1, "triangle: bad material handle"};
+      if (surface_material(o.mat) && !(triangles[o.a].has & 2u)) throw BuildError{-1, "triangle: a material on a surface texture needs a triangle with UVs"};
       break;
     default:
       if (!valid(o.a)) throw BuildError{-1, "wrapper: bad object handle"};
@@ -257,31 +260,53 @@ static bool make_triangle(const float* v, HostTriangle* tri, const char** why) {
   return true;
 }
 
-uint32_t SceneBuilder::add_triangle(const float* v, uint32_t material) {
+// include/rtiow_gpu_surface.h: the vertex attributes as given -- not normalised, not turned; a zero normal is accepted (the
+// shading falls back to N where the interpolated length is 0); a component that is not finite is refused
+static bool add_attributes(const float* normals9, const float* uvs6, HostTriangle* tri, const char** why) {
+  for (int i = 0; normals9 && i < 9; i++)
+    if (!std::isfinite(normals9[i])) return *why = "triangle: a vertex normal component is not finite", false;
+  for (int i = 0; uvs6 && i < 6; i++)
+    if (!std::isfinite(uvs6[i])) return *why = "triangle: a vertex UV component is not finite", false;
+  tri->has = (normals9 ? 1u : 0u) | (uvs6 ? 2u : 0u);
+  for (int i = 0; i < 9; i++) tri->attr[i] = normals9 ? normals9[i] : 0.f;
+  for (int i = 0; i < 6; i++) tri->attr[9 + i] = uvs6 ? uvs6[i] : 0.f;
+  return true;
+}
+
+uint32_t SceneBuilder::add_triangle(const float* v, uint32_t material, const float* normals9, const float* uvs6) {
   if (material >= materials.size()) throw BuildError{-1, "triangle: bad material handle"};
   HostTriangle tri;
   const char* why = nullptr;
-  if (!make_triangle(v, &tri, &why)) throw BuildError{-1, why};
+  if (!make_triangle(v, &tri, &why) || !add_attributes(normals9, uvs6, &tri, &why)) throw BuildError{-1, why};
   HostObject o;
   o.kind = HostObject::TRI, o.mat = material, o.a = (uint32_t)triangles.size();
   triangles.push_back(tri);
-  return add_object(o);
+  try {
+    return add_object(o);
+  } catch (...) {
+    triangles.pop_back();  // (a surface material on a triangle without UVs: the builder stays as it was)
+    throw;
+  }
 }
 
-uint32_t SceneBuilder::add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah) {
+uint32_t SceneBuilder::add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah,
+                                const float* normals, const float* uvs) {
   if (n_triangles == 0) throw BuildError{-2, "Can't create a BVH from zero objects."};  // bvh.rs:60
   if (material >= materials.size()) throw BuildError{-1, "mesh: bad material handle"};
   if (n_triangles > 0xfffffffeull - objects.size()) throw BuildError{-4, "mesh: more triangles than object ids"};
   std::vector<HostTriangle> tris(n_triangles);  // every triangle is checked before the builder changes
   for (size_t t = 0; t < n_triangles; t++) {
-    float v[9];
+    float v[9], nn[9], uv[6];
     for (int k = 0; k < 3; k++) {
       const uint32_t ix = indices[3 * t + k];
       if (ix >= n_vertices) throw BuildError{-1, "mesh: a vertex index is >= n_vertices"};
       for (int c = 0; c < 3; c++) v[3 * k + c] = vertices[3 * (size_t)ix + c];
+      for (int c = 0; normals && c < 3; c++) nn[3 * k + c] = normals[3 * (size_t)ix + c];
+      for (int c = 0; uvs && c < 2; c++) uv[2 * k + c] = uvs[2 * (size_t)ix + c];
     }
     const char* why = nullptr;
-    if (!make_triangle(v, &tris[t], &why)) throw BuildError{-1, std::string("mesh: ") + why};
+    if (!make_triangle(v, &tris[t], &why) || !add_attributes(normals ? nn : nullptr, uvs ? uv : nullptr, &tris[t], &why))
+      throw BuildError{-1, std::string("mesh: ") + why};
   }
   const size_t n_obj = objects.size(), n_nodes = bvh_nodes.size(), n_tri = triangles.size();
   try {
@@ -310,7 +335,9 @@ void push(FlatScene* s, float a, float b, float c, float d, uint32_t e, uint32_t
 // copies of material facts into a primitive's flag word: MatKind and "reads a non-constant texture"
 static uint32_t mat_flags(const SceneBuilder& b, uint32_t mat) {
   const HostMaterial& m = b.materials[mat];
-  const bool textured = m.tex != 0xffffffffu && b.textures[m.tex].kind != TEX_CONSTANT;
+  uint32_t tex = m.tex;
+  if (tex != 0xffffffffu && b.textures[tex].kind == TEX_SURFACE) tex = b.textures[tex].t0;  // (a surface texture: its child is what is evaluated)
+  const bool textured = tex != 0xffffffffu && b.textures[tex].kind != TEX_CONSTANT;
   return (m.kind << F_MATKIND_SHIFT) | (textured ? F_TEXTURED : 0u);
 }
 
@@ -436,9 +463,18 @@ void SceneBuilder::emit(uint32_t id, bool under_bvh, int depth, FlatScene* out, 
     uint32_t t = id;
     while (objects[t].kind == HostObject::FLIP) flip = !flip, t = objects[t].a;
     if (objects[t].kind == HostObject::TRI) {
-      const float *v = triangles[objects[t].a].v, *r = triangles[objects[t].a].rec;  // v0; e1, e2, N
-      push(out, v[0], v[1], v[2], r[0], fbits(r[1]), fbits(r[2]), objects[t].mat, OP_TRI | (flip ? F_FLIP : 0u) | mat_flags(*this, objects[t].mat));
-      push(out, r[3], r[4], r[5], r[6], fbits(r[7]), fbits(r[8]), 0, OP_EXT);
+      const HostTriangle& ht = triangles[objects[t].a];
+      const float *v = ht.v, *r = ht.rec, *a = ht.attr;  // v0; e1, e2, N; n0, n1, n2, uv0, uv1, uv2
+      const uint32_t attr_flags = ((ht.has & 1u) ? F_TRI_NORMALS : 0u) | ((ht.has & 2u) ? F_TRI_UVS : 0u);
+      push(out, v[0], v[1], v[2], r[0], fbits(r[1]), fbits(r[2]), objects[t].mat, OP_TRI | (flip ? F_FLIP : 0u) | attr_flags | mat_flags(*this, objects[t].mat));
+      if (!attr_flags) {
+        push(out, r[3], r[4], r[5], r[6], fbits(r[7]), fbits(r[8]), 0, OP_EXT);
+      } else {  // include/rtiow_gpu_surface.h: the fifteen attribute floats in word 6 of the data record and two more records
+        push(out, r[3], r[4], r[5], r[6], fbits(r[7]), fbits(r[8]), fbits(a[0]), OP_EXT);
+        push(out, a[1], a[2], a[3], a[4], fbits(a[5]), fbits(a[6]), fbits(a[7]), OP_EXT);
+        push(out, a[8], a[9], a[10], a[11], fbits(a[12]), fbits(a[13]), fbits(a[14]), OP_EXT);
+        out->features |= FEAT_SURFACE;
+      }
       out->features |= FEAT_TRI;
       return;
     }
@@ -842,18 +878,23 @@ void SceneBuilder::finish_materials(FlatScene* out) const {
     float c[3] = {m.albedo[0], m.albedo[1], m.albedo[2]};
     uint32_t texkind = TEX_CONSTANT, tex = 0;
     const bool scatters_with_albedo = m.kind != MAT_DIFFUSE_LIGHT && m.kind != MAT_DIELECTRIC;
+    uint32_t surface = 0u;
     if (m.tex != kNone) {
-      const HostTexture& t = textures[m.tex];
+      // a surface texture (TEX_SURFACE): the record names the CHILD, with MAT_SURFACE beside its kind (flat_scene.h)
+      const bool surf = textures[m.tex].kind == TEX_SURFACE;
+      const uint32_t id = surf ? textures[m.tex].t0 : m.tex;
+      const HostTexture& t = textures[id];
       texkind = t.kind;
-      tex = m.tex;
+      tex = id;
+      surface = surf ? MAT_SURFACE : 0u;
       if (t.kind == TEX_CONSTANT) c[0] = t.rgb[0], c[1] = t.rgb[1], c[2] = t.rgb[2];
       else out->features |= FEAT_TEXTURE;
-      if (scatters_with_albedo) range_of_texture(m.tex);
+      if (scatters_with_albedo) range_of_texture(id);
     } else if (scatters_with_albedo) {
       range_of_constant(c);
     }
     out->mat.push_back(Packet{{fbits(c[0]), fbits(c[1]), fbits(c[2]), fbits(m.param)}});
-    out->mat.push_back(Packet{{tex, 0, 0, m.kind | (texkind << 8)}});
+    out->mat.push_back(Packet{{tex, 0, 0, m.kind | (texkind << 8) | surface}});
   }
   // texture records, then the texels of the images behind them (flat_scene.h TEX_IMAGE): ids keep indexing records
   // (an image's record names its first texel by a 32-bit packet index: a scene whose records and texels together do not fit one
@@ -869,6 +910,9 @@ void SceneBuilder::finish_materials(FlatScene* out) const {
     } else if (t.kind == TEX_EXT) {
       out->tex.push_back(Packet{{fbits(t.m[0]), fbits(t.m[1]), fbits(t.m[2]), fbits(t.m[3])}});
       out->tex.push_back(Packet{{fbits(t.m[4]), fbits(t.m[5]), fbits(t.m[6]), fbits(t.m[7])}});
+    } else if (t.kind == TEX_SURFACE) {  // no record refers to this slot (flat_scene.h): a black constant
+      out->tex.push_back(Packet{{0, 0, 0, 0}});
+      out->tex.push_back(Packet{{0, 0, 0, TEX_CONSTANT}});
     } else {
       out->tex.push_back(Packet{{fbits(t.rgb[0]), fbits(t.rgb[1]), fbits(t.rgb[2]), fbits(t.scale)}});
       out->tex.push_back(Packet{{t.t0, t.t1, 0, t.kind}});

@@ -30,6 +30,10 @@ struct HostObject {
 struct HostTriangle {  // include/rtiow_gpu_mesh.h: the vertices as given (the bounding box is theirs) and the record rt_triangle.h tri_record makes
   float v[9];    // v0, v1, v2
   float rec[9];  // e1, e2, N
+  // include/rtiow_gpu_surface.h: bit 0 = per-vertex normals, bit 1 = per-vertex UVs; attr = n0, n1, n2, (u0, v0), (u1, v1), (u2, v2), as
+  // given, +0 where the triangle has none.  has = 0: a plain triangle, two records as ever (flat_scene.h OP_TRI)
+  uint32_t has = 0;
+  float attr[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 struct HostBvhNode {  // bvh.rs:9-19
@@ -87,8 +91,14 @@ class SceneBuilder {
   uint32_t add_object(const HostObject& o);
   uint32_t add_bvh(const uint32_t* objs, size_t n, float e0, float e1, bool sah = false);
   // include/rtiow_gpu_mesh.h: one triangle (v: 9 floats), and n_triangles of them under one Bvh; a refusal leaves the builder as it was
-  uint32_t add_triangle(const float* v, uint32_t material);
-  uint32_t add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah);
+  // (normals9 / uvs6, normals / uvs: include/rtiow_gpu_surface.h, null = none -- then exactly the plain triangle and mesh)
+  uint32_t add_triangle(const float* v, uint32_t material, const float* normals9 = nullptr, const float* uvs6 = nullptr);
+  uint32_t add_mesh(const float* vertices, size_t n_vertices, const uint32_t* indices, size_t n_triangles, uint32_t material, bool sah,
+                    const float* normals = nullptr, const float* uvs = nullptr);
+  // is `material` built on an rtg_texture_surface texture?  Only a triangle with UVs takes such a material
+  bool surface_material(uint32_t material) const {
+    return material < materials.size() && materials[material].tex < textures.size() && textures[materials[material].tex].kind == TEX_SURFACE;
+  }
   Box3 bounding_box(uint32_t obj, float e0, float e1) const;
   void flatten(const uint32_t* world, size_t n, FlatScene* out) const;
   // The light table of `world` (flat_scene.h LightRect) and, per material, whether it is sampled (scene option light_sampling)

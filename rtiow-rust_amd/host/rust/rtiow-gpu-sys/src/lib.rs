@@ -15,6 +15,8 @@ pub mod image;
 pub mod mesh;
 /// Ray frames (`include/rtiow_gpu_rays.h`): path-trace the caller's rays.
 pub mod rays;
+/// Surface attributes (`include/rtiow_gpu_surface.h`): per-vertex normals and UVs, surface-mapped textures.
+pub mod surface;
 
 pub const RTG_OK: c_int = 0;
 pub const RTG_ERR_INVALID: c_int = -1;

@@ -94,6 +94,45 @@ def cornell_mesh_scene(b, nx, ny, subdivisions=2, sah=False):
     return scene, cam, exposure
 
 
+def surface_test_image(w=8, h=4):
+    """A small image whose every texel differs: what cornell_surface_scene maps on its box mesh."""
+    y, x = np.mgrid[0:h, 0:w]
+    img = np.stack([(x + 1.0) / (w + 1.0), (y + 1.0) / (h + 1.0), 0.25 + 0.5 * ((x + y) % 2)], axis=-1)
+    return img.astype(np.float32)
+
+
+def box_uvs(vertices):
+    """Per-vertex UVs for triangle.box(): (x, y) of the vertex scaled to the unit square.  The faces orthogonal to z show the
+    image once; the others stretch a row or a column of it."""
+    p = np.asarray(vertices, dtype=np.float64)
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    return ((p[:, :2] - lo[:2]) / (hi[:2] - lo[:2])).astype(np.float32)
+
+
+def cornell_surface_scene(b, nx, ny, subdivisions=2, sah=False, image=None, filter=0, box_wrapped=True, smooth=True):
+    """Not in the reference: cornell_mesh_scene with surface attributes (include/rtiow_gpu_surface.h) -- the icosphere with
+    per-vertex normals (smooth shading), the tall box mesh with per-vertex UVs and an image mapped on its surface through
+    Builder.surface, under the reference's own Translate{RotateY}, and an emissive UV-textured triangle below the ceiling.
+    Returns (scene, cam, exposure, info): info names the image texture, its parameters and the box mesh's object id."""
+    from . import image as image_mod, triangle
+    cam, exposure = _cornell_camera(b.be, nx, ny)
+    scene = cornell_box(b)
+    white = b.lambertian(b.constant(vfrom(0.73)))
+    vs, fs, ns, _ = triangle.icosphere_attr(subdivisions, radius=82.5, centre=(212.5, 82.5, 147.5))
+    scene.append(b.mesh(vs, fs, white, sah=sah, normals=ns if smooth else None))
+    img = surface_test_image() if image is None else image
+    prm = image_mod.planar((1.0, 0.0, 0.0), 0.0, (0.0, 1.0, 0.0), 0.0, filter=filter)   # ordinary UV mapping: v up, row 0 at the top
+    tex = b.image(img, prm)
+    mapped = b.lambertian(b.surface(tex))
+    vb, fb = triangle.box((0.0, 0.0, 0.0), (165.0, 330.0, 165.0))
+    box = b.mesh(vb, fb, mapped, sah=sah, uvs=box_uvs(vb))
+    scene.append(b.translate(v(265.0, 0.0, 295.0), b.rotate_y(15.0, box)) if box_wrapped else box)
+    glow = b.diffuse_light(b.surface(b.image(surface_test_image(4, 4), prm)), 4.0)
+    scene.append(b.triangle_attr(v(100.0, 500.0, 100.0), v(200.0, 500.0, 100.0), v(100.0, 500.0, 200.0), glow,
+                                 uvs=((0.0, 0.0), (1.0, 0.0), (0.0, 1.0))))
+    return scene, cam, exposure, {"image": img, "params": prm, "texture": tex, "box": box}
+
+
 def motion_test(b, nx, ny):
     """main.rs:33-67"""
     cam, exposure = _cornell_camera(b.be, nx, ny)

@@ -9,7 +9,12 @@ under a time limit.
     choice: the full-feature pool kernel, or the lock-step kernel where launch_full_pool picks it); the analytic sphere of the
     same radius in the mesh's place as a yardstick; the host time of rtg_object_mesh; aabb_tests and prim_tests per ray from one instrumented call.
 
+  --surface: the part for include/rtiow_gpu_surface.h instead -- in both worlds the 320-triangle icosphere flat against smooth (per-vertex
+    normals) with the 81 920-triangle flat icosphere beside them, a planar image against the surface-mapped image on the same
+    mesh, and the host time of rtg_object_mesh_attr.
+
   python tools/mesh_cost.py
+  python tools/mesh_cost.py --surface
   python tools/mesh_cost.py --nx 64 --ny 64 --ns 4 --reps 2 --subdivisions 2 4
 """
 import argparse
@@ -81,6 +86,47 @@ def measure(nx, ny, ns, reps, subdivisions, sah_max):
     print(json.dumps(out), flush=True)
 
 
+def measure_surface(nx, ny, ns, reps):
+    """The part for surface attributes: production kernels only (scene option kernel = 3)."""
+    pkg = graft.load_package()
+    gpu = pkg.load()
+    S, T, I = pkg.scenes, pkg.triangle, pkg.image
+    img = np.random.RandomState(3).rand(64, 64, 3).astype(np.float32)
+
+    def build(where, sub, normals, texture):
+        b = gpu.builder()
+        cam, _ = S._cornell_camera(gpu, nx, ny)
+        world = S.cornell_box(b) if where == "cornell" else []
+        v, f, nn, uv = T.icosphere_attr(sub, RADIUS, CENTRE)
+        if texture == "planar":
+            mat = b.lambertian(b.image(img, I.planar((1.0 / 180.0, 0, 0), 0.0, (0, 1.0 / 180.0, 0), 0.0)))
+        elif texture == "surface":
+            mat = b.lambertian(b.surface(b.image(img, I.planar((1, 0, 0), 0.0, (0, 1, 0), 0.0))))
+        else:
+            mat = b.lambertian(b.constant(S.vfrom(0.73)))
+        t0 = time.perf_counter()
+        world.append(b.mesh(v, f, mat, normals=nn if normals else None, uvs=uv if texture == "surface" else None))
+        took = time.perf_counter() - t0
+        return b.scene(world), cam, took
+
+    out = {"frame": "%dx%dx%d" % (nx, ny, ns), "reps": reps, "worlds": {}}
+    for where in ("cornell", "sky"):
+        kw = {"background": SKY} if where == "sky" else {}
+        cases = {"ico320_flat": build(where, 2, False, None), "ico320_smooth": build(where, 2, True, None),
+                 "ico81920_flat": build(where, 6, False, None), "ico320_planar_image": build(where, 2, False, "planar"),
+                 "ico320_surface_image": build(where, 2, False, "surface"), "ico81920_smooth_surface_image": build(where, 6, True, "surface")}
+        t = {name: [] for name in cases}
+        for rep_ in range(reps + 1):
+            for name, (sc, cam, _) in cases.items():
+                sc.set_option("kernel", 3)
+                _, st = sc.par_cast(cam, nx, ny, ns, stats=True, counters=False, **kw)
+                if rep_:
+                    t[name].append(st["kernel_ms"])
+        out["worlds"][where] = {name: {"kernel3_ms": spread(t[name]), "host_build_s": round(took, 3), "records": sc.info()["instructions"]}
+                                for name, (sc, cam, took) in cases.items()}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--nx", type=int, default=256)
@@ -89,13 +135,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--subdivisions", type=int, nargs="+", default=[2, 4, 6])
     ap.add_argument("--sah-max", type=int, default=81920, help="largest mesh that also gets a SAH Bvh")
+    ap.add_argument("--surface", action="store_true", help="the part for include/rtiow_gpu_surface.h")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child and args.surface:
+        measure_surface(args.nx, args.ny, args.ns, args.reps)
+        return
     if args.child:
         measure(args.nx, args.ny, args.ns, args.reps, args.subdivisions, args.sah_max)
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--nx", str(args.nx), "--ny", str(args.ny), "--ns", str(args.ns),
-           "--reps", str(args.reps), "--sah-max", str(args.sah_max), "--subdivisions"] + [str(s) for s in args.subdivisions]
+           "--reps", str(args.reps), "--sah-max", str(args.sah_max), "--subdivisions"] + [str(s) for s in args.subdivisions] + (["--surface"] if args.surface else [])
     try:
         rc = subprocess.run(cmd, timeout=STEP_TIMEOUT_S).returncode
     except subprocess.TimeoutExpired:
