@@ -9,6 +9,7 @@ Layout:
   features.py  the numpy definition of the RTG_FLAG_FEATURES rays (subpixel_rays) and of the planes' fold
   background.py the numpy definition of the RTG_FLAG_BACKGROUND colour (sky: constant, or the book's gradient)
   image.py     the numpy definition of the image texture (sample, atan2f) and ways to make one (from_u8, bake)
+  environment.py the numpy definition of the scene's environment (direction, colour), a Radiance .hdr reader / writer, sun_sky
   triangle.py  the numpy definition of the triangle primitive (record, hit, closest, occluded) and ways to make a mesh (icosphere, box, grid, load_obj)
   rays.py      ray generators for ray frames (Scene.cast_rays): the library's own camera rays, restated; equirect / fisheye / ortho
   scenes.py    the reference's scene builders (src/lib.rs, src/main.rs, benches/scene.rs)
@@ -22,7 +23,7 @@ There is NO CPU fallback: load() raises if the HIP library is missing.
 """
 import os
 
-from . import background, capi, denoise, features, image, noise, ppm, rays, scenes, small_rng, triangle  # noqa: F401  (parallel imports torch: import it explicitly)
+from . import background, capi, denoise, environment, features, image, noise, ppm, rays, scenes, small_rng, triangle  # noqa: F401  (parallel imports torch: import it explicitly)
 from .capi import Backend, Camera, Params, Stats, RtError, make_params  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -689,6 +689,26 @@ MESH_SYMBOLS = ["object_triangle", "object_mesh", "debug_triangle_host"]
 # include/rtiow_gpu_surface.h: per-vertex normals and UVs, surface-mapped textures (not part of ABI_SYMBOLS either)
 SURFACE_SYMBOLS = ["object_triangle_attr", "object_mesh_attr", "texture_surface", "debug_triangle_attr_host", "debug_hit_surface"]
 FEAT_SURFACE = 2048   # flat_scene.h: the flattened program holds a triangle with per-vertex normals or UVs
+# include/rtiow_gpu_environment.h: the scene's environment and its probes (not part of ABI_SYMBOLS either)
+ENVIRONMENT_SYMBOLS = ["builder_set_environment", "builder_get_environment", "debug_environment_host", "debug_environment"]
+FEAT_TEXTURE = 8          # flat_scene.h: a non-constant texture is referenced, or the scene carries an environment
+FEAT_ENVIRONMENT = 4096   # flat_scene.h: the scene carries an environment
+
+
+class EnvironmentParams(C.Structure):
+    """rtg_environment_params (include/rtiow_gpu_environment.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("texture", C.c_uint32), ("scale", C.c_float * 3), ("rotate_y_degrees", C.c_float),
+                ("reserved_in", C.c_uint32 * 2)]
+
+    @classmethod
+    def new(cls, texture, scale=(1.0, 1.0, 1.0), rotate_y=0.0):
+        p = cls()
+        p.struct_size = C.sizeof(cls)
+        p.texture = INVALID_ID if texture is None else int(texture)
+        for i in range(3):
+            p.scale[i] = float(scale[i])
+        p.rotate_y_degrees = float(rotate_y)
+        return p
 
 
 class ImageParams(C.Structure):
@@ -807,6 +827,11 @@ class Backend:
         f("texture_surface", C.c_uint32, [C.c_void_p, C.c_uint32])
         f("debug_triangle_attr_host", C.c_int, [C.c_size_t, c_f32p, c_f32p, C.c_uint32, c_f32p, C.c_float, c_f32p])
         f("debug_hit_surface", C.c_int, [C.c_void_p, C.c_size_t, c_f32p, C.c_uint64, C.c_float, c_f32p, c_u32p])
+        # include/rtiow_gpu_environment.h (ENVIRONMENT_SYMBOLS)
+        f("builder_set_environment", C.c_int, [C.c_void_p, C.POINTER(EnvironmentParams)])
+        f("builder_get_environment", C.c_int, [C.c_void_p, C.POINTER(EnvironmentParams), c_f32p])
+        f("debug_environment_host", C.c_int, [C.c_void_p, C.c_size_t, c_f32p, c_f32p])
+        f("debug_environment", C.c_int, [C.c_void_p, C.c_size_t, c_f32p, c_f32p])
 
     def _fn(self, name, restype, argtypes):
         try:
@@ -1012,6 +1037,27 @@ class Builder:
         p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
         out = np.empty_like(p)
         self.be.check(self.be._debug_texture_host(self.h, texture, len(p), p.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
+
+    def environment(self, texture, scale=(1.0, 1.0, 1.0), rotate_y=0.0):
+        """rtg_builder_set_environment (include/rtiow_gpu_environment.h): what a ray that leaves the scene sees -- `scale` times
+        `texture` at the point rot_y(unit(d)); an image with image.spherical() is a lat-long map.  texture=None clears; a second
+        call replaces.  Scenes made afterwards carry it."""
+        p = texture if isinstance(texture, EnvironmentParams) else EnvironmentParams.new(texture, scale, rotate_y)
+        self.be.check(self.be._builder_set_environment(self.h, C.byref(p)))
+
+    def get_environment(self):
+        """rtg_builder_get_environment: dict(texture (None when there is none), scale, rotate_y, s, c)."""
+        p, sc = EnvironmentParams(), (C.c_float * 2)()
+        self.be.check(self.be._builder_get_environment(self.h, C.byref(p), sc))
+        return dict(texture=None if p.texture == INVALID_ID else int(p.texture), scale=np.array(list(p.scale), dtype=np.float32),
+                    rotate_y=float(p.rotate_y_degrees), s=np.float32(sc[0]), c=np.float32(sc[1]), struct_size=int(p.struct_size))
+
+    def environment_host(self, d):
+        """rtg_debug_environment_host: E(d) for the directions d [n, 3] on the host (image and constant textures)."""
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+        out = np.empty_like(d)
+        self.be.check(self.be._debug_environment_host(self.h, len(d), d.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
         return out
 
     def set_perlin_tables(self, vecs, perm_x, perm_y, perm_z):
@@ -1640,6 +1686,14 @@ class Scene:
         p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
         out = np.empty_like(p)
         self.be.check(self.be._debug_texture(self.h, texture, len(p), p.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
+        return out
+
+    def debug_environment(self, d):
+        """rtg_debug_environment (include/rtiow_gpu_environment.h): E(d) for the directions d [n, 3] on the scene's device,
+        through the function the kernels' miss branches call.  Every texture kind."""
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+        out = np.empty_like(d)
+        self.be.check(self.be._debug_environment(self.h, len(d), d.ctypes.data_as(c_f32p), out.ctypes.data_as(c_f32p)))
         return out
 
     # ---- ray queries (include/rtiow_gpu_query.h) ---------------------------------------------------------------------

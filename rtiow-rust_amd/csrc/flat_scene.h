@@ -193,6 +193,10 @@ constexpr uint32_t FEAT_TRI = 1024u;   // TRI present (include/rtiow_gpu_mesh.h)
                                        // FEAT_TRI / TRI instantiations of the one-lane family, the full-feature pool kernel and the lock-step kernel
 constexpr uint32_t FEAT_SURFACE = 2048u; // a TRI with F_TRI_NORMALS / F_TRI_UVS present (include/rtiow_gpu_surface.h): always with FEAT_TRI; walked by the
                                        // FEAT_SURFACE / SURF instantiations of the same three kernel families, which carry (tu, tv) beside the hit normal
+constexpr uint32_t FEAT_ENVIRONMENT = 4096u; // the scene carries an environment (include/rtiow_gpu_environment.h): always with FEAT_TEXTURE, so never a lean
+                                       // program, and no second program; the miss branches of the one-lane family's textured instantiations and of the
+                                       // PROG_ENV instantiations of the full-feature pool and lock-step kernels (rt_pool_full.h) read it from the frame
+                                       // parameters (rt_device.h BG_TEXTURE)
 constexpr uint32_t FEAT_BRIGHT_ALBEDO = 64u; // an albedo component may exceed 1 (a constant in (1, 4], or Perlin turbulence, <= 3.47): the pool
                                             // kernels then need max_bounces <= 63 for the strength to stay finite
 constexpr uint32_t FEAT_WIDE_ALBEDO = 32u;  // an albedo component outside [0, 4]: path strength may overflow or change sign, so the pool

@@ -46,6 +46,10 @@ constexpr float F32_MAX = 3.402823466e+38f;
 // What a ray that leaves the scene sees; it travels at the end of the frame parameters (rt_trace.h DevParams) and is read in
 // the miss branch alone.  mode 0 = none: a miss is black and accum is discarded (lib.rs:100), the call without the flag.
 constexpr uint32_t BG_NONE = 0u, BG_CONSTANT = 1u, BG_GRADIENT = 2u;  // (rtg_background.mode + 1)
+// The scene's environment (include/rtiow_gpu_environment.h) in the same seven words, where the call has no block: bottom = scale,
+// top = (the texture id's bits, s, c).  Only the instantiations that can reach a texture read it (rt_trace.h miss_colour_scene);
+// background_colour below never sees it.
+constexpr uint32_t BG_TEXTURE = 3u;
 struct Background {
   uint32_t mode;
   float bottom[3], top[3];

@@ -260,7 +260,7 @@ RT_DEV V3 color_ls(const DevScene& sc, const LightTable& lt, V3 o, V3 d, float t
     rng.set_event(bounces + 1);
   }
   bounces_out = bounces;
-  if (P.bg.mode != BG_NONE) return miss_colour(P.bg, accum, strength, d);
+  if (P.bg.mode != BG_NONE) return miss_colour_scene<FEAT>(sc, P.bg, accum, strength, d);  // (the environment too: at full weight, never sampled)
   return accum;
 }
 

@@ -204,7 +204,11 @@ RT_DEV void full_push_finished(const QueueRsrc qr, uint32_t& s_count, uint32_t& 
 // walk only steps further (exec_op under RT_DEFER_HIT keeps (t, record pc) as for every hit); rebuild_hit recomputes u, v from the
 // primitive-space ray it already has and returns the shading normal and (tu, tv), which the shade pass hands to a surface-mapped
 // texture in place of p.
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>
+// PROG + PROG_ENV (only with TEX): the instantiations for scenes that carry an environment (include/rtiow_gpu_environment.h;
+// FEAT_ENVIRONMENT): a ray that hit nothing fetches E(d) where a hit fetches its texture value, and the miss branch books it.  A bit
+// of the first template argument, so that every other instantiation keeps its name and its code, byte for byte.
+constexpr int PROG_ENV = 4;
+template <int PROGE, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_pool(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
@@ -213,6 +217,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
   // TEX = the scene references a checker / Perlin texture: only then is texture_eval (and its register
   // footprint) compiled in
   constexpr uint32_t FEAT = FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | (TEX ? FEAT_TEXTURE : 0u);
+  constexpr int PROG = PROGE & 3;
+  constexpr bool ENV = TEX && (PROGE & PROG_ENV) != 0;
   extern __shared__ uint4 s_mem[];
   constexpr uint32_t OP_SLOW_LAST = (uint32_t)OP_SEG;  // records a slow pass executes: SPHERE .. SEG (BEND only occurs in GENB programs)
   constexpr uint32_t STACK_LEVELS = GENB ? 2 * MAX_XFORM_DEPTH : MAX_XFORM_DEPTH;   // a boundary stream nests below the medium's own wrappers
@@ -477,6 +483,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
             else mlo = sc.mat[2 * hm], mhi = sc.mat[2 * hm + 1];
             if constexpr (SURF) texval = material_texture<PASS_FEAT>(sc, mlo, mhi, (mhi.w & MAT_SURFACE) ? mk(s_tu, s_tv, 0.f) : p);
             else texval = material_texture<PASS_FEAT>(sc, mlo, mhi, p);  // = albedo / emission colour for constant textures
+          } else if constexpr (ENV) {  // a miss under the scene's environment (rt_trace.h environment_colour): E(d), fetched here for the same reason
+            if (P.bg.mode == BG_TEXTURE) texval = environment_colour(sc, load_const(&lc->P.bg), sd);
           }
           strength = mk(SQ_LD_F(SQ_STRENGTH, j), SQ_LD_F(SQ_STRENGTH + 1, j), SQ_LD_F(SQ_STRENGTH + 2, j));
           bounces = SQ_LD_U(SQ_BOUNCES, j), s = SQ_LD_U(SQ_SAMPLE, j);
@@ -558,8 +566,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
                 lpt_on = s < cm.lpt_samples && bounces == cm.lpt_deep;  // phase 1 of the cost-ordered queue (rt_pool.h)
               }
             }
-          } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the miss sees the background (rt_device.h)
-            result = miss_colour(load_const(&lc->P.bg), accum, strength, sd);
+          } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND, or the scene's environment (ENV alone): the miss sees it (rt_device.h)
+            result = miss_colour_fetched<ENV>(load_const(&lc->P.bg), accum, strength, sd, texval);
           }
           if (COUNT) total_draws += rng.draws;
           if (COUNT) trd += rng.draws;

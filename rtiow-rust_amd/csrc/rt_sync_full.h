@@ -10,12 +10,14 @@
 
 namespace rtg {
 
-template <int PROG, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>  // (TRI, SURF: as render_full_pool's)
+template <int PROGE, bool TEX, bool COUNT, bool GENB = false, bool LIST = false, bool TRI = false, bool SURF = false>  // (TRI, SURF, PROG_ENV: as render_full_pool's)
 __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_sync(DevScene sc, const LaunchConsts* __restrict__ lc, float* __restrict__ out,
                                                         uint32_t total_work, uint32_t* __restrict__ queue,
                                                         unsigned long long* counters, PoolTuning tune,
                                                         float* __restrict__ g_stack, uint32_t window) {
   constexpr uint32_t FEAT = FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | (TEX ? FEAT_TEXTURE : 0u);
+  constexpr int PROG = PROGE & 3;
+  constexpr bool ENV = TEX && (PROGE & PROG_ENV) != 0;
   extern __shared__ uint4 s_mem[];
   constexpr uint32_t OP_SLOW_LAST = (uint32_t)OP_SEG;  // SPHERE .. SEG (this kernel steps over OP_SEG: it hoists nothing)
   constexpr uint32_t STACK_LEVELS = GENB ? 2 * MAX_XFORM_DEPTH : MAX_XFORM_DEPTH;
@@ -101,6 +103,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
           mlo = sc.mat[2 * hm], mhi = sc.mat[2 * hm + 1];
           if constexpr (SURF) texval = material_texture<FEAT>(sc, mlo, mhi, (mhi.w & MAT_SURFACE) ? mk(h_tu, h_tv, 0.f) : p);
           else texval = material_texture<FEAT>(sc, mlo, mhi, p);
+        } else if constexpr (ENV) {  // a miss under the scene's environment (rt_trace.h environment_colour): E(d), fetched where a hit's texture value is
+          if (P.bg.mode == BG_TEXTURE) texval = environment_colour(sc, load_const(&lc->P.bg), d);
         }
         const V3 sd = d;
         SampleRng rng;
@@ -171,8 +175,8 @@ __global__ __launch_bounds__(TEX ? RT_FULL_TEX_THREADS : 1024) void render_full_
               lpt_on = ps < cm.lpt_samples && bounces == cm.lpt_deep;
             }
           }
-        } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND: the miss sees the background (rt_device.h)
-          result = miss_colour(load_const(&lc->P.bg), mk(0.f, 0.f, 0.f), strength, sd);
+        } else if (P.bg.mode != BG_NONE) {  // RTG_FLAG_BACKGROUND, or the scene's environment (ENV alone): the miss sees it (rt_device.h)
+          result = miss_colour_fetched<ENV>(load_const(&lc->P.bg), mk(0.f, 0.f, 0.f), strength, sd, texval);
         }
         if (COUNT) total_draws += rng.draws, tr_draws += rng.draws;
         if (ended) {

@@ -3,6 +3,7 @@
 #pragma once
 #include "flat_scene.h"
 #include "rt_device.h"
+#include "rt_environment.h"
 #include "rt_image.h"
 #include "rt_sphere_hit.h"
 #include "rt_triangle.h"
@@ -797,6 +798,36 @@ __device__ __attribute__((noinline)) V3 texture_eval(const DevScene& sc, uint32_
   }
 }
 
+// E(d) of the scene's environment (include/rtiow_gpu_environment.h) for the direction d of a ray that left the scene: the
+// texture's value at the POINT q = rot(d / |d|) (rt_environment.h), times the scale.  bg.mode is BG_TEXTURE (rt_device.h).
+// Out of line like texture_eval, which it calls: the miss branch of a kernel that can reach it gains a call and no more.
+__device__ __attribute__((noinline)) V3 environment_colour(const DevScene& sc, Background bg, V3 d) {
+  float q[3];
+  environment_direction(d.x, d.y, d.z, bg.top[1], bg.top[2], q);
+  const V3 t = texture_eval(sc, __float_as_uint(bg.top[0]), mk(q[0], q[1], q[2]));
+  return vmul(mk(bg.bottom[0], bg.bottom[1], bg.bottom[2]), t);
+}
+// miss_colour (rt_device.h) for a kernel that walks a scene: the BG_TEXTURE case and its texture_eval call exist only in the
+// instantiations that can reach a texture; every other one is miss_colour itself, instruction for instruction.
+template <uint32_t FEAT>
+RT_DEV V3 miss_colour_scene(const DevScene& sc, const Background& bg, V3 accum, V3 strength, V3 d) {
+  if constexpr ((FEAT & FEAT_TEXTURE) != 0u) {
+    if (bg.mode == BG_TEXTURE) return vadd(accum, vmul(strength, environment_colour(sc, bg, d)));
+  }
+  return miss_colour(bg, accum, strength, d);
+}
+// The same in two steps, for the pool kernels, whose shade passes fetch every texture value FIRST, while almost nothing is live
+// across the out-of-line call (rt_pool_full.h): there `env` = environment_colour for a ray that hit nothing, and here the sample
+// colour of the miss from it.  ENV: the kernel's environment instantiation (rt_pool_full.h PROG_ENV); every other one is
+// miss_colour itself, instruction for instruction.
+template <bool ENV>
+RT_DEV V3 miss_colour_fetched(const Background& bg, V3 accum, V3 strength, V3 d, V3 env) {
+  if constexpr (ENV) {
+    if (bg.mode == BG_TEXTURE) return vadd(accum, vmul(strength, env));
+  }
+  return miss_colour(bg, accum, strength, d);
+}
+
 // material's texture value at p: inlined colour for constant textures, table walk otherwise
 template <uint32_t FEAT>
 RT_DEV V3 material_texture(const DevScene& sc, uint4 mlo, uint4 mhi, V3 p) {
@@ -898,7 +929,7 @@ RT_DEV V3 color(const DevScene& sc, V3 o, V3 d, float time, const DevParams& P, 
     rng.set_event(bounces + 1);
   }
   bounces_out = bounces;
-  if (P.bg.mode != BG_NONE) return miss_colour(P.bg, accum, strength, d);  // RTG_FLAG_BACKGROUND: the miss sees the background
+  if (P.bg.mode != BG_NONE) return miss_colour_scene<FEAT>(sc, P.bg, accum, strength, d);  // RTG_FLAG_BACKGROUND, or the scene's environment: the miss sees it
   return mk(0.f, 0.f, 0.f);  // lib.rs:100
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/rtiow_gpu_image.h"
 #include "../../include/rtiow_gpu_mesh.h"
 #include "../../include/rtiow_gpu_surface.h"
+#include "../../include/rtiow_gpu_environment.h"
 #include "rt_pool.h"
 #include "rt_box_plan.h"
 #include "rt_camera_probe.h"
@@ -171,6 +172,9 @@ struct rtg_scene {
   uint32_t n_prog = 0, n_mat = 0, n_tex = 0;
   std::vector<uint8_t> tex_kind;  // kind of every texture record (flat_scene.h TexKind, TEX_EXT): which ids rtg_debug_texture evaluates
   std::vector<uint32_t> tex_child;  // ... and the child of every TEX_SURFACE id (include/rtiow_gpu_surface.h), the id itself otherwise
+  // The environment the builder carried when the scene was made (include/rtiow_gpu_environment.h), as the kernels read it from the
+  // frame parameters of a call without an RTG_FLAG_BACKGROUND block (rt_device.h BG_TEXTURE); mode BG_NONE: the scene has none
+  Background env_bg{BG_NONE, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
   uint64_t bytes = 0;
   std::vector<void*> owned;    // what `upload` allocated: freed when the scene is destroyed
   const uint32_t* d_parent = nullptr;  // the wrapper around every program record (rt_pool_full.h rebuild_hit)
@@ -575,10 +579,15 @@ rtg_id rtg_object_scale(rtg_builder* b, const float factor[3], rtg_id object) {
   if (!factor) return bad("null argument");
   return wrapper(b, HostObject::SCALE, factor, object);
 }
-rtg_id rtg_object_rotate_y(rtg_builder* b, float degrees, rtg_id object) {
-  // object.rs:477-484: radians = degrees * PI / 180; sin/cos via the platform libm (host-side setup)
+// object.rs:477-484: radians = degrees * PI / 180; sin/cos via the platform libm (host-side setup).  The one place the pair is
+// made: rtg_object_rotate_y and rtg_builder_set_environment (rtg_environment.inc)
+static void rotate_y_pair(float degrees, float* s, float* c) {
   float radians = degrees * 3.14159265358979323846f / 180.f;
-  float sc[3] = {sinf(radians), cosf(radians), 0.f};
+  *s = sinf(radians), *c = cosf(radians);
+}
+rtg_id rtg_object_rotate_y(rtg_builder* b, float degrees, rtg_id object) {
+  float sc[3] = {0.f, 0.f, 0.f};
+  rotate_y_pair(degrees, &sc[0], &sc[1]);
   return wrapper(b, HostObject::ROTATE_Y, sc, object);
 }
 rtg_id rtg_object_and(rtg_builder* b, rtg_id o0, rtg_id o1) {
@@ -789,6 +798,13 @@ int rtg_scene_create(rtg_builder* b, const rtg_id* world, size_t n, int device, 
   s->n_tex = fs.n_tex;  // records, not the texels behind them
   for (const HostTexture& t : b->sb.textures) s->tex_kind.push_back((uint8_t)t.kind);
   for (size_t i = 0; i < b->sb.textures.size(); i++) s->tex_child.push_back(b->sb.textures[i].kind == TEX_SURFACE ? b->sb.textures[i].t0 : (uint32_t)i);
+  if (fs.features & FEAT_ENVIRONMENT) {  // include/rtiow_gpu_environment.h: the builder's environment at this moment
+    const SceneBuilder::Environment& ev = b->sb.environment;
+    s->env_bg.mode = BG_TEXTURE;
+    for (int c = 0; c < 3; c++) s->env_bg.bottom[c] = ev.scale[c];
+    std::memcpy(&s->env_bg.top[0], &ev.texture, sizeof(uint32_t));
+    s->env_bg.top[1] = ev.s, s->env_bg.top[2] = ev.c;
+  }
   int rc;
   if ((rc = upload(s, &s->dev.lo, fs.lo.data(), fs.lo.size() * 16)) ||
       (rc = upload(s, &s->dev.hi, fs.hi.data(), fs.hi.size() * 16)) ||
@@ -979,7 +995,15 @@ int rtg_scene_set_option(rtg_scene* s, const char* name, int value) {
     s->ray_pool = value;
   }
   else if (k == "small_frames") s->small_frames = value;        // 0: one geometry for every frame size (measurement switch)
-  else if (k == "verbose") s->verbose = value;                  // print launch geometry / schedule statistics to stderr
+  else if (k == "verbose") {                                    // print launch geometry / schedule statistics to stderr
+    s->verbose = value;
+    if (value && s->env_bg.mode == BG_TEXTURE) {
+      uint32_t id;
+      std::memcpy(&id, &s->env_bg.top[0], sizeof(id));
+      fprintf(stderr, "[rtg] environment: texture %u, scale (%g, %g, %g), (s, c) = (%.9g, %.9g)\n", id, s->env_bg.bottom[0], s->env_bg.bottom[1], s->env_bg.bottom[2],
+              s->env_bg.top[1], s->env_bg.top[2]);
+    }
+  }
   else if (k == "window") s->window = value;                    // full-feature kernel: records staged in LDS, -1 = automatic
   else if (k == "box_leave") s->pool_tune.box_leave = s->full_tune.box_leave = s->sync_tune.box_leave = u;
   else if (k == "refill_min") s->pool_tune.refill_min = s->full_tune.refill_min = s->sync_tune.refill_min = u;
@@ -1041,7 +1065,7 @@ static int check_params(const rtg_scene* s, const rtg_camera* camera, const rtg_
   if (d.tile_w % 8u || d.tile_h % 8u) return fail(RTG_ERR_INVALID, "tile_w / tile_h must be multiples of 8");
   d.nranks = p->nranks ? p->nranks : 1u;
   d.rank = p->rank;
-  d.bg = Background{BG_NONE, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // (RTG_FLAG_BACKGROUND: the entry points fill it in once they have read the block)
+  d.bg = s->env_bg;  // the scene's environment, BG_NONE without one (RTG_FLAG_BACKGROUND: the entry points put the block in its place once they have read it)
   if (d.rank >= d.nranks) return fail(RTG_ERR_INVALID, "rank >= nranks");
   if ((p->flags & RTG_FLAG_RESUME) && p->sample_begin > p->ns) return fail(RTG_ERR_INVALID, "RTG_FLAG_RESUME: sample_begin > ns");
   if ((p->flags & RTG_FLAG_RETIRE) && (~p->flags & (RTG_FLAG_SAMPLE_COUNTS | RTG_FLAG_SUM_SQUARES)))
@@ -1243,3 +1267,5 @@ int rtg_par_cast(rtg_scene* s, const rtg_camera* camera, const rtg_params* param
 #include "rtg_mesh.inc"
 
 #include "rtg_surface.inc"
+
+#include "rtg_environment.inc"

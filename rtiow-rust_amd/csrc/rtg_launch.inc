@@ -614,9 +614,18 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
   // counts call of such a scene to the baseline kernel) and never the pool-2 kernel (such a scene has no second program)
   // ... with FEAT_SURFACE (attribute triangles, include/rtiow_gpu_surface.h): their SURF siblings, chosen the same way
   const bool tri = (s->features & FEAT_TRI) != 0, surf = (s->features & FEAT_SURFACE) != 0;
-  with_bools([&](auto tex_c, auto genb_c, auto list_c, auto tri_c, auto surf_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
+  // ... with FEAT_ENVIRONMENT (include/rtiow_gpu_environment.h): the PROG_ENV instantiations (rt_pool_full.h), which exist with TEX and
+  // without GENB and LIST alone (launch_slice sends the other frames of such a scene to the baseline kernel); no pool-2 kernel
+  const bool env = (s->features & FEAT_ENVIRONMENT) != 0;
+  with_bools([&](auto tex_c, auto genb_c, auto list_c, auto tri_c, auto surf_c, auto env_c) {  // (a counts call: the LIST variants; the pool-2 kernel has no GENB one)
     constexpr bool T = decltype(tex_c)::value, G = decltype(genb_c)::value, LI = decltype(list_c)::value, TR = decltype(tri_c)::value, SU = decltype(surf_c)::value;
-    if constexpr (TR) {
+    if constexpr (decltype(env_c)::value) {
+      if constexpr (T && !G && !LI && (TR || !SU)) {
+        constexpr int E = PROG_ENV;
+        kernel = prog == 0 ? render_full_pool<0 + E, true, COUNT, false, false, TR, SU> : (prog == 1 ? render_full_pool<1 + E, true, COUNT, false, false, TR, SU> : render_full_pool<2 + E, true, COUNT, false, false, TR, SU>);
+        sync_kernel = render_full_sync<1 + E, true, COUNT, false, false, TR, SU>;
+      }
+    } else if constexpr (TR) {
       if constexpr (!LI) {
         kernel = prog == 0 ? render_full_pool<0, T, COUNT, G, false, true, SU> : (prog == 1 ? render_full_pool<1, T, COUNT, G, false, true, SU> : render_full_pool<2, T, COUNT, G, false, true, SU>);
         sync_kernel = render_full_sync<1, T, COUNT, G, false, true, SU>;
@@ -626,8 +635,8 @@ static hipError_t launch_full_pool(rtg_scene* s, const DevCamera& cam, const Dev
       sync_kernel = render_full_sync<1, T, COUNT, G, LI>;
       pool2_kernel = render_full_pool2<T, COUNT, LI>;
     }
-  }, tex, genb, sl.counts, tri, surf);
-  if (!kernel) return hipErrorInvalidValue;  // (a counts call on a FEAT_TRI program: not routed here)
+  }, tex, genb, sl.counts, tri, surf, env);
+  if (!kernel) return hipErrorInvalidValue;  // (a counts call on a FEAT_TRI program, a counts call or a FEAT_BOUNDARY program under an environment: not routed here)
   // The lock-step kernel (rt_sync_full.h: one path per lane, no stacks, no pools) renders list worlds without a Bvh -- and, by
   // default (option sync = -1), programs whose Bvhs are tiny (<= 32 BOX records: the Criterion scene of benches/scene.rs has 15,
   // volume_test under bvh::from_scene 5; a box loop has nothing to batch there) and frames with fewer work items than the chip has
@@ -861,8 +870,11 @@ static hipError_t launch_slice(rtg_scene* s, const DevCamera& cam, const DevPara
   // scene option light_sampling: the one-lane-per-pixel family in every case, whatever options kernel, bvh4 and the pool thresholds say
   // FEAT_TRI: the full-feature pool kernel and the lock-step kernel have instantiations that execute the record (rt_pool_full.h TRI);
   // their LIST variants do not exist, so a counts call of such a scene renders on the baseline kernel
+  // FEAT_ENVIRONMENT: the pool kernels' environment instantiations (rt_pool_full.h PROG_ENV) exist without LIST and GENB: a counts
+  // call of such a scene, and every frame of one with FEAT_BOUNDARY, renders on the baseline kernel
   const bool pool_ok = accum_zero && s->kernel_version >= 3 && d.nx <= 0xffffu && d.ny <= 0xffffu && !(s->features & FEAT_DEEP) && !s->light_sampling &&
-                       !((s->features & FEAT_TRI) && sl.counts);
+                       !((s->features & FEAT_TRI) && sl.counts) &&
+                       !((s->features & FEAT_ENVIRONMENT) && (sl.counts || (s->features & FEAT_BOUNDARY)));
   if (pool_ok) {  // (launch_full_pool names the kernel it picks)
     s->cx->last_kernel = geom != 0 ? KernelKind::full_pool : KernelKind::lean_pool;
     return geom != 0 ? launch_full_pool<COUNT>(s, cam, d, d_out, stream, sl) : launch_pool<COUNT>(s, cam, d, d_out, stream, sl);

@@ -598,10 +598,14 @@ void SceneBuilder::flatten(const uint32_t* world, size_t n, FlatScene* out) cons
   flatten_program(world, n, out, 0, 0);
   bool has_box = false;
   for (const Packet& h : out->hi) has_box |= (h.w[3] & 0xffu) == OP_BOX;
-  const bool full_pool = has_box && (out->features & (FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | FEAT_TEXTURE | FEAT_BOUNDARY)) != 0u &&
+  // An environment (include/rtiow_gpu_environment.h) makes the scene a textured one -- a lean program too, which then renders on
+  // the full-feature pool kernel -- and it gets no second program: the pool-2 kernel has no texture in its miss branch.
+  const bool env = environment.texture != kNone;
+  const bool full_pool = has_box && ((out->features & (FEAT_XFORM | FEAT_MEDIUM | FEAT_RECT | FEAT_TEXTURE | FEAT_BOUNDARY)) != 0u || env) &&
                          !(out->features & (FEAT_DEEP | FEAT_TRI));  // (a TRI: the one-lane family, flat_scene.h OP_TRI)
   if (hoist_segments && full_pool && seg1 > seg0) flatten_program(world, n, out, seg0, seg1);
-  if (full_pool) (void)flatten_pool2(world, n, out);  // the second program, when the world has the shape for it
+  if (full_pool && !env) (void)flatten_pool2(world, n, out);  // the second program, when the world has the shape for it
+  if (env) out->lo2.clear(), out->hi2.clear(), out->p2 = P2Table{}, out->features |= FEAT_TEXTURE | FEAT_ENVIRONMENT;
   if (out->features & FEAT_DEEP) {  // which instantiation of the general walk this graph needs (flat_scene.h)
     if (out->deep_wrappers <= DEEP_FEW_WRAPPERS) out->features |= FEAT_DEEP_FEW_WRAPPERS;
     if (out->deep_media <= 1) out->features |= FEAT_DEEP_ONE_LEVEL;

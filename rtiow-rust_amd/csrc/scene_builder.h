@@ -86,6 +86,13 @@ class SceneBuilder {
   std::array<float, 1024> perlin_vecs{};
   std::array<uint8_t, 768> perlin_perm{};
   bool has_perlin = false;
+  // include/rtiow_gpu_environment.h: what a ray that leaves the scene sees; texture = 0xffffffff: none.  (s, c) from the degrees
+  // by rotate_y_pair (rtg_api.hip), the pair rtg_object_rotate_y makes.
+  struct Environment {
+    uint32_t texture = 0xffffffffu;
+    float scale[3] = {1.f, 1.f, 1.f};
+    float degrees = 0.f, s = 0.f, c = 1.f;
+  } environment;
 
   // All return an id or throw BuildError.
   uint32_t add_object(const HostObject& o);

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/rtiow_gpu.h"
+#include "../../include/rtiow_gpu_environment.h"
 #include "../../include/rtiow_gpu_image.h"
 #include "../../include/rtiow_gpu_mesh.h"
 
@@ -259,7 +260,17 @@ struct Image {
   std::vector<float> rgb;  // ny * nx * 3
 };
 
+// Not in the reference (include/rtiow_gpu_environment.h): what a ray that leaves the scene sees -- `scale` times `texture` at the point
+// rot_y(unit(d)).  texture::image with mapping 1 (spherical) about (0, 0, 0) is a lat-long map, row 0 = world +y.  The builder of
+// this header lives inside make_scene, so the environment rides in the CastOptions: rtg_builder_set_environment is called there.
+struct Environment {
+  Texture texture;
+  float scale[3] = {1.f, 1.f, 1.f};
+  float rotate_y_degrees = 0.f;
+};
+
 struct CastOptions {
+  std::shared_ptr<const Environment> environment;  // null: none (a miss is black, or the call's background)
   uint64_t seed = 0xDEADBEEF;
   int device = 0;
   // perlin.rs:24-29 tables (only needed when a perlin texture is used)
@@ -282,6 +293,14 @@ inline SceneHandle make_scene(const Scene& world, const CastOptions& opt) {
   if (opt.perlin_vecs) check(rtg_builder_set_perlin_tables(b, opt.perlin_vecs, opt.perm_x, opt.perm_y, opt.perm_z));
   std::vector<rtg_id> ids;
   for (const auto& o : world) ids.push_back(o.emit(b));
+  if (opt.environment) {
+    rtg_environment_params ep{};
+    ep.struct_size = sizeof(ep);
+    ep.texture = opt.environment->texture.emit(b);
+    for (int c = 0; c < 3; c++) ep.scale[c] = opt.environment->scale[c];
+    ep.rotate_y_degrees = opt.environment->rotate_y_degrees;
+    check(rtg_builder_set_environment(b, &ep));
+  }
   rtg_scene* s = nullptr;
   check(rtg_scene_create(b, ids.data(), ids.size(), opt.device, &s));
   return SceneHandle(s, rtg_scene_destroy);

@@ -9,6 +9,8 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_float, c_int, c_void};
 
+/// The scene's environment (`include/rtiow_gpu_environment.h`): rays that leave the scene see a texture.
+pub mod environment;
 /// Image textures (`include/rtiow_gpu_image.h`): a sampled image as a fourth texture kind.
 pub mod image;
 /// Triangles and meshes (`include/rtiow_gpu_mesh.h`): a third primitive beside Sphere and Rect.

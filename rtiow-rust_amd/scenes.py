@@ -278,3 +278,18 @@ def random_scene(b, nx, ny, rng=None, use_bvh=True, sky="dome"):
     if sky == "background":
         return world, cam, exposure, {"bottom": DOME_COLOUR}
     return world, cam, exposure
+
+
+def book1_environment_scene(b, nx, ny, rng=None, use_bvh=True, sky=None, filter=1, scale=(1.0, 1.0, 1.0), rotate_y=0.0):
+    """Not in the reference: book-1 without its dome, under an environment map (include/rtiow_gpu_environment.h;
+    Builder.environment).  `sky`: a lat-long image float32 [h, w, 3], row 0 = world +y (default: environment.sun_sky(64, 32)).
+    The builder carries the environment when this returns, so the scene made from the world renders under it.
+    Returns (world, camera, exposure, info): info names the image texture and the environment's parameters."""
+    from . import environment as environment_mod, image as image_mod
+    if sky is None:
+        sky = environment_mod.sun_sky(64, 32)
+    world, cam, exposure, _ = random_scene(b, nx, ny, rng=rng, use_bvh=use_bvh, sky="background")
+    prm = image_mod.spherical(filter=filter, wrap_u=image_mod.REPEAT, wrap_v=image_mod.CLAMP)
+    tex = b.image(sky, prm)
+    b.environment(tex, scale=scale, rotate_y=rotate_y)
+    return world, cam, exposure, dict(texture=tex, image=np.asarray(sky, dtype=f32), params=prm, scale=scale, rotate_y=rotate_y)
